@@ -8,7 +8,7 @@ scaling: every rank owns an independent shard of envs and there is no data-path 
 all-gather (RCCL) of the 8-float episodic-return summary at the end of every horizon, inside the timed region (N = 1, one
 process: no process group exists and the "gather" of the one rank's summary is a view — no launch; the summary kernels still run).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Started WITHOUT a launcher and with --gpus N > 1, bench.py starts its own N ranks: it re-executes itself under
@@ -17,25 +17,35 @@ Started WITHOUT a launcher and with --gpus N > 1, bench.py starts its own N rank
 
 The K timed steps run as rollouts of min(K, 25) launches (+ a shorter last one when 25 does not divide K), each followed
 by the episodic summary (eb_episode_summary: two small kernels; --acc-summary: accumulating launches + one fold) and its all-gather; the K-step region is bracketed by barrier +
-synchronize, measured `--repeats` times (default 11) and the MEDIAN is `value` (min / max are reported too).  The
-launches go out either as one hipGraph replay per rollout (eb_plan_*, --graph) or as host calls (--eager); by default
-a short untimed trial picks the faster form and `config.workload` names the one that ran.  Rank 0 prints ONE JSON line:
+synchronize and timed once, so K is the number of timed steps (`--repeats R` times R such regions and the MEDIAN is `value`; min / max
+are reported too).  The launches go out either as one hipGraph replay per rollout (eb_plan_*, --graph) or as host calls (--eager); by default
+a short untimed trial picks the faster form and `config.workload` names the one that ran.
+
+--dump-outputs DIR writes, after the timed region, what the last timed step returned to a caller of rollout_out (rank 0's shard):
+DIR/obses.npy [B, D] (the next observation) and DIR/out5.npy [5, B] (rewards, punish_term_for_training, real_punish_term,
+veh2veh4real, veh2road4real), float32, and DIR/summary.npy [8] (the episodic summary of the last rollout, all ranks).  The inputs are
+seeded, so two builds run with the same arguments can be compared file for file.  Above 64 MB in all, a fixed seeded sample of the
+env rows is written instead (dump_outputs).
+
+A plain run measures the headline alone: `strong`, `roofline.hbm_resident`, `extra` and `cpu_baseline` are null / empty.  --full adds
+them (each takes runs of its own, minutes in all); --no-side / --no-cpu-baseline then leave out a part again.  Rank 0 prints ONE JSON
+line:
 
   roofline      algorithmic bytes per launch (104 + 32 N_veh per env-step) / the rollout kernel's
                 average launch duration from HIP event pairs (eb_event_*) on the launch stream around every rollout of
                 the timed region (inter-kernel gaps included), against the 8 TB/s HBM peak.  The headline working set
                 (two 36 MB obs buffers + outputs) fits the 256 MiB Infinity Cache, so
-  roofline.hbm_resident   repeats the measurement where it cannot: (a) the same kernel and batch size cycling over 8
+  roofline.hbm_resident   (--full) repeats the measurement where it cannot: (a) the same kernel and batch size cycling over 8
                 independent env sets (lane l steps, then lane l+1, ...: 518 MB of other traffic between a line's write
                 and its re-read, 0.9 GB footprint), (b) one batch of 524 288 envs (290 MB per obs buffer), (c) the env sets
                 of (a) dealt to four HIP streams, so that launches of different sets overlap (wall-clock timed);
-  strong        BASELINE configs[3]: 262 144 envs in total, split 262 144 / N per rank (strong scaling; at N = 1 the
+  strong        (--full) BASELINE configs[3]: 262 144 envs in total, split 262 144 / N per rank (strong scaling; at N = 1 the
                 one-GPU reference point of that curve);
-  extra         configs[1] (4 096 x 16, fp32; + `one_launch_forms`: the same 25 steps as ONE gated launch with open gates /
+  extra         (--full) configs[1] (4 096 x 16, fp32; + `one_launch_forms`: the same 25 steps as ONE gated launch with open gates /
                 fed by a second stream, and the open-loop tape), configs[4] (65 536 x 64, fp16 state) and `env_step` — the
                 env-side step of endtoend.py (CrossroadEnd2end.step through eb_env_step, one launch) at 65 536 and 4 096 envs
                 x 16 candidates with its own algorithmic bytes and roofline fraction — on rank 0 at N = 1;
-  cpu_baseline  the CPU oracle (oracle/, plain-C port of the reference path, OpenMP over envs) timed on this box's host
+  cpu_baseline  (--full) the CPU oracle (oracle/, plain-C port of the reference path, OpenMP over envs) timed on this box's host
                 cores on a bounded sample of the same workload, on rank 0 after every timed GPU region (at any N: "next to
                 the reference CPU path ... in the same run"); never part of the GPU path.
   At N > 1 also: roofline.aggregate (sum over ranks of the per-rank achieved GB/s against N x 8 TB/s, with the per-rank
@@ -59,6 +69,8 @@ HBM_PEAK_GBS = 8000.0                            # MI355X_MICROARCH.md: 8 TB/s s
 MALL_BYTES = 256 << 20                           # Infinity Cache
 MAX_PAIRS = 64                                   # HIP event pairs per repeat
 TWO_PASS_SUMMARY = True                          # False: --acc-summary (A/B aid)
+DUMP_MAX_BYTES = 64 * 1000 * 1000                # --dump-outputs: all files together
+FULL_REPEATS = 11                                # --full: the side measurements' repeat counts derive from this unless --repeats is given
 
 
 def alg_bytes_per_env_step(n_veh, f16=False):
@@ -398,6 +410,24 @@ def pmc_traffic(which, *path):
 def roofline_of(alg_bytes, launch_us):
     achieved = alg_bytes / (launch_us * 1e-6) / 1e9
     return achieved, achieved / HBM_PEAK_GBS
+
+
+def dump_outputs(out_dir, shard, last_h, summary):
+    """--dump-outputs: the last timed step's results as a caller of rollout_out receives them — the next obs [B, D] (in `final`: the
+    last launch of every rollout writes there) and the five outputs [5, B] (out5 row last_h - 1 of that rollout) — plus the episodic
+    summary [8].  Above DUMP_MAX_BYTES the same env rows of both arrays are kept: a sorted sample drawn with a fixed seed."""
+    import numpy as np
+    obs = shard.final[0].float().cpu().numpy()
+    out5 = shard.out5[0][last_h - 1].cpu().numpy()
+    n_env = obs.shape[0]
+    keep = (DUMP_MAX_BYTES - (1 << 16)) // (4 * (obs.shape[1] + out5.shape[0]))   # (room for the three files' headers and the summary)
+    if n_env > keep:
+        rows = np.sort(np.random.default_rng(0).choice(n_env, keep, replace=False))
+        obs, out5 = obs[rows], out5[:, rows]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'obses.npy'), np.ascontiguousarray(obs, dtype=np.float32))
+    np.save(os.path.join(out_dir, 'out5.npy'), np.ascontiguousarray(out5, dtype=np.float32))
+    np.save(os.path.join(out_dir, 'summary.npy'), np.asarray(summary, dtype=np.float32))
 
 
 def side_config(torch, dist, model, n_env, n_veh, seed, steps, warmup, repeats, f16=False, lanes=1, use_dist=False,
@@ -945,14 +975,20 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=2000)
     ap.add_argument('--warmup', type=int, default=100)
-    ap.add_argument('--repeats', type=int, default=11, help='timed regions of --steps steps each; the median is reported')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='timed regions of --steps steps each; the median is reported (default 1: --steps is the number of timed steps; '
+                         'the --full side measurements take min(R, 7) / min(R, 5) regions, R = %d by default)' % FULL_REPEATS)
     ap.add_argument('--n-env', type=int, default=N_ENV, help='envs per GPU (default: configs[2])')
     ap.add_argument('--n-veh', type=int, default=N_VEH)
     ap.add_argument('--eager', action='store_true', help='one host launch per step instead of hipGraph replays')
     ap.add_argument('--graph', action='store_true', help='hipGraph replays (default: whichever of the two an untimed trial finds faster)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also the side measurements (hbm_resident / strong / extra) and the cpu_baseline leg; a plain run times the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the last step\'s obses / out5 and the episodic summary as DIR/*.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the cpu_baseline leg')
     ap.add_argument('--cpu-budget-s', type=float, default=18.0, help='seconds of host time the cpu_baseline leg may use')
-    ap.add_argument('--no-side', action='store_true', help='skip hbm_resident / strong / extra (headline line only)')
+    ap.add_argument('--no-side', action='store_true', help='with --full: skip hbm_resident / strong / extra')
     ap.add_argument('--acc-summary', action='store_true',
                     help='A/B aid: the accumulating launches (eb_rollout_step_acc, ABI 5) + one fold per horizon instead of plain launches '
                          '+ eb_episode_summary — same-box A/B, round 5 (profiles/r5_ab_acc_summary.txt): the in-launch accumulation costs '
@@ -969,7 +1005,7 @@ def main():
     global TWO_PASS_SUMMARY
     TWO_PASS_SUMMARY = not args.acc_summary
     n_env, n_veh = args.n_env, args.n_veh
-    if args.steps < 1 or args.repeats < 1:
+    if args.steps < 1 or (args.repeats is not None and args.repeats < 1):
         raise SystemExit('--steps and --repeats must be >= 1')
     if args.shield:
         return shield_bench(args)
@@ -1035,9 +1071,11 @@ def main():
             flag = torch.tensor([1 if tm.eager else 0], dtype=torch.int32, device=dev if backend == 'nccl' else 'cpu')
             dist.broadcast(flag, 0)
             tm.eager = bool(flag.item())
-    r = tm.measure(args.steps, args.warmup, args.repeats)
+    r = tm.measure(args.steps, args.warmup, args.repeats or 1)
     dt = median(r['dt'])
     summary = [float(x) for x in combine_summaries(tm.gathered).tolist()]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, shard, Timer.segments(args.steps)[-1], summary)
     per_rank = gather_floats(torch, dist, [r['launch_us'], float(r['launches_timed'])], dev) if use_dist else \
         [[r['launch_us'], float(r['launches_timed'])]]
     job = {'rccl_ranks': dist.get_world_size(), 'backend': dist.get_backend() + (' (RCCL)' if dist.get_backend() == 'nccl' else '')} \
@@ -1047,10 +1085,11 @@ def main():
     # ---- side measurements (untimed for `value`) ----
     strong = hbm = None
     extra = []
-    if not args.no_side and not args.open_loop:
+    rep_full = args.repeats or FULL_REPEATS
+    if args.full and not args.no_side and not args.open_loop:
         # side measurements: regions of 20 horizons whatever --steps says (a one-horizon region — the driver's --steps 20 — measures its
         # own launch and wake-up latency: fp16 x 64 read 22.7 us per launch that way against 20.1 in a long region)
-        side_steps, side_warm, side_rep = 20 * HORIZON, HORIZON, min(args.repeats, 7)
+        side_steps, side_warm, side_rep = 20 * HORIZON, HORIZON, min(rep_full, 7)
         _MODELS[n_veh] = model
         m32 = model_for(torch, EnvironmentModel, dev, N_VEH)
         per = STRONG_TOTAL // world
@@ -1086,8 +1125,8 @@ def main():
                                                     'rank-to-rank jitter'}
         if world == 1:
             lanes = 8
-            a = side_config(torch, dist, m32, N_ENV, N_VEH, 0, 100, HORIZON, min(args.repeats, 5), lanes=lanes, forms=('eager',))
-            b = side_config(torch, dist, m32, 8 * N_ENV, N_VEH, 7, 100, HORIZON, min(args.repeats, 5))
+            a = side_config(torch, dist, m32, N_ENV, N_VEH, 0, 100, HORIZON, min(rep_full, 5), lanes=lanes, forms=('eager',))
+            b = side_config(torch, dist, m32, 8 * N_ENV, N_VEH, 7, 100, HORIZON, min(rep_full, 5))
             hbm = {'bound': 'hbm', 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                    'achieved': a['achieved_GBs'], 'frac': a['frac'],
                    'exceeds_infinity_cache': 'both: (a) 8 env sets x 65 536 envs stepped round-robin — 7 x 74 MB of other traffic '
@@ -1097,7 +1136,7 @@ def main():
                    'lanes8_x_65536': a, 'single_524288': b,
                    # the same 8 independent env sets dealt to four HIP streams: a set's launch may start while another set's
                    # blocks drain (what one generation of co-resident blocks cannot do for itself; wall-clock timed)
-                   'lanes8_x_65536_four_streams': side_config(torch, dist, m32, N_ENV, N_VEH, 0, 100, HORIZON, min(args.repeats, 5),
+                   'lanes8_x_65536_four_streams': side_config(torch, dist, m32, N_ENV, N_VEH, 0, 100, HORIZON, min(rep_full, 5),
                                                               lanes=lanes, forms=('eager',), streams=4)}
             m16 = model_for(torch, EnvironmentModel, dev, 16)
             extra.append(dict(side_config(torch, dist, m16, 4096, 16, 11, side_steps, side_warm, side_rep),
@@ -1181,7 +1220,7 @@ def main():
             'ranks': world, 'avg_launch_us_min': min(us), 'avg_launch_us_max': max(us), 'avg_launch_us_by_rank': us,
             'note': 'sum over ranks of alg_bytes_per_launch / that rank\'s own event-timed launch duration; `achieved` / `frac` '
                     'above are rank 0\'s'}
-        if not args.no_cpu_baseline:   # rank 0, after every timed GPU region (the other ranks wait at the final barrier)
+        if args.full and not args.no_cpu_baseline:   # rank 0, after every timed GPU region (the other ranks wait at the final barrier)
             line['cpu_baseline'] = cpu_baseline(shard.inp, shard.obs0_f32.cpu().numpy(), n_veh, budget_s=args.cpu_budget_s)
         else:
             line['cpu_baseline'] = None

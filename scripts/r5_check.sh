@@ -18,7 +18,7 @@ for l in open('$OUT/env_step.jsonl'):
 PY
 timeout 300 python scripts/trace_rollout.py --n-env 65536 > $OUT/trace_rollout_65536.txt 2>&1; head -24 $OUT/trace_rollout_65536.txt
 timeout 300 python scripts/trace_rollout.py --n-env 32768 > $OUT/trace_rollout_32768.txt 2>&1; head -24 $OUT/trace_rollout_32768.txt
-timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench_steps20.err; python - <<PY
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench_steps20.err; python - <<PY
 import json
 try:
     d = json.load(open('$OUT/bench_steps20.json'))

@@ -9,7 +9,7 @@ python -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1; echo "
 timeout 600 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "accumulating or plan_graph or episode_summary" > $OUT/pytest_acc.log 2>&1; echo "acc tests rc=$?"; tail -5 $OUT/pytest_acc.log
 timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -4 $OUT/pytest_gpu.log
 timeout 300 ./scripts/micro/chainbench > $OUT/chainbench.txt 2>&1; cat $OUT/chainbench.txt
-timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench_steps20.err; python - <<PY
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench_steps20.err; python - <<PY
 import json
 try:
     d = json.load(open('$OUT/bench_steps20.json'))

@@ -4,7 +4,7 @@ TAG=${1:-r6g}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 python -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1
 t0=$(date +%s.%N)
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench.err; echo "rc=$?"
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench.err; echo "rc=$?"
 t1=$(date +%s.%N); python -c "print(\"bench wall: %.1f s\" % ($t1 - $t0))"
 tail -3 $OUT/bench.err
 python - <<PY

@@ -4,8 +4,8 @@ TAG=${1:-r6chk3}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 python -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1; echo "build rc=$?"
 python scripts/r6_ab_envprio.py 2>&1 | grep -v amdgpu.ids | tee $OUT/ab_envprio.txt
-python bench.py 2> $OUT/bench.err | tail -1 > $OUT/bench.json; echo "bench rc=$?"
-python bench.py --steps 20 --warmup 5 2> $OUT/bench20.err | tail -1 > $OUT/bench_steps20.json; echo "bench20 rc=$?"
+python bench.py --full 2> $OUT/bench.err | tail -1 > $OUT/bench.json; echo "bench rc=$?"
+python bench.py --full --steps 20 --warmup 5 2> $OUT/bench20.err | tail -1 > $OUT/bench_steps20.json; echo "bench20 rc=$?"
 EB_TAG=$TAG python - <<'PY'
 import json, os
 for f in ('bench.json', 'bench_steps20.json'):
