@@ -37,6 +37,14 @@ int fail_hip(const char* what, hipError_t e) {
         if (e_ != hipSuccess) return fail_hip(#call, e_); \
     } while (0)
 
+// scratch of one call: allocated in stream order (hipMallocAsync into p), released in stream order on every return path, after the
+// launches that read it (two streams may drive one handle through the separate launches)
+struct StreamScratch {
+    void* p;
+    hipStream_t s;
+    ~StreamScratch() { if (p) (void)hipFreeAsync(p, s); }
+};
+
 }  // namespace
 
 struct eb_handle_s {
@@ -76,7 +84,6 @@ struct eb_handle_s {
 static hipError_t upload_tables(eb_handle_s* h);
 
 static int obs_dim(const eb_config& c) { return 6 + 3 * (c.n_future + 1) + 4 * c.n_veh; }
-static hipStream_t pick(eb_handle, void* stream) { return (hipStream_t)stream; }   // NULL = the HIP null stream
 
 // Closest-point cell grid.  For every 0.5 m cell C of a grid around the paths and every path k, the
 // index range [lo, hi] of the stride-10 table outside of which no point can be the closest one for
@@ -497,7 +504,7 @@ int eb_f_xu(eb_handle h, int32_t n, const float* states, const float* actions, f
     if (!h || n < 0 || !states || !actions || !next_states) return fail(EB_EINVAL, "eb_f_xu: bad argument");
     if (n == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
-    EB_HIP(eb::launch_f_xu(n, states, actions, tau, next_states, params, pick(h, stream)));
+    EB_HIP(eb::launch_f_xu(n, states, actions, tau, next_states, params, (hipStream_t)stream));
     return EB_OK;
 }
 
@@ -505,7 +512,7 @@ int eb_action_transform(eb_handle h, int32_t n, const float* actions, float* sca
     if (!h || n < 0 || !actions || !scaled) return fail(EB_EINVAL, "eb_action_transform: bad argument");
     if (n == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
-    EB_HIP(eb::launch_action_transform(n, actions, scaled, pick(h, stream)));
+    EB_HIP(eb::launch_action_transform(n, actions, scaled, (hipStream_t)stream));
     return EB_OK;
 }
 
@@ -515,11 +522,10 @@ int eb_compute_rewards(eb_handle h, int32_t n_env, const float* obs, const float
     if (n_env == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
     EB_HIP(eb::launch_rewards(h->cfg.task, n_env, obs_dim(h->cfg), h->cfg.n_future, h->cfg.n_veh, obs, actions, out5,
-                              out_dict16, pick(h, stream)));
+                              out_dict16, (hipStream_t)stream));
     return EB_OK;
 }
 
-// obs_in / obs_out point at fp32 rows, or at binary16 rows when storage_f16 is set
 struct GateArgs {
     const uint32_t* ready;
     uint32_t* done;
@@ -540,6 +546,25 @@ struct ShieldArgs {
     float* punish;
     uint8_t* safe;
     int row, first, last;
+};
+// one launch of the rollout kernels (rollout): the arrays first, then what a caller changes by name — by default a step of
+// rollout_out (raw actions, rewards into out5) on fp32 rows in the tile shape pick_variant chooses
+struct RolloutLaunch {
+    const float* obs_in;                  // fp32 rows, or binary16 rows when storage_f16 is set (obs_out too)
+    float* obs_out;
+    const float* actions;                 // [n_env, 2]; the tape [tape_horizon, n_env, 2] when tape_horizon > 0
+    const int32_t* ref_idx;
+    int32_t path_id;
+    float* out5 = nullptr;                // [5, n_env]; [tape_horizon, 5, n_env] for a tape
+    float* scaled_actions = nullptr;
+    int actions_raw = 1;                  // 1: raw [-1, 1] actions (rollout_out), 0: already scaled
+    int do_rewards = 1;                   // 0: compute_next_obses only
+    int storage_f16 = 0;
+    int tape_horizon = 0;                 // > 0: the whole tape in one launch of the tape kernel
+    const GateArgs* gate = nullptr;       // eb_rollout_gated's step gates (a tape)
+    const AccArgs* acc = nullptr;
+    const ShieldArgs* shield = nullptr;
+    int variant = -1;                     // the tile shape; -1: pick_variant's (eb_rollout_gated: the one gated_blocks chose)
 };
 static int envs_per_tile(eb_handle h, int variant) {
     return std::max(1, std::min(64, eb::fused_tile_records(variant) / h->cfg.n_veh));
@@ -567,7 +592,7 @@ static int pick_variant(eb_handle h, int32_t n_env) {
         variant = 2;
         for (int v = 0; v < 2; ++v) {
             if (v == 0 && 64 * h->cfg.n_veh <= eb::fused_tile_records(1)) continue;
-            const int e = std::max(1, std::min(64, eb::fused_tile_records(v) / h->cfg.n_veh));
+            const int e = envs_per_tile(h, v);
             if ((n_env + e - 1) / e >= 2 * h->n_cu) { variant = v; break; }
         }
     }
@@ -576,7 +601,7 @@ static int pick_variant(eb_handle h, int32_t n_env) {
 
 // Small grids (at most two blocks per CU) keep the stride-10 path tables in LDS for the whole launch: their steps are bound
 // by the env wave's chain of dependent table reads, not by throughput.  Larger ones leave the LDS to occupancy.  ONE
-// decision for the launch (rollout_fused) and for the residency query (gated_blocks): eb_debug_set_stage_paths forces it.
+// decision for the launch (rollout) and for the residency query (gated_blocks): eb_debug_set_stage_paths forces it.
 static bool stage_paths_in_lds(eb_handle h, int grid) {
     return h->stage_paths < 0 ? grid <= 2 * h->n_cu : h->stage_paths != 0;
 }
@@ -592,18 +617,15 @@ static void rollout_sched(eb_handle h, int variant, int grid, int envs_per_tile_
     *rolling = variant != 0 ? 0 : h->sched_rolling >= 0 ? h->sched_rolling : (grid <= 3 * h->n_cu || envs_per_tile_ <= 32);
 }
 
-static int rollout_fused(eb_handle h, int variant, int32_t n_env, const float* obs_in, const float* actions,
-                         const int32_t* ref_idx, int32_t path_id, float* obs_out, float* out5,
-                         float* scaled_actions, int actions_raw, int do_rewards, hipStream_t s, int storage_f16,
-                         int tape_horizon = 0,   // > 0: `actions` is a tape [H, n_env, 2], `out5` is [H, 5, n_env], one launch
-                         const GateArgs* gate = nullptr, const AccArgs* acc = nullptr, const ShieldArgs* shield = nullptr) {
+static int rollout(eb_handle h, int32_t n_env, const RolloutLaunch& r, hipStream_t s) {
     const int NV = h->cfg.n_veh;
-    if (tape_horizon > 0 && !gate) variant = eb::tape_tile_variant(variant, NV, storage_f16);
+    int variant = r.variant >= 0 ? r.variant : pick_variant(h, n_env);
+    if (r.tape_horizon > 0 && !r.gate) variant = eb::tape_tile_variant(variant, NV, r.storage_f16);
     eb::FusedArgs A;
     std::memset(&A, 0, sizeof A);
-    A.storage_f16 = storage_f16;
-    A.obs_in = obs_in; A.actions = actions; A.ref_idx = ref_idx; A.obs_out = obs_out; A.out5 = out5;
-    A.scaled_actions = scaled_actions;
+    A.storage_f16 = r.storage_f16;
+    A.obs_in = r.obs_in; A.actions = r.actions; A.ref_idx = r.ref_idx; A.obs_out = r.obs_out; A.out5 = r.out5;
+    A.scaled_actions = r.scaled_actions;
     A.dt = h->d_pt;
     A.xy10 = reinterpret_cast<const float*>(h->d_red_all);
     A.phi10 = h->d_phi10_all;
@@ -613,24 +635,24 @@ static int rollout_fused(eb_handle h, int variant, int32_t n_env, const float* o
     for (int k = 0; k < 3; ++k) { A.red_off[k] = h->red_off[k]; A.red_len[k] = h->pt.red_len[k]; }
     A.n_paths = h->pt.n_paths;
     A.n_env = n_env; A.obs_dim = obs_dim(h->cfg); A.n_veh = NV; A.n_future = h->cfg.n_future;
-    A.nv_magic = NV == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)NV - 1) / (unsigned)NV);   // 0: item / 1
+    A.nv_magic = eb::div_magic(NV);
     A.envs_per_tile = envs_per_tile(h, variant);
-    A.path_id = path_id;
+    A.path_id = r.path_id;
     A.training = h->cfg.mode == EB_MODE_TRAINING;
-    A.actions_raw = actions_raw;
-    A.do_rewards = do_rewards;
+    A.actions_raw = r.actions_raw;
+    A.do_rewards = r.do_rewards;
     A.trace = h->trace; A.trace_words = h->trace_words; A.scan_one_trip = h->scan_one_trip;
-    if (shield) {
+    if (const ShieldArgs* shield = r.shield) {
         A.shield_punish = shield->punish; A.shield_safe = shield->safe; A.shield_row = shield->row;
         A.shield_first = shield->first; A.shield_last = shield->last;
     }
-    if (gate) {
+    if (const GateArgs* gate = r.gate) {
         A.gate_ready = gate->ready; A.gate_done = gate->done; A.gate_obs = gate->obs_steps; A.gate_status = gate->status;
         A.gate_spin = gate->spin;
     }
     const int grid = (n_env + A.envs_per_tile - 1) / A.envs_per_tile;
-    if (tape_horizon == 0) rollout_sched(h, variant, grid, A.envs_per_tile, &A.rolling, &A.by_progress);
-    if (acc) {   // records are indexed by THIS grid (the same at every step of a rollout: one handle state, one n_env)
+    if (r.tape_horizon == 0) rollout_sched(h, variant, grid, A.envs_per_tile, &A.rolling, &A.by_progress);
+    if (const AccArgs* acc = r.acc) {   // records are indexed by THIS grid (the same at every step of a rollout: one handle state, one n_env)
         // the rollout a workspace belongs to is fixed by its step-0 launch
         eb_handle_s::AccRun* run = nullptr;
         for (auto& r : h->acc_runs) if (r.ws == acc->workspace) run = &r;
@@ -645,19 +667,10 @@ static int rollout_fused(eb_handle h, int variant, int32_t n_env, const float* o
         if (acc->step > 0) { A.prev_out5 = acc->prev_out5; A.prev_rec = acc_records(acc->workspace, acc->step - 1, (size_t)grid); }
         if (acc->step == acc->horizon - 1) A.acc_final = acc_finals(acc->workspace, acc->horizon, (size_t)grid);
     }
-    if (tape_horizon > 0 && stage_paths_in_lds(h, grid)) A.stage_entries = h->red_total + 4;
-    if (tape_horizon > 0) EB_HIP(eb::launch_rollout_tape_fused(h->cfg.task, variant, A, tape_horizon, grid, s));
+    if (r.tape_horizon > 0 && stage_paths_in_lds(h, grid)) A.stage_entries = h->red_total + 4;
+    if (r.tape_horizon > 0) EB_HIP(eb::launch_rollout_tape_fused(h->cfg.task, variant, A, r.tape_horizon, grid, s));
     else EB_HIP(eb::launch_rollout_fused(h->cfg.task, variant, A, grid, s));
     return EB_OK;
-}
-
-static int rollout_common(eb_handle h, int32_t n_env, const float* obs_in, const float* actions,
-                          const int32_t* ref_idx, int32_t path_id, float* obs_out, float* out5,
-                          float* scaled_actions, int actions_raw, int do_rewards, hipStream_t s, int storage_f16 = 0,
-                          int tape_horizon = 0, const GateArgs* gate = nullptr, const AccArgs* acc = nullptr,
-                          const ShieldArgs* shield = nullptr) {
-    return rollout_fused(h, pick_variant(h, n_env), n_env, obs_in, actions, ref_idx, path_id, obs_out, out5, scaled_actions,
-                         actions_raw, do_rewards, s, storage_f16, tape_horizon, gate, acc, shield);
 }
 
 // blocks of a gated rollout over n_env envs, or 0 when they cannot all be resident at once next to a producer: a gated
@@ -667,9 +680,9 @@ static int gated_blocks(eb_handle h, int32_t n_env, int* variant_out = nullptr) 
     // the tile shape the per-step kernel would take for this batch, or the next larger one whose grid fits (a forced shape stays)
     const int first = pick_variant(h, n_env);
     for (int variant = first; variant >= 0; --variant) {
-        const int ept = std::max(1, std::min(64, eb::fused_tile_records(variant) / h->cfg.n_veh));
+        const int ept = envs_per_tile(h, variant);
         const int grid = (n_env + ept - 1) / ept;
-        const size_t dyn = stage_paths_in_lds(h, grid) ? (size_t)(h->red_total + 4) * 12 : 0;   // as rollout_fused will launch it
+        const size_t dyn = stage_paths_in_lds(h, grid) ? (size_t)(h->red_total + 4) * 12 : 0;   // as rollout will launch it
         const int per_cu = eb::tape_blocks_per_cu(h->cfg.task, variant, h->cfg.n_veh, 0, dyn);
         if (grid <= per_cu * h->n_cu / 2) {
             if (variant_out) *variant_out = variant;
@@ -689,7 +702,9 @@ int eb_compute_next_obses(eb_handle h, int32_t n_env, const float* obs, const fl
     if (obs == obs_out) return fail(EB_EINVAL, "eb_compute_next_obses: in-place update is not supported");
     if (n_env == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
-    return rollout_common(h, n_env, obs, actions, ref_idx, path_id, obs_out, nullptr, nullptr, 0, 0, pick(h, stream));
+    RolloutLaunch r{obs, obs_out, actions, ref_idx, path_id};
+    r.actions_raw = 0; r.do_rewards = 0;
+    return rollout(h, n_env, r, (hipStream_t)stream);
 }
 
 int eb_rollout_step(eb_handle h, int32_t n_env, const float* obs_in, const float* actions, const int32_t* ref_idx,
@@ -701,8 +716,9 @@ int eb_rollout_step(eb_handle h, int32_t n_env, const float* obs_in, const float
     if (obs_in == obs_out) return fail(EB_EINVAL, "eb_rollout_step: in-place update is not supported");
     if (n_env == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
-    return rollout_common(h, n_env, obs_in, actions, ref_idx, path_id, obs_out, out5, scaled_actions, 1, 1,
-                          pick(h, stream));
+    RolloutLaunch r{obs_in, obs_out, actions, ref_idx, path_id, out5};
+    r.scaled_actions = scaled_actions;
+    return rollout(h, n_env, r, (hipStream_t)stream);
 }
 
 int eb_episode_acc_bytes(eb_handle h, int32_t n_env, int32_t horizon, int64_t* bytes) {
@@ -724,8 +740,9 @@ int eb_rollout_step_acc(eb_handle h, int32_t n_env, const float* obs_in, const f
     if (obs_in == obs_out) return fail(EB_EINVAL, "eb_rollout_step_acc: in-place update is not supported");
     EB_HIP(hipSetDevice(h->cfg.device));
     const AccArgs a{acc, step, horizon, prev_out5};
-    return rollout_common(h, n_env, obs_in, actions, ref_idx, path_id, obs_out, out5, scaled_actions, 1, 1, pick(h, stream), 0, 0,
-                          nullptr, &a);
+    RolloutLaunch r{obs_in, obs_out, actions, ref_idx, path_id, out5};
+    r.scaled_actions = scaled_actions; r.acc = &a;
+    return rollout(h, n_env, r, (hipStream_t)stream);
 }
 
 int eb_episode_acc_finish(eb_handle h, int32_t n_env, int32_t horizon, const void* acc, float* out8, void* stream) {
@@ -743,7 +760,7 @@ int eb_episode_acc_finish(eb_handle h, int32_t n_env, int32_t horizon, const voi
         }
     void* ws = const_cast<void*>(acc);
     EB_HIP(eb::launch_acc_fold((int)grid, n_env, horizon, acc_records(ws, 0, grid), acc_finals(ws, horizon, grid), out8,
-                               pick(h, stream)));
+                               (hipStream_t)stream));
     return EB_OK;
 }
 
@@ -756,8 +773,9 @@ static int rollout_tape_stepwise(eb_handle h, int32_t n_env, int32_t horizon, co
     for (int t = 0; t < horizon; ++t) {
         float* dst = ((horizon - 1 - t) % 2 == 0) ? obs_out : obs_work;
         const AccArgs a{acc, t, horizon, t > 0 ? out5_steps + (size_t)(t - 1) * 5 * n_env : nullptr};
-        int rc = rollout_common(h, n_env, cur, action_tape + (size_t)t * n_env * 2, ref_idx, path_id, dst,
-                                out5_steps + (size_t)t * 5 * n_env, nullptr, 1, 1, s, storage_f16, 0, nullptr, acc ? &a : nullptr);
+        RolloutLaunch r{cur, dst, action_tape + (size_t)t * n_env * 2, ref_idx, path_id, out5_steps + (size_t)t * 5 * n_env};
+        r.storage_f16 = storage_f16; r.acc = acc ? &a : nullptr;
+        int rc = rollout(h, n_env, r, s);
         if (rc) return rc;
         cur = dst;
     }
@@ -772,8 +790,9 @@ static int rollout_tape_any(eb_handle h, int32_t n_env, int32_t horizon, const f
     if (h->tape_stepwise)
         return rollout_tape_stepwise(h, n_env, horizon, obs_in, action_tape, ref_idx, path_id, obs_work, obs_out, out5_steps, s,
                                      storage_f16);
-    return rollout_common(h, n_env, obs_in, action_tape, ref_idx, path_id, obs_out, out5_steps, nullptr, 1, 1, s, storage_f16,
-                          horizon);
+    RolloutLaunch r{obs_in, obs_out, action_tape, ref_idx, path_id, out5_steps};
+    r.storage_f16 = storage_f16; r.tape_horizon = horizon;
+    return rollout(h, n_env, r, s);
 }
 
 int eb_rollout_tape(eb_handle h, int32_t n_env, int32_t horizon, const float* obs_in, const float* action_tape,
@@ -789,7 +808,7 @@ int eb_rollout_tape(eb_handle h, int32_t n_env, int32_t horizon, const float* ob
     if (n_env == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
     return rollout_tape_any(h, n_env, horizon, obs_in, action_tape, ref_idx, path_id, obs_work, obs_out, out5_steps,
-                            pick(h, stream), 0);
+                            (hipStream_t)stream, 0);
 }
 
 int eb_rollout_gated_blocks(eb_handle h, int32_t n_env, int32_t* n_blocks) {
@@ -826,8 +845,9 @@ int eb_rollout_gated(eb_handle h, int32_t n_env, int32_t horizon, const float* o
     if (n_blocks != grid)
         return fail(EB_EINVAL, "eb_rollout_gated: n_blocks does not match the grid this handle launches now (call eb_rollout_gated_blocks again)");
     const GateArgs g{step_ready, step_done, obs_steps, status, spin_limit};
-    return rollout_fused(h, variant, n_env, obs_in, action_tape, ref_idx, path_id, obs_out, out5_steps, nullptr, 1, 1, pick(h, stream), 0,
-                         horizon, &g);
+    RolloutLaunch r{obs_in, obs_out, action_tape, ref_idx, path_id, out5_steps};
+    r.tape_horizon = horizon; r.gate = &g; r.variant = variant;
+    return rollout(h, n_env, r, (hipStream_t)stream);
 }
 
 int eb_gate_feed(eb_handle h, int32_t n_env, int32_t horizon, int32_t n_blocks, const float* staged_tape,
@@ -869,8 +889,9 @@ int eb_rollout_step_f16(eb_handle h, int32_t n_env, const uint16_t* obs_in, cons
     if (n_env < 0 || !obs_in || !actions || !obs_out || !out5) return fail(EB_EINVAL, "eb_rollout_step_f16: bad argument");
     if (obs_in == obs_out) return fail(EB_EINVAL, "eb_rollout_step_f16: in-place update is not supported");
     EB_HIP(hipSetDevice(h->cfg.device));
-    return rollout_common(h, n_env, reinterpret_cast<const float*>(obs_in), actions, ref_idx, path_id,
-                          reinterpret_cast<float*>(obs_out), out5, scaled_actions, 1, 1, pick(h, stream), 1);
+    RolloutLaunch r{reinterpret_cast<const float*>(obs_in), reinterpret_cast<float*>(obs_out), actions, ref_idx, path_id, out5};
+    r.scaled_actions = scaled_actions; r.storage_f16 = 1;
+    return rollout(h, n_env, r, (hipStream_t)stream);
 }
 
 int eb_rollout_tape_f16(eb_handle h, int32_t n_env, int32_t horizon, const uint16_t* obs_in, const float* action_tape,
@@ -886,7 +907,7 @@ int eb_rollout_tape_f16(eb_handle h, int32_t n_env, int32_t horizon, const uint1
     EB_HIP(hipSetDevice(h->cfg.device));
     return rollout_tape_any(h, n_env, horizon, reinterpret_cast<const float*>(obs_in), action_tape, ref_idx, path_id,
                             reinterpret_cast<float*>(obs_work), reinterpret_cast<float*>(obs_out), out5_steps,
-                            pick(h, stream), 1);
+                            (hipStream_t)stream, 1);
 }
 
 int eb_find_closest_point(eb_handle h, int32_t n, const float* xs, const float* ys, const int32_t* ref_idx,
@@ -898,7 +919,7 @@ int eb_find_closest_point(eb_handle h, int32_t n, const float* xs, const float* 
     if (n == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
     EB_HIP(eb::launch_tracking(h->cfg.task, n, h->pt, xs, ys, nullptr, nullptr, ref_idx, path_id, 0, ratio, nullptr,
-                               out_index, out_points, pick(h, stream)));
+                               out_index, out_points, (hipStream_t)stream));
     return EB_OK;
 }
 
@@ -910,7 +931,7 @@ int eb_path_points(eb_handle h, int32_t n, const int32_t* index, const int32_t* 
     if (!ref_idx && (path_id < 0 || path_id >= h->pt.n_paths)) return fail(EB_EINVAL, "eb_path_points: bad path_id");
     if (n == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
-    EB_HIP(eb::launch_path_points(n, h->pt, index, ref_idx, path_id, n_future, out_points, pick(h, stream)));
+    EB_HIP(eb::launch_path_points(n, h->pt, index, ref_idx, path_id, n_future, out_points, (hipStream_t)stream));
     return EB_OK;
 }
 
@@ -918,7 +939,7 @@ int eb_phi_diff(eb_handle h, int32_t n, const float* phi_diff, float* out, void*
     if (!h || n < 0 || (n > 0 && (!phi_diff || !out))) return fail(EB_EINVAL, "eb_phi_diff: bad argument");
     if (n == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
-    EB_HIP(eb::launch_phi_diff(n, phi_diff, out, pick(h, stream)));
+    EB_HIP(eb::launch_phi_diff(n, phi_diff, out, (hipStream_t)stream));
     return EB_OK;
 }
 
@@ -926,7 +947,7 @@ int eb_ego_predict(eb_handle h, int32_t n, const float* ego, const float* action
     if (!h || n < 0 || (n > 0 && (!ego || !actions || !next_ego))) return fail(EB_EINVAL, "eb_ego_predict: bad argument");
     if (n == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
-    EB_HIP(eb::launch_ego_predict(n, ego, actions, next_ego, pick(h, stream)));
+    EB_HIP(eb::launch_ego_predict(n, ego, actions, next_ego, (hipStream_t)stream));
     return EB_OK;
 }
 
@@ -939,7 +960,7 @@ int eb_tracking_error(eb_handle h, int32_t n, const float* xs, const float* ys, 
     if (n == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
     EB_HIP(eb::launch_tracking(h->cfg.task, n, h->pt, xs, ys, phis, vs, ref_idx, path_id, n_future, 10, out, nullptr,
-                               nullptr, pick(h, stream)));
+                               nullptr, (hipStream_t)stream));
     return EB_OK;
 }
 
@@ -949,7 +970,7 @@ int eb_veh_predict(eb_handle h, int32_t n_env, const float* veh, float* veh_out,
     if (rc) return rc;
     if (n_env == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
-    EB_HIP(eb::launch_veh_predict(n_env, h->cfg.n_veh, h->modes, veh, veh_out, pick(h, stream)));
+    EB_HIP(eb::launch_veh_predict(n_env, h->cfg.n_veh, h->modes, veh, veh_out, (hipStream_t)stream));
     return EB_OK;
 }
 
@@ -963,7 +984,7 @@ int eb_ss(eb_handle h, int32_t n_env, const float* obs, const float* actions, co
     EB_HIP(hipSetDevice(h->cfg.device));
     EB_HIP(eb::launch_ss(h->cfg.task, n_env, obs_dim(h->cfg), h->cfg.n_future, h->cfg.n_veh, h->pt, h->modes, obs,
                          actions, ref_idx, path_id, h->cfg.mode == EB_MODE_TRAINING, (float)(1.0 - lam), out,
-                         pick(h, stream)));
+                         (hipStream_t)stream));
     return EB_OK;
 }
 
@@ -972,12 +993,53 @@ int eb_env_ego_step(eb_handle h, int32_t n, const float* ego, const float* actio
     if (!h || n < 0 || !ego || !actions || !next_ego || !params) return fail(EB_EINVAL, "eb_env_ego_step: bad argument");
     if (n == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
-    EB_HIP(eb::launch_env_ego_step(n, ego, actions, next_ego, params, pick(h, stream)));
+    EB_HIP(eb::launch_env_ego_step(n, ego, actions, next_ego, params, (hipStream_t)stream));
     return EB_OK;
 }
 
 // eb_debug_set_tile on the env-side kernels: 0 / 1 / 2 = 64- / 32- / 16-env tiles (every shape computes the same bits), else by batch size
 static int forced_env_tile(const eb_handle_s* h) { return h->tile_variant == 0 ? 64 : h->tile_variant == 1 ? 32 : h->tile_variant == 2 ? 16 : 0; }
+
+// What every one-launch env kernel (csrc/eb_env_step.hip) is given: the shape, the divisor magics, the tables, the slot plan and the
+// handle's debug settings.  Each caller adds its own part: the step, the observation alone, or the masked reset.
+static eb::EnvStepArgs env_step_base(eb_handle h, int32_t n_env, int32_t m_cand, int32_t path_id) {
+    eb::EnvStepArgs A;
+    std::memset(&A, 0, sizeof A);
+    const int D = obs_dim(h->cfg), NV = h->cfg.n_veh;
+    A.n_env = n_env; A.D = D; A.n_future = h->cfg.n_future; A.NV = NV; A.m_cand = m_cand; A.path_id = path_id;
+    A.d_magic = eb::div_magic(D); A.m_magic = eb::div_magic(m_cand); A.nv_magic = eb::div_magic(NV);
+    A.pt = h->pt; A.modes = h->modes;
+    eb::env_step_slot_plan(h->modes, NV, A);
+    A.trace = h->trace; A.trace_words = h->trace_words;
+    A.tile_envs = forced_env_tile(h); A.waves = h->env_waves; A.scan_one_trip = h->scan_one_trip;
+    return A;
+}
+
+// The observation of the rows of row_mask (every row when NULL) from the state as it stands: through the one-launch machinery
+// (pair-parallel staging, the bit-set slot selection) when the shape allows it, else the per-thread / staged kernel.
+// forced: the handle's debug settings reach the one-launch form (eb_get_obs); the separate-launch paths run it by batch size
+static hipError_t get_obs(eb_handle h, int32_t n_env, const float* ego, const int32_t* ref_idx, int32_t path_id, int32_t m_cand,
+                          const float* cand, const uint8_t* cand_mode, const uint8_t* v_light, const uint8_t* virtual_flag,
+                          const uint8_t* row_mask, float* obs_out, hipStream_t s, bool forced) {
+    if (!eb::env_step_is_fused(obs_dim(h->cfg), h->cfg.n_veh, m_cand, cand, ego))
+        return eb::launch_get_obs(h->cfg.task, n_env, obs_dim(h->cfg), h->cfg.n_future, h->cfg.n_veh, h->pt, h->modes, ego, ref_idx,
+                                  path_id, m_cand, cand, cand_mode, v_light, virtual_flag, row_mask, obs_out, s);
+    eb::EnvStepArgs A = env_step_base(h, n_env, m_cand, path_id);
+    if (!forced) { A.trace = nullptr; A.trace_words = 0; A.tile_envs = 0; A.waves = 0; A.scan_one_trip = 0; }
+    A.by_progress = 0;   // (not the handle's rollout schedule)
+    A.tturn = {};        // (no traffic handle: nothing moves)
+    A.obs_only = 1; A.row_mask = row_mask;
+    A.ref_idx = ref_idx; A.ego = const_cast<float*>(ego); A.cand = const_cast<float*>(cand); A.cand_mode = cand_mode;
+    A.v_light = v_light; A.virtual_flag = virtual_flag; A.obs_out = obs_out;
+    return eb::launch_env_step(h->cfg.task, A, s);
+}
+
+// eb_traffic_flow_step's launch for the flow rule of an eb_env_step call
+static hipError_t flow_step(const eb_flow_rule* f, int32_t n_env, float* cand, hipStream_t s) {
+    return eb::launch_traffic_flow_step(n_env, f->per_route, cand, f->active, f->timer, f->emitted, f->sim_step, f->lane, f->period, f->v_max,
+                                        f->dt, f->exit_range, f->accel, f->lane_len, f->light_cycle, f->seed, f->counter, f->cand_mode,
+                                        f->v_light, s);
+}
 
 int eb_get_obs(eb_handle h, int32_t n_env, const float* ego, const int32_t* ref_idx, int32_t path_id,
                int32_t m_cand, const float* cand, const uint8_t* cand_mode, const uint8_t* v_light,
@@ -992,10 +1054,13 @@ int eb_get_obs(eb_handle h, int32_t n_env, const float* ego, const int32_t* ref_
     if (n_env == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
     // (exit ids live in device memory: the kernel masks them to 0..3 instead of a host-side range check)
-    EB_HIP(eb::launch_get_obs(h->cfg.task, n_env, obs_dim(h->cfg), h->cfg.n_future, h->cfg.n_veh, h->pt, h->modes, ego,
-                              ref_idx, path_id, m_cand, cand, cand_mode, v_light, virtual_flag, obs_out, pick(h, stream),
-                              nullptr, nullptr, nullptr, exit_id, &h->xc, row_mask, nullptr, forced_env_tile(h), h->env_waves, h->trace,
-                              h->trace_words, h->scan_one_trip));
+    if (exit_id)
+        EB_HIP(eb::launch_get_obs_exit(h->cfg.task, n_env, obs_dim(h->cfg), h->cfg.n_future, h->cfg.n_veh, h->pt, h->modes, ego, ref_idx,
+                                       path_id, m_cand, cand, cand_mode, v_light, virtual_flag, exit_id, h->xc, row_mask, obs_out,
+                                       (hipStream_t)stream));
+    else
+        EB_HIP(get_obs(h, n_env, ego, ref_idx, path_id, m_cand, cand, cand_mode, v_light, virtual_flag, row_mask, obs_out,
+                       (hipStream_t)stream, true));
     return EB_OK;
 }
 
@@ -1004,7 +1069,7 @@ int eb_exit_frame(eb_handle h, int32_t n, const uint8_t* exit_id, int32_t invers
     if (!h || n < 0 || (n > 0 && (!exit_id || !ego || !ego_out))) return fail(EB_EINVAL, "eb_exit_frame: bad argument");
     if (n == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
-    EB_HIP(eb::launch_exit_frame(n, exit_id, inverse ? 1 : 0, h->xc, ego, ego_out, pick(h, stream)));
+    EB_HIP(eb::launch_exit_frame(n, exit_id, inverse ? 1 : 0, h->xc, ego, ego_out, (hipStream_t)stream));
     return EB_OK;
 }
 
@@ -1016,7 +1081,7 @@ int eb_judge_done(eb_handle h, int32_t n_env, const float* ego, const float* par
     if (n_env == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
     EB_HIP(eb::launch_judge_done(h->cfg.task, n_env, obs_dim(h->cfg), ego, params, obs, m_cand, cand, cand_mode,
-                                 cand_lw, v_light, done_code, pick(h, stream)));
+                                 cand_lw, v_light, done_code, (hipStream_t)stream));
     return EB_OK;
 }
 
@@ -1060,25 +1125,17 @@ int eb_env_step(eb_handle h, eb_handle traffic, int32_t n_env, const float* obs,
     if (time_limit && (!time_limit->episode_step || time_limit->max_episode_steps < 1))
         return fail(EB_EINVAL, "eb_env_step: bad time limit (episode_step given, max_episode_steps >= 1)");
     if (n_env == 0) return EB_OK;
-    hipStream_t s = pick(h, stream);
+    hipStream_t s = (hipStream_t)stream;
     EB_HIP(hipSetDevice(h->cfg.device));
     const int D = obs_dim(h->cfg);
     if (eb::env_step_is_fused(D, h->cfg.n_veh, m_cand, cand, ego, actions, scaled_actions, params, flow != nullptr)) {
         // the whole step — the six calls and the pool's re-entry — as ONE launch (csrc/eb_env_step.hip)
-        eb::EnvStepArgs A;
-        std::memset(&A, 0, sizeof A);
-        auto magic = [](int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); };
-        A.n_env = n_env; A.D = D; A.n_future = h->cfg.n_future; A.NV = h->cfg.n_veh; A.m_cand = m_cand; A.path_id = path_id;
-        A.d_magic = magic(D); A.m_magic = magic(m_cand); A.nv_magic = magic(h->cfg.n_veh);
-        A.pt = h->pt; A.modes = h->modes;
+        eb::EnvStepArgs A = env_step_base(h, n_env, m_cand, path_id);
         std::memcpy(A.tturn.t, traffic->modes.turn, sizeof A.tturn.t);
-        eb::env_step_slot_plan(h->modes, h->cfg.n_veh, A);
+        A.by_progress = h->sched_progress;   // (-1: launch_env_step decides by the grid)
         A.obs = obs; A.raw = actions; A.ref_idx = ref_idx; A.ego = ego; A.params = params; A.cand = cand; A.cand_mode = cand_mode;
         A.cand_lw = cand_lw; A.v_light = v_light; A.virtual_flag = virtual_flag; A.scaled = scaled_actions; A.out5 = out5;
         A.d16 = out_dict16; A.obs_out = obs_out; A.done_code = done_code;
-        A.trace = h->trace; A.trace_words = h->trace_words;
-        A.tile_envs = forced_env_tile(h); A.waves = h->env_waves; A.scan_one_trip = h->scan_one_trip;
-        A.by_progress = h->sched_progress;   // (-1: launch_env_step decides by the grid)
         if (respawn) {
             A.respawn_entry = respawn->entry; A.limit = respawn->limit; A.span = respawn->span; A.v_max = respawn->v_max;
             A.seed = respawn->seed; A.counter = respawn->counter;
@@ -1097,24 +1154,19 @@ int eb_env_step(eb_handle h, eb_handle traffic, int32_t n_env, const float* obs,
             A.flow_dt = flow->dt; A.flow_exit_range = flow->exit_range; A.flow_accel = flow->accel; A.flow_lane_len = flow->lane_len;
             A.flow_light_cycle = flow->light_cycle; A.seed = flow->seed; A.counter = flow->counter;
             A.flow_mode_out = flow->cand_mode; A.v_light_out = flow->v_light;
-            A.k_magic = magic(flow->per_route);
+            A.k_magic = eb::div_magic(flow->per_route);
         }
         if (time_limit) { A.episode_step = time_limit->episode_step; A.max_episode_steps = time_limit->max_episode_steps; }
         EB_HIP(eb::launch_env_step(h->cfg.task, A, s));
         return EB_OK;
     }
     // separate launches (no candidates, a tile that does not fit the LDS, an unaligned candidate buffer)
-    // (scratch per call, allocated and released in stream order: two streams may drive one handle through this path)
     float* scaled = scaled_actions;
-    float* own_scaled = nullptr;
+    StreamScratch own_scaled{nullptr, s};
     if (!scaled) {
-        EB_HIP(hipMallocAsync(reinterpret_cast<void**>(&own_scaled), (size_t)n_env * 2 * sizeof(float), s));
-        scaled = own_scaled;
+        EB_HIP(hipMallocAsync(&own_scaled.p, (size_t)n_env * 2 * sizeof(float), s));
+        scaled = static_cast<float*>(own_scaled.p);
     }
-    struct Release {   // on every return path below, after the launches that read it
-        float* p; hipStream_t s;
-        ~Release() { if (p) (void)hipFreeAsync(p, s); }
-    } release{own_scaled, s};
     // E2E:133-135 in one launch: action scaling, reward on the current obs, ego step in place (the same device
     // functions eb_action_transform / eb_compute_rewards / eb_env_ego_step run)
     EB_HIP(eb::launch_env_pre(h->cfg.task, n_env, D, h->cfg.n_future, h->cfg.n_veh, obs, actions,
@@ -1123,50 +1175,39 @@ int eb_env_step(eb_handle h, eb_handle traffic, int32_t n_env, const float* obs,
     if (m_cand > 0 && eb::get_obs_is_staged(D, m_cand, cand)) {
         // E2E:140-141 in one launch: the observation kernel keeps the tile's candidates and the new delta_y in LDS and
         // appends _judge_done (the same device functions eb_judge_done runs)
-        EB_HIP(eb::launch_get_obs(h->cfg.task, n_env, D, h->cfg.n_future, h->cfg.n_veh, h->pt, h->modes, ego,
-                                  ref_idx, path_id, m_cand, cand, cand_mode, v_light, virtual_flag, obs_out, s, params,
-                                  cand_lw, done_code));
+        const eb::JudgeArgs judge{params, cand_lw, done_code};
+        EB_HIP(eb::launch_get_obs(h->cfg.task, n_env, D, h->cfg.n_future, h->cfg.n_veh, h->pt, h->modes, ego, ref_idx, path_id, m_cand, cand,
+                                  cand_mode, v_light, virtual_flag, nullptr, obs_out, s, &judge));
     } else {
-        EB_HIP(eb::launch_get_obs(h->cfg.task, n_env, D, h->cfg.n_future, h->cfg.n_veh, h->pt, h->modes, ego,
-                                  ref_idx, path_id, m_cand, cand, cand_mode, v_light, virtual_flag, obs_out, s));   /* E2E:140 */
+        EB_HIP(get_obs(h, n_env, ego, ref_idx, path_id, m_cand, cand, cand_mode, v_light, virtual_flag, nullptr, obs_out, s, false));   /* E2E:140 */
         EB_HIP(eb::launch_judge_done(h->cfg.task, n_env, D, ego, params, obs_out, m_cand, cand, cand_mode,
-                                     cand_lw, v_light, done_code, s));                                          /* E2E:141 */
+                                     cand_lw, v_light, done_code, s));                                                           /* E2E:141 */
     }
     if (time_limit) EB_HIP(eb::launch_time_limit(n_env, time_limit->episode_step, time_limit->max_episode_steps, done_code, s));
     if (respawn)
         EB_HIP(eb::launch_traffic_respawn(n_env, m_cand, cand, respawn->entry, respawn->limit, respawn->span, respawn->v_max,
                                           respawn->seed, respawn->counter, nullptr, nullptr, s));
-    if (flow && auto_reset) {   // the flow source: its step first, then the masked reset's launches (eb_env_reset, the source's own reset, obs, flags)
-        const eb_auto_reset* ar = auto_reset;
-        EB_HIP(eb::launch_traffic_flow_step(n_env, flow->per_route, cand, flow->active, flow->timer, flow->emitted, flow->sim_step, flow->lane,
-                                            flow->period, flow->v_max, flow->dt, flow->exit_range, flow->accel, flow->lane_len,
-                                            flow->light_cycle, flow->seed, flow->counter, flow->cand_mode, flow->v_light, s));
-        if (ar->final_obs) EB_HIP(eb::launch_copy_rows_masked(n_env, D, done_code, obs_out, ar->final_obs, s));
-        uint8_t* d_vnext = nullptr;
-        EB_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_vnext), (size_t)n_env, s));
-        struct ReleaseV { uint8_t* p; hipStream_t s; ~ReleaseV() { (void)hipFreeAsync(p, s); } } release_v{d_vnext, s};
-        EB_HIP(eb::launch_env_reset(h->cfg.task, n_env, h->pt, done_code, ar->seed, ar->counter, ar->training ? 1 : 0, ego, params, ar->ref_idx,
-                                    d_vnext, nullptr, s));
-        EB_HIP(eb::launch_traffic_flow_reset(n_env, flow->per_route, done_code, ego, cand, flow->active, flow->timer, flow->emitted, flow->sim_step,
-                                             ar->flow_phase0, flow->lane, flow->period, flow->v_max, ar->flow_cand_len, flow->lane_len,
-                                             ar->flow_random_phase ? 1 : 0, ar->training ? 1 : 0, ar->flow_seed, ar->flow_counter,
-                                             flow->cand_mode, flow->v_light, s));
-        EB_HIP(eb::launch_get_obs(h->cfg.task, n_env, D, h->cfg.n_future, h->cfg.n_veh, h->pt, h->modes, ego, ar->ref_idx, 0, m_cand, cand,
-                                  flow->cand_mode, flow->v_light, ar->virtual_flag, obs_out, s, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                  done_code));
-        EB_HIP(eb::launch_flag_swap(n_env, done_code, d_vnext, ar->virtual_flag, s));
-        return EB_OK;
-    }
-    if (const eb_auto_reset* ar = auto_reset) {   // the same composition the header spells out, as launches of their own
-        if (ar->final_obs) EB_HIP(eb::launch_copy_rows_masked(n_env, D, done_code, obs_out, ar->final_obs, s));
+    if (flow) EB_HIP(flow_step(flow, n_env, cand, s));
+    const eb_auto_reset* ar = auto_reset;
+    if (!ar) return EB_OK;
+    if (ar->final_obs) EB_HIP(eb::launch_copy_rows_masked(n_env, D, done_code, obs_out, ar->final_obs, s));
+    if (!flow)   // the same composition the header spells out, as launches of their own
         return eb_env_reset_pool(h, traffic, n_env, done_code, ar->seed, ar->counter, ar->training, ego, params, ar->ref_idx,
                                  ar->virtual_flag, ar->v_light, nullptr, nullptr, m_cand, cand, cand_mode, &ar->pool, obs_out, nullptr,
                                  nullptr, stream);   // (the time limit above has restarted the finished envs' counts)
-    }
-    if (flow)
-        EB_HIP(eb::launch_traffic_flow_step(n_env, flow->per_route, cand, flow->active, flow->timer, flow->emitted, flow->sim_step, flow->lane,
-                                            flow->period, flow->v_max, flow->dt, flow->exit_range, flow->accel, flow->lane_len,
-                                            flow->light_cycle, flow->seed, flow->counter, flow->cand_mode, flow->v_light, s));
+    // the flow source: after its step, the masked reset's launches (eb_env_reset, the source's own reset, obs, flags)
+    StreamScratch vnext{nullptr, s};
+    EB_HIP(hipMallocAsync(&vnext.p, (size_t)n_env, s));
+    uint8_t* d_vnext = static_cast<uint8_t*>(vnext.p);
+    EB_HIP(eb::launch_env_reset(h->cfg.task, n_env, h->pt, done_code, ar->seed, ar->counter, ar->training ? 1 : 0, ego, params, ar->ref_idx,
+                                d_vnext, nullptr, s));
+    EB_HIP(eb::launch_traffic_flow_reset(n_env, flow->per_route, done_code, ego, cand, flow->active, flow->timer, flow->emitted, flow->sim_step,
+                                         ar->flow_phase0, flow->lane, flow->period, flow->v_max, ar->flow_cand_len, flow->lane_len,
+                                         ar->flow_random_phase ? 1 : 0, ar->training ? 1 : 0, ar->flow_seed, ar->flow_counter,
+                                         flow->cand_mode, flow->v_light, s));
+    EB_HIP(get_obs(h, n_env, ego, ar->ref_idx, 0, m_cand, cand, flow->cand_mode, flow->v_light, ar->virtual_flag, done_code, obs_out, s,
+                   false));
+    EB_HIP(eb::launch_flag_swap(n_env, done_code, d_vnext, ar->virtual_flag, s));
     return EB_OK;
 }
 
@@ -1179,7 +1220,7 @@ int eb_env_reset(eb_handle h, int32_t n_env, const uint8_t* mask, uint64_t seed,
     if (n_env == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
     EB_HIP(eb::launch_env_reset(h->cfg.task, n_env, h->pt, mask, seed, counter, training ? 1 : 0, ego, params, ref_idx,
-                                virtual_next, done_code, pick(h, stream), nullptr, episode_step));
+                                virtual_next, done_code, (hipStream_t)stream, nullptr, episode_step));
     return EB_OK;
 }
 
@@ -1187,7 +1228,7 @@ int eb_ego_dynamics(eb_handle h, int32_t n, const float* ego, const float* param
     if (!h || n < 0 || (n > 0 && (!ego || !params || !out))) return fail(EB_EINVAL, "eb_ego_dynamics: bad argument");
     if (n == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
-    EB_HIP(eb::launch_ego_dynamics(n, ego, params, out, pick(h, stream)));
+    EB_HIP(eb::launch_ego_dynamics(n, ego, params, out, (hipStream_t)stream));
     return EB_OK;
 }
 
@@ -1207,26 +1248,29 @@ int eb_env_reset_pool(eb_handle h, eb_handle traffic, int32_t n_env, const uint8
     if (rc) return rc;
     if (n_env == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
     if (eb::env_step_is_fused(obs_dim(h->cfg), h->cfg.n_veh, m_cand, cand, ego, nullptr, nullptr, params)) {
         // ONE launch (csrc/eb_env_step.hip, env_reset_pool_kernel): a tile's masked rows are drawn, their pool re-entered clear of
         // the new ego, their observation built from the state still in LDS, their flag swapped — the same arithmetic, in the
         // same order per row, as the four launches below
-        const eb::EnvResetArgs R{seed, counter, training ? 1 : 0, params, ref_idx, virtual_flag, v_light, done_code, pool->entry,
-                                 pool->span, pool->v_max, pool->edge_span, pool->seed, pool->counter,
-                                 mask && obs_src != obs ? obs_src : nullptr, mask && done_code && done_src != done_code ? done_src : nullptr,
-                                 episode_step};
-        EB_HIP(eb::launch_get_obs(h->cfg.task, n_env, obs_dim(h->cfg), h->cfg.n_future, h->cfg.n_veh, h->pt, h->modes, ego, ref_idx, 0,
-                                  m_cand, cand, cand_mode, nullptr, virtual_flag, obs, pick(h, stream), nullptr, nullptr, nullptr, nullptr,
-                                  nullptr, mask, &R, forced_env_tile(h), h->env_waves, h->trace, h->trace_words, h->scan_one_trip));
+        eb::EnvStepArgs A = env_step_base(h, n_env, m_cand, 0);
+        A.by_progress = 0;   // (not the handle's rollout schedule)
+        A.tturn = {};        // (no traffic handle: nothing moves)
+        A.obs_only = 1; A.reset = 1; A.row_mask = mask;
+        A.ref_idx = ref_idx; A.ego = ego; A.cand = cand; A.cand_mode = cand_mode; A.virtual_flag = virtual_flag; A.obs_out = obs;
+        A.v_light = nullptr;   // (the reset clears the light of its rows: v_light_out)
+        A.training = training ? 1 : 0; A.reset_seed = seed; A.reset_counter = counter; A.params = params; A.episode_step = episode_step;
+        A.ref_idx_out = ref_idx; A.virtual_out = virtual_flag; A.v_light_out = v_light; A.done_code = done_code;
+        A.pool_entry = pool->entry; A.pool_span = pool->span; A.pool_v_max = pool->v_max; A.edge_span = pool->edge_span;
+        A.pool_seed = pool->seed; A.pool_counter = pool->counter;
+        A.obs = mask && obs_src != obs ? obs_src : nullptr;   // the rows outside the mask: carried over from the caller's previous arrays
+        A.done_src = mask && done_code && done_src != done_code ? done_src : nullptr;
+        EB_HIP(eb::launch_env_step(h->cfg.task, A, s));
         return EB_OK;
     }
-    hipStream_t s = pick(h, stream);
-    uint8_t* d_vnext = nullptr;   // the flags eb_env_reset draws, until they are swapped in: per call, in stream order
-    EB_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_vnext), (size_t)n_env, s));
-    struct Release {
-        uint8_t* p; hipStream_t s;
-        ~Release() { (void)hipFreeAsync(p, s); }
-    } release{d_vnext, s};
+    StreamScratch vnext{nullptr, s};   // the flags eb_env_reset draws, until they are swapped in
+    EB_HIP(hipMallocAsync(&vnext.p, (size_t)n_env, s));
+    uint8_t* d_vnext = static_cast<uint8_t*>(vnext.p);
     if (mask && obs_src && obs_src != obs)       // the rows outside the mask: carried over from the caller's previous arrays
         EB_HIP(hipMemcpyAsync(obs, obs_src, (size_t)n_env * obs_dim(h->cfg) * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (mask && done_src && done_code && done_src != done_code)
@@ -1237,8 +1281,7 @@ int eb_env_reset_pool(eb_handle h, eb_handle traffic, int32_t n_env, const uint8
                                 done_code, s, v_light, episode_step));
     EB_HIP(eb::launch_traffic_respawn(n_env, m_cand, cand, pool->entry, -1.0f, pool->span, pool->v_max, pool->seed, pool->counter, mask,
                                       nullptr, s, ego, pool->edge_span));
-    EB_HIP(eb::launch_get_obs(h->cfg.task, n_env, obs_dim(h->cfg), h->cfg.n_future, h->cfg.n_veh, h->pt, h->modes, ego, ref_idx, 0,
-                              m_cand, cand, cand_mode, v_light, virtual_flag, obs, s, nullptr, nullptr, nullptr, nullptr, nullptr, mask));
+    EB_HIP(get_obs(h, n_env, ego, ref_idx, 0, m_cand, cand, cand_mode, v_light, virtual_flag, mask, obs, s, false));
     EB_HIP(eb::launch_flag_swap(n_env, mask, d_vnext, virtual_flag, s));
     return EB_OK;
 }
@@ -1364,7 +1407,7 @@ int eb_episode_summary(eb_handle h, int32_t n_env, int32_t horizon, const float*
         return fail(EB_EINVAL, "eb_episode_summary: bad argument");
     EB_HIP(hipSetDevice(h->cfg.device));
     EB_HIP(eb::launch_summary(n_env, horizon, obs_dim(h->cfg), out5_steps, obs_final, h->d_partials,
-                              eb::SUMMARY_MAX_PARTS, out8, pick(h, stream)));
+                              eb::SUMMARY_MAX_PARTS, out8, (hipStream_t)stream));
     return EB_OK;
 }
 
@@ -1532,7 +1575,7 @@ int eb_traffic_respawn(eb_handle h, int32_t n_env, int32_t m_cand, float* cand, 
     if (n_env == 0) return EB_OK;
     EB_HIP(hipSetDevice(h->cfg.device));
     EB_HIP(eb::launch_traffic_respawn(n_env, m_cand, cand, entry, limit, span, v_max, seed, counter, env_mask, respawned,
-                                      pick(h, stream), ego, edge_span));
+                                      (hipStream_t)stream, ego, edge_span));
     return EB_OK;
 }
 
@@ -1549,7 +1592,7 @@ int eb_traffic_flow_reset(eb_handle h, int32_t n_env, int32_t per_route, const u
     EB_HIP(hipSetDevice(h->cfg.device));
     EB_HIP(eb::launch_traffic_flow_reset(n_env, per_route, mask, ego, cand, active, timer, emitted, sim_step, phase0, lane,
                                          period, v_max, cand_len, lane_len, random_phase ? 1 : 0, training ? 1 : 0, seed,
-                                         counter, cand_mode, v_light, pick(h, stream)));
+                                         counter, cand_mode, v_light, (hipStream_t)stream));
     return EB_OK;
 }
 
@@ -1565,7 +1608,7 @@ int eb_traffic_flow_step(eb_handle h, int32_t n_env, int32_t per_route, float* c
     EB_HIP(hipSetDevice(h->cfg.device));
     EB_HIP(eb::launch_traffic_flow_step(n_env, per_route, cand, active, timer, emitted, sim_step, lane, period, v_max, dt,
                                         exit_range, accel, lane_len, light_cycle, seed, counter, cand_mode, v_light,
-                                        pick(h, stream)));
+                                        (hipStream_t)stream));
     return EB_OK;
 }
 
@@ -1671,7 +1714,7 @@ int eb_shield_is_safe(eb_handle h, eb_mlp policy, int32_t n_env, const float* ob
     if (policy->cfg.obs_dim != obs_dim(h->cfg) || policy->cfg.out_dim != 4) return fail(EB_EINVAL, "eb_shield_is_safe: the policy does not fit the model (obs_dim, out_dim = 4)");
     if (policy->cfg.device != h->cfg.device) return fail(EB_EINVAL, "eb_shield_is_safe: policy and model live on different devices");
     EB_HIP(hipSetDevice(h->cfg.device));
-    hipStream_t s = pick(h, stream);
+    hipStream_t s = (hipStream_t)stream;
     eb::MlpArgs A;
     // punish += penalty (hier_decision.py:93-97) rides on the step's launch: the env wave that has just made out5's rows 2 / 3 adds
     // the one asked for to the running sum and, in the last look-ahead, sets the flag — two launches per look-ahead instead of three
@@ -1682,7 +1725,9 @@ int eb_shield_is_safe(eb_handle h, eb_mlp policy, int32_t n_env, const float* ob
         if (rc) return rc;
         EB_HIP(eb::launch_mlp(A, s));
         const ShieldArgs sh{punish, safe, penalty == EB_PENALTY_VEH2VEH4REAL ? 3 : 2, t == 0, t == steps - 1};   // rows of rollout_out's outputs (DAM:126)
-        rc = rollout_common(h, n_env, cur, actions, ref_idx, path_id, dst, out5, nullptr, 1, 1, s, 0, 0, nullptr, nullptr, &sh);
+        RolloutLaunch r{cur, dst, actions, ref_idx, path_id, out5};
+        r.shield = &sh;
+        rc = rollout(h, n_env, r, s);
         if (rc) return rc;
         cur = dst;
     }

@@ -55,12 +55,10 @@ __global__ void env_pre_kernel(int n_env, int D, int n_future, int NV, const flo
 
 hipError_t launch_env_pre(int task, int n_env, int D, int n_future, int NV, const float* obs, const float* raw,
                           float* scaled, float* out5, float* d16, float* ego, float* params, hipStream_t s) {
-    const dim3 g((n_env + 127) / 128), b(128);
-    switch (task) {
-        case TASK_LEFT: hipLaunchKernelGGL(env_pre_kernel<TASK_LEFT>, g, b, 0, s, n_env, D, n_future, NV, obs, raw, scaled, out5, d16, ego, params); break;
-        case TASK_STRAIGHT: hipLaunchKernelGGL(env_pre_kernel<TASK_STRAIGHT>, g, b, 0, s, n_env, D, n_future, NV, obs, raw, scaled, out5, d16, ego, params); break;
-        default: hipLaunchKernelGGL(env_pre_kernel<TASK_RIGHT>, g, b, 0, s, n_env, D, n_future, NV, obs, raw, scaled, out5, d16, ego, params); break;
-    }
+    with_task(task, [&](auto t) {
+        hipLaunchKernelGGL(env_pre_kernel<t>, dim3((n_env + 127) / 128), dim3(128), 0, s, n_env, D, n_future, NV, obs, raw, scaled, out5,
+                           d16, ego, params);
+    });
     return hipGetLastError();
 }
 
@@ -97,13 +95,6 @@ size_t get_obs_lds_bytes(int D, int m_cand) {
     const int rs4 = m_cand + ((m_cand & 1) ? 2 : 1);
     return (size_t)64 * rs4 * 16 + (size_t)64 * (D + 1) * 4 + (size_t)64 * (m_cand + 4) + (size_t)256 * (m_cand + 1);
 }
-
-// _judge_done appended to the observation kernel (eb_env_step): the tile's candidates and the new delta_y are in LDS
-struct JudgeArgs {
-    const float* params;      // [n_env, 4]
-    const float* cand_lw;     // [n_env, m_cand, 2] or NULL
-    uint8_t* done_code;       // NULL: observation only (eb_get_obs)
-};
 
 template <int TASK, bool STAGED>
 __global__ __launch_bounds__(256) void get_obs_kernel(int n_env, int D, int n_future, int NV, PathTables pt, VehModes modes,
@@ -551,80 +542,33 @@ hipError_t launch_copy_rows_masked(int n_env, int D, const uint8_t* mask, const 
     return hipGetLastError();
 }
 
-// done_code != NULL appends _judge_done (needs the staged form: check get_obs_is_staged first)
-hipError_t launch_get_obs(int task, int n_env, int D, int n_future, int NV, const PathTables& pt,
-                          const VehModes& modes, const float* ego, const int* ref_idx, int path_id, int m_cand,
-                          const float* cand, const uint8_t* cand_mode, const uint8_t* v_light, const uint8_t* virtual_flag,
-                          float* obs_out, hipStream_t s, const float* params, const float* cand_lw,
-                          uint8_t* done_code, const uint8_t* exit_id, const ExitConsts* xc, const uint8_t* row_mask,
-                          const EnvResetArgs* reset, int tile_envs, int env_waves, long long* trace, long long trace_words,
-                          int scan_one_trip) {
-    if (reset && (exit_id || done_code || !env_step_is_fused(D, NV, m_cand, cand, ego, nullptr, nullptr, reset->params))) return hipErrorInvalidValue;
-    if (exit_id) {
-        if (done_code || !xc) return hipErrorInvalidValue;
-        const dim3 g((n_env + 63) / 64), b(64);
-        switch (task) {
-            case TASK_LEFT: hipLaunchKernelGGL(get_obs_exit_kernel<TASK_LEFT>, g, b, 0, s, n_env, D, n_future, NV, pt, modes, ego, ref_idx, path_id, m_cand, cand, cand_mode, v_light, virtual_flag, exit_id, *xc, row_mask, obs_out); break;
-            case TASK_STRAIGHT: hipLaunchKernelGGL(get_obs_exit_kernel<TASK_STRAIGHT>, g, b, 0, s, n_env, D, n_future, NV, pt, modes, ego, ref_idx, path_id, m_cand, cand, cand_mode, v_light, virtual_flag, exit_id, *xc, row_mask, obs_out); break;
-            default: hipLaunchKernelGGL(get_obs_exit_kernel<TASK_RIGHT>, g, b, 0, s, n_env, D, n_future, NV, pt, modes, ego, ref_idx, path_id, m_cand, cand, cand_mode, v_light, virtual_flag, exit_id, *xc, row_mask, obs_out); break;
-        }
-        return hipGetLastError();
-    }
-    if (!done_code && env_step_is_fused(D, NV, m_cand, cand, ego, nullptr, nullptr, reset ? reset->params : nullptr)) {
-        // the observation alone through the one-launch step's machinery (eb_env_step.hip, OBS variant): pair-parallel
-        // staging and the bit-set slot selection instead of one lane per env walking its candidates
-        EnvStepArgs A;
-        std::memset(&A, 0, sizeof A);
-        auto magic = [](int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); };
-        A.n_env = n_env; A.D = D; A.n_future = n_future; A.NV = NV; A.m_cand = m_cand; A.path_id = path_id;
-        A.d_magic = magic(D); A.m_magic = magic(m_cand); A.nv_magic = magic(NV);
-        A.pt = pt; A.modes = modes;
-        env_step_slot_plan(modes, NV, A);
-        A.ref_idx = ref_idx; A.ego = const_cast<float*>(ego); A.cand = const_cast<float*>(cand); A.cand_mode = cand_mode;
-        A.v_light = v_light; A.virtual_flag = virtual_flag; A.obs_out = obs_out; A.obs_only = 1; A.row_mask = row_mask;
-        A.tile_envs = tile_envs; A.waves = env_waves; A.trace = trace; A.trace_words = trace_words; A.scan_one_trip = scan_one_trip;
-        if (reset) {   // eb_env_reset_pool: the masked rows' state is drawn in the same launch
-            A.reset = 1; A.training = reset->training; A.reset_seed = reset->seed; A.reset_counter = reset->counter;
-            A.params = reset->params; A.ref_idx_out = reset->ref_idx; A.virtual_flag = reset->virtual_flag; A.virtual_out = reset->virtual_flag;
-            A.v_light = nullptr; A.v_light_out = reset->v_light; A.done_code = reset->done_code;
-            A.pool_entry = reset->entry; A.pool_span = reset->span; A.pool_v_max = reset->v_max; A.edge_span = reset->edge_span;
-            A.pool_seed = reset->pool_seed; A.pool_counter = reset->pool_counter;
-            A.obs = reset->obs_src; A.done_src = reset->done_src; A.episode_step = reset->episode_step;
-        }
-        return launch_env_step(task, A, s);
-    }
-    const size_t lds = get_obs_lds_bytes(D, m_cand);
+hipError_t launch_get_obs_exit(int task, int n_env, int D, int n_future, int NV, const PathTables& pt, const VehModes& modes,
+                               const float* ego, const int* ref_idx, int path_id, int m_cand, const float* cand,
+                               const uint8_t* cand_mode, const uint8_t* v_light, const uint8_t* virtual_flag, const uint8_t* exit_id,
+                               const ExitConsts& xc, const uint8_t* row_mask, float* obs_out, hipStream_t s) {
+    with_task(task, [&](auto t) {
+        hipLaunchKernelGGL(get_obs_exit_kernel<t>, dim3((n_env + 63) / 64), dim3(64), 0, s, n_env, D, n_future, NV, pt, modes, ego, ref_idx,
+                           path_id, m_cand, cand, cand_mode, v_light, virtual_flag, exit_id, xc, row_mask, obs_out);
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_get_obs(int task, int n_env, int D, int n_future, int NV, const PathTables& pt, const VehModes& modes,
+                          const float* ego, const int* ref_idx, int path_id, int m_cand, const float* cand, const uint8_t* cand_mode,
+                          const uint8_t* v_light, const uint8_t* virtual_flag, const uint8_t* row_mask, float* obs_out, hipStream_t s,
+                          const JudgeArgs* judge) {
     const bool staged = !row_mask && get_obs_is_staged(D, m_cand, cand);   // (a masked pass outside the one-launch machinery: one thread per env)
-    if (done_code && !staged) return hipErrorInvalidValue;
-    const JudgeArgs J{params, cand_lw, done_code};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev = dev < 0 || dev >= 64 ? 0 : dev;
-    hipError_t e = hipSuccess;
-#define EB_GET_OBS(T)                                                                                                \
-    do {                                                                                                             \
-        const dim3 g((n_env + 63) / 64), b(staged ? 256 : 64);                                                       \
-        if (staged) {                                                                                                \
-            static size_t granted[64];   /* the > 48 KB opt-in is per kernel and device, and sticky */               \
-            if (lds > 48 * 1024 && lds > granted[dev]) {                                                             \
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(&get_obs_kernel<T, true>),                    \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                       \
-                if (e == hipSuccess) granted[dev] = lds;                                                             \
-            }                                                                                                        \
-            if (e == hipSuccess)                                                                                     \
-                hipLaunchKernelGGL((get_obs_kernel<T, true>), g, b, lds, s, n_env, D, n_future, NV, pt, modes, ego,  \
-                                   ref_idx, path_id, m_cand, cand, cand_mode, v_light, virtual_flag, obs_out, J, row_mask); \
-        } else {                                                                                                     \
-            hipLaunchKernelGGL((get_obs_kernel<T, false>), g, b, 0, s, n_env, D, n_future, NV, pt, modes, ego,       \
-                               ref_idx, path_id, m_cand, cand, cand_mode, v_light, virtual_flag, obs_out, J, row_mask); \
-        }                                                                                                            \
-    } while (0)
-    switch (task) {
-        case TASK_LEFT: EB_GET_OBS(TASK_LEFT); break;
-        case TASK_STRAIGHT: EB_GET_OBS(TASK_STRAIGHT); break;
-        default: EB_GET_OBS(TASK_RIGHT); break;
-    }
-#undef EB_GET_OBS
+    if (judge && !staged) return hipErrorInvalidValue;
+    const JudgeArgs J = judge ? *judge : JudgeArgs{nullptr, nullptr, nullptr};
+    const size_t lds = staged ? get_obs_lds_bytes(D, m_cand) : 0;
+    const int dev = current_device_index();
+    const hipError_t e = with_task(task, [&](auto t) {
+        return with_bool(staged, [&](auto st) {
+            return launch_lds<&get_obs_kernel<t, st>>(dim3((n_env + 63) / 64), dim3(st ? 256 : 64), lds, dev, s, n_env, D, n_future, NV, pt,
+                                                      modes, ego, ref_idx, path_id, m_cand, cand, cand_mode, v_light, virtual_flag,
+                                                      obs_out, J, row_mask);
+        });
+    });
     return e != hipSuccess ? e : hipGetLastError();
 }
 
@@ -891,11 +835,9 @@ hipError_t launch_traffic_flow_step(int n_env, int K, float* cand, uint8_t* acti
                                     float exit_range, float accel, float lane_len, int light_cycle, uint64_t seed,
                                     uint64_t counter, uint8_t* cand_mode, uint8_t* v_light, hipStream_t s) {
     if (n_env <= 0) return hipSuccess;
-    const int M = 12 * K;
-    const unsigned m_magic = M <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)M - 1) / (unsigned)M);
     hipLaunchKernelGGL(traffic_flow_step_kernel, dim3((n_env + FS_ENVS - 1) / FS_ENVS), dim3(256), 0, s, n_env, K, cand, active,
                        timer, emitted, sim_step, lane, period, v_max, dt, exit_range, accel, lane_len, light_cycle, seed, counter,
-                       cand_mode, v_light, m_magic);
+                       cand_mode, v_light, div_magic(12 * K));
     return hipGetLastError();
 }
 

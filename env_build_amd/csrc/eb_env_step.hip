@@ -46,7 +46,7 @@ void env_step_slot_plan(const VehModes& modes, int NV, EnvStepArgs& A) {
         } else A.dm_ok = 0;              // a third slot of one mode
     }
     if (A.n_dm > EB_VMODE_COUNT) A.dm_ok = 0;   // (cannot happen: twelve mode ids)
-    A.dm_magic = A.n_dm <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)A.n_dm - 1) / (unsigned)A.n_dm);
+    A.dm_magic = div_magic(A.n_dm);
 }
 
 // cand and params are accessed as float4, ego / actions / scaled actions as float2: a buffer that is not aligned to its vector
@@ -70,9 +70,7 @@ hipError_t launch_env_step(int task, const EnvStepArgs& A_in, hipStream_t s) {
     int ET = A.tile_envs == 16 || A.tile_envs == 32 || A.tile_envs == 64 ? A.tile_envs
                                                                            : env_step_tile_envs(A.n_env, A.D, A.NV, A.m_cand, A.flow_on != 0);
     if (ET != 16 && env_step_lds_bytes(A.D, A.NV, A.m_cand, ET, A.flow_on != 0) + ES_STATIC_LDS > 156 * 1024) ET = 16;   // a forced shape that does not fit
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev = dev < 0 || dev >= 64 ? 0 : dev;
+    const int dev = current_device_index();
     // eight waves per block at small and medium batches (16- / 32-env tiles: few blocks per CU, the launch is a wave's instruction
     // stream) — the step, the observation and the masked reset alike —, four otherwise; A.waves = 4 / 8 forces it (eb_debug_set_env_waves)
     const int wforce = A.waves;
@@ -91,11 +89,7 @@ hipError_t launch_env_step(int task, const EnvStepArgs& A_in, hipStream_t s) {
     const bool w8 = wforce != 4 && ET <= 32 && (n_blocks <= 3 * n_cu[dev] || wforce == 8);
     const size_t lds = env_step_lds_bytes(A.D, A.NV, A.m_cand, ET, A.flow_on != 0, !w8);
     if (A.trace && A.trace_words < (long long)n_blocks * (w8 ? 8 : 4) * 16) A.trace = nullptr;   // a mark buffer too small for this launch: no marks
-    switch (task) {
-        case TASK_LEFT: return launch_env_step_task<TASK_LEFT>(A, ET, w8, n_blocks, lds, dev, s);
-        case TASK_STRAIGHT: return launch_env_step_task<TASK_STRAIGHT>(A, ET, w8, n_blocks, lds, dev, s);
-        default: return launch_env_step_task<TASK_RIGHT>(A, ET, w8, n_blocks, lds, dev, s);
-    }
+    return with_task(task, [&](auto t) { return launch_env_step_task<t>(A, ET, w8, n_blocks, lds, dev, s); });
 }
 
 }  // namespace eb

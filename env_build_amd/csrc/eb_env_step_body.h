@@ -1266,43 +1266,18 @@ __global__ __launch_bounds__(NW * 64) void env_reset_pool_kernel(const EnvStepAr
 // file took 95 s of a 115 s build as one unit).  Shape decisions (tile, waves, LDS bytes) are the caller's: launch_env_step.
 template <int TASK>
 hipError_t launch_env_step_task(const EnvStepArgs& A, int ET, bool w8, int n_blocks, size_t lds, int dev, hipStream_t s) {
-    hipError_t e = hipSuccess;
     const dim3 g(n_blocks), b(w8 ? 512 : 256);
-#define EB_ENV_STEP_W(T, E, O, AU, W)                                                                                 \
-    do {                                                                                                             \
-        static size_t granted[64];   /* the > 48 KB opt-in is per kernel and device, and sticky */                   \
-        if (lds > 48 * 1024 && lds > granted[dev]) {                                                                 \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&env_step_kernel<T, E, O, AU, W>),                 \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
-            if (e == hipSuccess) granted[dev] = lds;                                                                 \
-        }                                                                                                            \
-        if (e == hipSuccess) hipLaunchKernelGGL((env_step_kernel<T, E, O, AU, W>), g, b, lds, s, A);                 \
-    } while (0)
-#define EB_ENV_STEP(T, E, O, AU) do { if ((E) <= 32 && w8) EB_ENV_STEP_W(T, (E) <= 32 ? (E) : 32, O, AU, 8); else EB_ENV_STEP_W(T, E, O, AU, 4); } while (0)
-#define EB_ENV_RESET_W(T, E, W)                                                                                       \
-    do {                                                                                                             \
-        static size_t granted[64];                                                                                   \
-        if (lds > 48 * 1024 && lds > granted[dev]) {                                                                 \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&env_reset_pool_kernel<T, E, W>),                  \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
-            if (e == hipSuccess) granted[dev] = lds;                                                                 \
-        }                                                                                                            \
-        if (e == hipSuccess) hipLaunchKernelGGL((env_reset_pool_kernel<T, E, W>), g, b, lds, s, A);                  \
-    } while (0)
-#define EB_ENV_RESET(T, E) do { if ((E) <= 32 && w8) EB_ENV_RESET_W(T, (E) <= 32 ? (E) : 32, 8); else EB_ENV_RESET_W(T, E, 4); } while (0)
-#define EB_ENV_STEP_T(T)                                                                                             \
-    do {                                                                                                             \
-        if (A.reset) { if (ET == 16) EB_ENV_RESET(T, 16); else if (ET == 32) EB_ENV_RESET(T, 32); else EB_ENV_RESET(T, 64); } \
-        else if (A.obs_only) { if (ET == 16) EB_ENV_STEP(T, 16, true, false); else if (ET == 32) EB_ENV_STEP(T, 32, true, false); else EB_ENV_STEP(T, 64, true, false); } \
-        else if (A.auto_reset) { if (ET == 16) EB_ENV_STEP(T, 16, false, true); else if (ET == 32) EB_ENV_STEP(T, 32, false, true); else EB_ENV_STEP(T, 64, false, true); } \
-        else { if (ET == 16) EB_ENV_STEP(T, 16, false, false); else if (ET == 32) EB_ENV_STEP(T, 32, false, false); else EB_ENV_STEP(T, 64, false, false); } \
-    } while (0)
-    EB_ENV_STEP_T(TASK);
-#undef EB_ENV_STEP_T
-#undef EB_ENV_RESET
-#undef EB_ENV_RESET_W
-#undef EB_ENV_STEP
-#undef EB_ENV_STEP_W
+    auto launch = [&](auto E, auto NW) {
+        if (A.reset) return launch_lds<&env_reset_pool_kernel<TASK, E, NW>>(g, b, lds, dev, s, A);
+        if (A.obs_only) return launch_lds<&env_step_kernel<TASK, E, true, false, NW>>(g, b, lds, dev, s, A);
+        if (A.auto_reset) return launch_lds<&env_step_kernel<TASK, E, false, true, NW>>(g, b, lds, dev, s, A);
+        return launch_lds<&env_step_kernel<TASK, E, false, false, NW>>(g, b, lds, dev, s, A);
+    };
+    auto tile = [&](auto E) {   // eight waves per block exist for the 16- and 32-env tiles only
+        if constexpr (E <= 32) { if (w8) return launch(E, int_c<8>{}); }
+        return launch(E, int_c<4>{});
+    };
+    const hipError_t e = ET == 16 ? tile(int_c<16>{}) : ET == 32 ? tile(int_c<32>{}) : tile(int_c<64>{});
     return e != hipSuccess ? e : hipGetLastError();
 }
 

@@ -3,11 +3,51 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "eb_device.h"
 
 namespace eb {
 
 constexpr int EB_MAX_VEH_SLOTS = 64;
+
+// ---- host-side launch helpers ----
+// a run-time choice -> the template argument of a kernel: f(int_c<TASK_...>{}) / f(std::true_type{}); inside f the tag converts to
+// its value where a template argument is expected (kernel<t, fast>, std::conditional_t<f16, _Float16, float>)
+template <int V> using int_c = std::integral_constant<int, V>;
+template <class F> decltype(auto) with_task(int task, F&& f) {   // (any other value runs as TASK_RIGHT)
+    switch (task) {
+        case TASK_LEFT: return f(int_c<TASK_LEFT>{});
+        case TASK_STRAIGHT: return f(int_c<TASK_STRAIGHT>{});
+        default: return f(int_c<TASK_RIGHT>{});
+    }
+}
+template <class F> decltype(auto) with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// the current device as an index into the per-device tables of the launchers (0 when out of their range)
+inline int current_device_index() {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    return dev < 0 || dev >= 64 ? 0 : dev;
+}
+// the opt-in for more than 48 KB of dynamic LDS is per kernel and device, and sticky: hipFuncSetAttribute only when a launch of K
+// needs more than it was granted before
+template <auto K> hipError_t grant_lds(size_t lds, int dev) {
+    static size_t granted[64];
+    if (lds <= 48 * 1024 || lds <= granted[dev]) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) granted[dev] = lds;
+    return e;
+}
+// a launch of K with `lds` bytes of dynamic LDS, behind its opt-in
+template <auto K, class... Args>
+hipError_t launch_lds(dim3 g, dim3 b, size_t lds, int dev, hipStream_t s, const Args&... args) {
+    const hipError_t e = grant_lds<K>(lds, dev);
+    if (e == hipSuccess) hipLaunchKernelGGL(K, g, b, lds, s, args...);
+    return e;
+}
+// ceil(2^32 / d): item / d == umulhi(item, magic) for the item counts of a launch; 0 stands for d <= 1 (item / 1)
+inline unsigned div_magic(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
 
 struct VehModes {
     uint8_t turn[64];   // TURN_* per slot (predict_for_a_mode, DAM:416-421)
@@ -38,7 +78,7 @@ struct FusedArgs {
     int actions_raw;           // 1: raw [-1,1] actions (rollout_out), 0: already scaled
     int do_rewards;            // 0: compute_next_obses only
     int rolling;               // per-step kernel, 2048-record tile: 1 = three record loads in flight per lane, record k + 3 requested when
-                               // record k is done; 0 = every record requested up front (eb_capi.hip:rollout_fused decides)
+                               // record k is done; 0 = every record requested up front (eb_capi.hip:rollout_sched decides)
     int by_progress;           // per-step kernel: 1 = a record wave's issue priority falls as it advances
     long long* trace;          // profiling aid (eb_debug_set_trace): [n_waves][8] s_memrealtime marks, or NULL
     long long trace_words;     //   its capacity in 64-bit words: a mark past it is dropped
@@ -117,18 +157,23 @@ struct ExitConsts {
     double c[4], s[4];
     float cf[8], sf[8];
 };
-// done_code != NULL appends _judge_done to the observation kernel (only in its LDS-staged form: get_obs_is_staged).
-// exit_id != NULL: the 12-ego scene's frames (one thread per env, float64 vehicle coordinates); needs `xc`.
-struct EnvResetArgs;
-hipError_t launch_get_obs(int task, int n_env, int D, int n_future, int NV, const PathTables& pt,
-                          const VehModes& modes, const float* ego, const int* ref_idx, int path_id, int m_cand,
-                          const float* cand, const uint8_t* cand_mode, const uint8_t* v_light, const uint8_t* virtual_flag,
-                          float* obs_out, hipStream_t s, const float* params = nullptr, const float* cand_lw = nullptr,
-                          uint8_t* done_code = nullptr, const uint8_t* exit_id = nullptr, const ExitConsts* xc = nullptr,
-                          const uint8_t* row_mask = nullptr, const EnvResetArgs* reset = nullptr,
-                          int tile_envs = 0, int env_waves = 0, long long* trace = nullptr, long long trace_words = 0,
-                          int scan_one_trip = 0);
-                          // tile_envs / env_waves / trace: EnvStepArgs::tile_envs / waves / trace for the one-launch machinery
+// exit ids: the 12-ego scene's frames (one thread per env, float64 vehicle coordinates); row_mask nullable
+hipError_t launch_get_obs_exit(int task, int n_env, int D, int n_future, int NV, const PathTables& pt, const VehModes& modes,
+                               const float* ego, const int* ref_idx, int path_id, int m_cand, const float* cand,
+                               const uint8_t* cand_mode, const uint8_t* v_light, const uint8_t* virtual_flag, const uint8_t* exit_id,
+                               const ExitConsts& xc, const uint8_t* row_mask, float* obs_out, hipStream_t s);
+// _judge_done appended to the observation kernel (eb_env_step): the tile's candidates and the new delta_y are in LDS
+struct JudgeArgs {
+    const float* params;      // [n_env, 4]
+    const float* cand_lw;     // [n_env, m_cand, 2] or NULL
+    uint8_t* done_code;       // NULL: observation only (eb_get_obs)
+};
+// the per-thread / LDS-staged observation kernel (the one-launch form is launch_env_step with EnvStepArgs::obs_only); judge != NULL
+// appends _judge_done, which needs the staged form (get_obs_is_staged) and no row mask
+hipError_t launch_get_obs(int task, int n_env, int D, int n_future, int NV, const PathTables& pt, const VehModes& modes,
+                          const float* ego, const int* ref_idx, int path_id, int m_cand, const float* cand, const uint8_t* cand_mode,
+                          const uint8_t* v_light, const uint8_t* virtual_flag, const uint8_t* row_mask, float* obs_out, hipStream_t s,
+                          const JudgeArgs* judge = nullptr);
 hipError_t launch_exit_frame(int n, const uint8_t* exit_id, int inverse, const ExitConsts& xc, const float* ego, float* out,
                              hipStream_t s);
 hipError_t launch_env_reset(int task, int n_env, const PathTables& pt, const uint8_t* mask, uint64_t seed, uint64_t counter,
@@ -231,21 +276,6 @@ struct EnvStepArgs {
     // reset = 1 (eb_env_reset_pool): the masked rows' counts are cleared (max_episode_steps unused)
     int* episode_step;
     int max_episode_steps;
-};
-struct EnvResetArgs {                      // launch_get_obs(..., reset): what eb_env_reset_pool adds to a masked observation pass
-    uint64_t seed, counter;                // eb_env_reset's
-    int training;
-    float* params;
-    int* ref_idx;
-    uint8_t* virtual_flag;
-    uint8_t* v_light;                      // nullable
-    uint8_t* done_code;                    // nullable
-    const float* entry;                    // the pool rule
-    float span, v_max, edge_span;
-    uint64_t pool_seed, pool_counter;
-    const float* obs_src;                  // nullable: the observation rows of the envs outside the mask
-    const uint8_t* done_src;               // nullable: their done codes
-    int* episode_step;                     // nullable: the masked rows' episode step counts are cleared
 };
 size_t env_step_lds_bytes(int D, int NV, int m_cand, int tile_envs, bool flow = false, bool four_waves = false);
 int env_step_tile_envs(int n_env, int D, int NV, int m_cand, bool flow = false);

@@ -121,12 +121,9 @@ __global__ void rewards_kernel(int n_env, int D, int n_future, int NV, const flo
 
 hipError_t launch_rewards(int task, int n_env, int D, int n_future, int NV, const float* obs, const float* act,
                           float* out5, float* d16, hipStream_t s) {
-    const dim3 g((n_env + 127) / 128), b(128);
-    switch (task) {
-        case TASK_LEFT: hipLaunchKernelGGL(rewards_kernel<TASK_LEFT>, g, b, 0, s, n_env, D, n_future, NV, obs, act, out5, d16); break;
-        case TASK_STRAIGHT: hipLaunchKernelGGL(rewards_kernel<TASK_STRAIGHT>, g, b, 0, s, n_env, D, n_future, NV, obs, act, out5, d16); break;
-        default: hipLaunchKernelGGL(rewards_kernel<TASK_RIGHT>, g, b, 0, s, n_env, D, n_future, NV, obs, act, out5, d16); break;
-    }
+    with_task(task, [&](auto t) {
+        hipLaunchKernelGGL(rewards_kernel<t>, dim3((n_env + 127) / 128), dim3(128), 0, s, n_env, D, n_future, NV, obs, act, out5, d16);
+    });
     return hipGetLastError();
 }
 
@@ -160,12 +157,10 @@ __global__ void tracking_kernel(int n, PathTables pt, const float* __restrict__ 
 hipError_t launch_tracking(int task, int n, const PathTables& pt, const float* xs, const float* ys, const float* phis,
                            const float* vs, const int* ref_idx, int path_id, int n_future, int ratio, float* out,
                            int* out_index, float* out_points, hipStream_t s) {
-    const dim3 g((n + 127) / 128), b(128);
-    switch (task) {
-        case TASK_LEFT: hipLaunchKernelGGL(tracking_kernel<TASK_LEFT>, g, b, 0, s, n, pt, xs, ys, phis, vs, ref_idx, path_id, n_future, ratio, out, out_index, out_points); break;
-        case TASK_STRAIGHT: hipLaunchKernelGGL(tracking_kernel<TASK_STRAIGHT>, g, b, 0, s, n, pt, xs, ys, phis, vs, ref_idx, path_id, n_future, ratio, out, out_index, out_points); break;
-        default: hipLaunchKernelGGL(tracking_kernel<TASK_RIGHT>, g, b, 0, s, n, pt, xs, ys, phis, vs, ref_idx, path_id, n_future, ratio, out, out_index, out_points); break;
-    }
+    with_task(task, [&](auto t) {
+        hipLaunchKernelGGL(tracking_kernel<t>, dim3((n + 127) / 128), dim3(128), 0, s, n, pt, xs, ys, phis, vs, ref_idx, path_id, n_future,
+                           ratio, out, out_index, out_points);
+    });
     return hipGetLastError();
 }
 
@@ -294,12 +289,10 @@ __global__ void ss_kernel(int n_env, int D, int n_future, int NV, PathTables pt,
 hipError_t launch_ss(int task, int n_env, int D, int n_future, int NV, const PathTables& pt, const VehModes& modes,
                      const float* obs, const float* actions, const int* ref_idx, int path_id, int training,
                      float one_m_lam, float* out, hipStream_t s) {
-    const dim3 g((n_env + 127) / 128), b(128);
-    switch (task) {
-        case TASK_LEFT: hipLaunchKernelGGL(ss_kernel<TASK_LEFT>, g, b, 0, s, n_env, D, n_future, NV, pt, modes, obs, actions, ref_idx, path_id, training, one_m_lam, out); break;
-        case TASK_STRAIGHT: hipLaunchKernelGGL(ss_kernel<TASK_STRAIGHT>, g, b, 0, s, n_env, D, n_future, NV, pt, modes, obs, actions, ref_idx, path_id, training, one_m_lam, out); break;
-        default: hipLaunchKernelGGL(ss_kernel<TASK_RIGHT>, g, b, 0, s, n_env, D, n_future, NV, pt, modes, obs, actions, ref_idx, path_id, training, one_m_lam, out); break;
-    }
+    with_task(task, [&](auto t) {
+        hipLaunchKernelGGL(ss_kernel<t>, dim3((n_env + 127) / 128), dim3(128), 0, s, n_env, D, n_future, NV, pt, modes, obs, actions, ref_idx,
+                           path_id, training, one_m_lam, out);
+    });
     return hipGetLastError();
 }
 

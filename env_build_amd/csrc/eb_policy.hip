@@ -293,28 +293,11 @@ hipError_t launch_mlp(const MlpArgs& A, hipStream_t s) {
     if (A.n <= 0) return hipSuccess;
     const dim3 g((A.n + MLP_ROWS - 1) / MLP_ROWS), b(MLP_THREADS);
     const size_t lds = mlp_lds_bytes(A);
-    hipError_t e = hipSuccess;
-    // the opt-in for > 48 KB of dynamic LDS is per kernel and device and sticky: raise it only when a launch needs more
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev = dev < 0 || dev >= 64 ? 0 : dev;
-#define EB_MLP_LAUNCH(RT, CT)                                                                                     \
-    do {                                                                                                          \
-        static size_t granted[64];                                                                                \
-        if (lds > 48 * 1024 && lds > granted[dev]) {                                                              \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_kernel<RT, CT>),                          \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                        \
-            if (e == hipSuccess) granted[dev] = lds;                                                              \
-        }                                                                                                         \
-        if (e == hipSuccess) hipLaunchKernelGGL((mlp_kernel<RT, CT>), g, b, lds, s, A);                           \
-    } while (0)
-    switch (A.units) {
-        case 64: EB_MLP_LAUNCH(1, 1); break;
-        case 128: EB_MLP_LAUNCH(2, 1); break;
-        case 256: EB_MLP_LAUNCH(2, 2); break;
-        default: EB_MLP_LAUNCH(2, 4); break;
-    }
-#undef EB_MLP_LAUNCH
+    const int dev = current_device_index();
+    const hipError_t e = A.units == 64 ? launch_lds<&mlp_kernel<1, 1>>(g, b, lds, dev, s, A)
+                         : A.units == 128 ? launch_lds<&mlp_kernel<2, 1>>(g, b, lds, dev, s, A)
+                         : A.units == 256 ? launch_lds<&mlp_kernel<2, 2>>(g, b, lds, dev, s, A)
+                                          : launch_lds<&mlp_kernel<2, 4>>(g, b, lds, dev, s, A);
     return e != hipSuccess ? e : hipGetLastError();
 }
 

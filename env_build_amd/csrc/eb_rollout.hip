@@ -31,7 +31,7 @@
 // waves that are BEHIND issue first (s_setprio by progress: the last wave, not the average one, ends a launch: 14.85 -> 14.0 us at
 // 65 536 x 32); a grid of at most three tiles per CU — and any grid of 32-env tiles — keeps three record loads in flight per lane
 // and requests record k + 3 when record k is done (every wave's first records come back sooner, the block's life shrinks: 9.3 ->
-// 8.5 us per step at 32 768 x 32, 25.7 -> 24.5 at 65 536 x 64).  Which grid gets what: eb_capi.hip:rollout_fused, from the sweeps of
+// 8.5 us per step at 32 768 x 32, 25.7 -> 24.5 at 65 536 x 64).  Which grid gets what: eb_capi.hip:rollout_sched, from the sweeps of
 // profiles/r6_sched_sweep1-2.txt.
 #include <type_traits>
 
@@ -1072,59 +1072,18 @@ int fused_tile_records(int variant) {
     }
 }
 
-#define EB_HOT_ARGS(ST) reinterpret_cast<const ST*>(A.obs_in), reinterpret_cast<ST*>(A.obs_out), A.n_env, A.obs_dim, A.n_veh, \
-                        A.envs_per_tile, A.nv_magic, (A.do_rewards ? HOT_REWARDS : 0) | (A.by_progress ? HOT_PRIO : 0), A.acc_rec, \
-                        reinterpret_cast<const unsigned char*>(A.dt) + offsetof(PathTables, turn)
-#define EB_LAUNCH_TASK(KERNEL, FAST_, PF_, ST)                                                                  \
-    switch (task) {                                                                                             \
-        case TASK_LEFT: hipLaunchKernelGGL((KERNEL<TASK_LEFT, FAST_, PF_, ST>), g, b, 0, s, EB_HOT_ARGS(ST), A); break; \
-        case TASK_STRAIGHT: hipLaunchKernelGGL((KERNEL<TASK_STRAIGHT, FAST_, PF_, ST>), g, b, 0, s, EB_HOT_ARGS(ST), A); break; \
-        default: hipLaunchKernelGGL((KERNEL<TASK_RIGHT, FAST_, PF_, ST>), g, b, 0, s, EB_HOT_ARGS(ST), A); break; \
-    }
-#define EB_LAUNCH_FAST(KERNEL, RW, PF_, ST)                                                                     \
-    if ((RW * 64) % A.n_veh == 0) { EB_LAUNCH_TASK(KERNEL, true, PF_, ST) } else { EB_LAUNCH_TASK(KERNEL, false, PF_, ST) }
-#define EB_LAUNCH(KERNEL, RW, PF_)                                                                              \
-    {                                                                                                           \
-        const dim3 g(grid), b((RW + 1) * 64);                                                                   \
-        if (A.storage_f16) { EB_LAUNCH_FAST(KERNEL, RW, PF_, _Float16) } else { EB_LAUNCH_FAST(KERNEL, RW, PF_, float) } \
-    }
-
-#define EB_TAPE_ARGS(ST) reinterpret_cast<const ST*>(A.obs_in), reinterpret_cast<ST*>(A.obs_out), A.n_env, A.obs_dim, A.n_veh, \
-                         A.envs_per_tile, A.nv_magic, horizon
-#define EB_TAPE_TASK(KERNEL, FAST_, ST)                                                                         \
-    switch (task) {                                                                                             \
-        case TASK_LEFT: hipLaunchKernelGGL((KERNEL<TASK_LEFT, FAST_, ST>), g, b, dyn, s, EB_TAPE_ARGS(ST), A); break; \
-        case TASK_STRAIGHT: hipLaunchKernelGGL((KERNEL<TASK_STRAIGHT, FAST_, ST>), g, b, dyn, s, EB_TAPE_ARGS(ST), A); break; \
-        default: hipLaunchKernelGGL((KERNEL<TASK_RIGHT, FAST_, ST>), g, b, dyn, s, EB_TAPE_ARGS(ST), A); break;    \
-    }
-#define EB_TAPE_FAST(KERNEL, RW, ST)                                                                            \
-    if ((RW * 64) % A.n_veh == 0) { EB_TAPE_TASK(KERNEL, true, ST) } else { EB_TAPE_TASK(KERNEL, false, ST) }
-#define EB_TAPE_LAUNCH(KERNEL, RW, EXTRA_WAVES)                                                                 \
-    {                                                                                                           \
-        const dim3 g(grid), b((RW + 1 + EXTRA_WAVES) * 64);                                                               \
-        const size_t dyn = (size_t)A.stage_entries * 12;                                                        \
-        if (A.storage_f16) { EB_TAPE_FAST(KERNEL, RW, _Float16) } else { EB_TAPE_FAST(KERNEL, RW, float) }       \
-    }
-
-#define EB_TAPE_OCC(KERNEL, RW)                                                                                  \
-    {                                                                                                           \
-        int nb = 0;                                                                                             \
-        const bool fast = (RW * 64) % n_veh == 0;                                                               \
-        hipError_t e;                                                                                           \
-        if (storage_f16) e = fast ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, KERNEL<TASK_LEFT, true, _Float16>, (RW + 3) * 64, dyn_bytes) \
-                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, KERNEL<TASK_LEFT, false, _Float16>, (RW + 3) * 64, dyn_bytes); \
-        else e = fast ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, KERNEL<TASK_LEFT, true, float>, (RW + 3) * 64, dyn_bytes)       \
-                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, KERNEL<TASK_LEFT, false, float>, (RW + 3) * 64, dyn_bytes);     \
-        return e == hipSuccess ? nb : 0;                                                                        \
-    }
 // resident blocks per CU of the tape kernel (the three tasks compile to the same resources; `left` stands for all)
 int tape_blocks_per_cu(int task, int variant, int n_veh, int storage_f16, size_t dyn_bytes) {
     (void)task;
-    switch (variant) {
-        case 0: EB_TAPE_OCC(rollout_gated_4x8, 4)
-        case 1: EB_TAPE_OCC(rollout_gated_4x4, 4)
-        default: EB_TAPE_OCC(rollout_gated_1x4, 1)
-    }
+    const int rw = variant == 0 || variant == 1 ? 4 : 1;
+    int nb = 0;
+    const hipError_t e = with_bool(storage_f16, [&](auto f16) { return with_bool((rw * 64) % n_veh == 0, [&](auto fast) {
+        using ST = std::conditional_t<f16, _Float16, float>;
+        auto occ = [&](auto kernel) { return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, (rw + 3) * 64, dyn_bytes); };
+        return variant == 0 ? occ(rollout_gated_4x8<TASK_LEFT, fast, ST>) : variant == 1 ? occ(rollout_gated_4x4<TASK_LEFT, fast, ST>)
+                                                                          : occ(rollout_gated_1x4<TASK_LEFT, fast, ST>);
+    }); });
+    return e == hipSuccess ? nb : 0;
 }
 
 // eb_gate_feed: the reference producer of a gated rollout — one block that hands the staged action tape over step by
@@ -1180,47 +1139,58 @@ hipError_t launch_gate_feed(int horizon, int n_blocks, size_t step_bytes, const 
     return hipGetLastError();
 }
 
-// A.actions = the tape [horizon, n_env, 2], A.out5 = [horizon, 5, n_env]
 // a mark buffer (eb_debug_set_trace) that does not hold a row of 8 words for every wave of the launch is dropped: the kernels do not test
+// (rows are indexed by blockIdx.x * (RW + 1) + wave: the couriers of the gated kernels do not mark)
 static FusedArgs trace_checked(const FusedArgs& A_in, int grid, int waves_per_block) {
     FusedArgs A = A_in;
     if (A.trace && A.trace_words < (long long)grid * waves_per_block * 8) A.trace = nullptr;
     return A;
 }
 
+// A.actions = the tape [horizon, n_env, 2], A.out5 = [horizon, 5, n_env]
 hipError_t launch_rollout_tape_fused(int task, int variant, const FusedArgs& A_in, int horizon, int grid, hipStream_t s) {
-    const FusedArgs A = trace_checked(A_in, grid, (variant == 2 ? 1 : 4) + 1);   // (rows are indexed by blockIdx.x * (RW + 1) + wave: the couriers do not mark)
-    if (A.gate_ready) {
-        switch (variant) {
-            case 0: EB_TAPE_LAUNCH(rollout_gated_4x8, 4, 2) break;
-            case 1: EB_TAPE_LAUNCH(rollout_gated_4x4, 4, 2) break;
-            default: EB_TAPE_LAUNCH(rollout_gated_1x4, 1, 2) break;
-        }
-        return hipGetLastError();
-    }
-    switch (variant) {
-        case 0: {
-            const dim3 g(grid), b((4 + 1) * 64);
-            const size_t dyn = (size_t)A.stage_entries * 12;
-            if ((4 * 64) % A.n_veh != 0) return hipErrorInvalidValue;            // the host routes these to the 4 x 4 tile (tape_tile_variant)
-            if (A.storage_f16) { EB_TAPE_TASK(rollout_tape_4x8, true, _Float16) } else { EB_TAPE_TASK(rollout_tape_4x8, true, float) }
-        } break;
-        case 1: EB_TAPE_LAUNCH(rollout_tape_4x4, 4, 0) break;
-        default: EB_TAPE_LAUNCH(rollout_tape_1x4, 1, 0) break;
-    }
+    const int rw = variant == 0 || variant == 1 ? 4 : 1;
+    const FusedArgs A = trace_checked(A_in, grid, rw + 1);
+    const bool gated = A.gate_ready != nullptr, fast = (rw * 64) % A.n_veh == 0;
+    if (variant == 0 && !gated && !fast) return hipErrorInvalidValue;   // the host routes these to the 4 x 4 tile (tape_tile_variant)
+    const dim3 g(grid), b((rw + 1 + (gated ? 2 : 0)) * 64);
+    const size_t dyn = (size_t)A.stage_entries * 12;
+    with_task(task, [&](auto t) { with_bool(A.storage_f16, [&](auto f16) { with_bool(fast, [&](auto fast_c) {
+        using ST = std::conditional_t<f16, _Float16, float>;
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, g, b, dyn, s, reinterpret_cast<const ST*>(A.obs_in), reinterpret_cast<ST*>(A.obs_out), A.n_env,
+                               A.obs_dim, A.n_veh, A.envs_per_tile, A.nv_magic, horizon, A);
+        };
+        if (gated && variant == 0) go(rollout_gated_4x8<t, fast_c, ST>);
+        else if (gated && variant == 1) go(rollout_gated_4x4<t, fast_c, ST>);
+        else if (gated) go(rollout_gated_1x4<t, fast_c, ST>);
+        else if (variant == 0) go(rollout_tape_4x8<t, true, ST>);   // (FAST only, see above)
+        else if (variant == 1) go(rollout_tape_4x4<t, fast_c, ST>);
+        else go(rollout_tape_1x4<t, fast_c, ST>);
+    }); }); });
     return hipGetLastError();
 }
 
 hipError_t launch_rollout_fused(int task, int variant, const FusedArgs& A_in, int grid, hipStream_t s) {
-    const FusedArgs A = trace_checked(A_in, grid, (variant == 2 ? 1 : 4) + 1);
-    // (A.rolling / A.by_progress: decided by the grid and the tile's envs — eb_capi.hip:rollout_fused — or forced,
+    const int rw = variant == 0 || variant == 1 ? 4 : 1;
+    const FusedArgs A = trace_checked(A_in, grid, rw + 1);
+    const dim3 g(grid), b((rw + 1) * 64);
+    const int hot = (A.do_rewards ? HOT_REWARDS : 0) | (A.by_progress ? HOT_PRIO : 0);
+    const unsigned char* turn_tab = reinterpret_cast<const unsigned char*>(A.dt) + offsetof(PathTables, turn);
+    // (A.rolling / A.by_progress: decided by the grid and the tile's envs — eb_capi.hip:rollout — or forced,
     // eb_debug_set_rollout_sched; every combination computes the same bits.  Rolling loads exist for the 2048-record tile only:
     // four records per lane leave little to roll, and the 256-record tile runs on grids that are launch-bound either way)
-    switch (variant) {
-        case 0: if (A.rolling) EB_LAUNCH(rollout_fused_4x8, 4, 3) else EB_LAUNCH(rollout_fused_4x8, 4, 8) break;
-        case 1: EB_LAUNCH(rollout_fused_4x4, 4, 4) break;
-        default: EB_LAUNCH(rollout_fused_1x4, 1, 4) break;
-    }
+    with_task(task, [&](auto t) { with_bool(A.storage_f16, [&](auto f16) { with_bool((rw * 64) % A.n_veh == 0, [&](auto fast) {
+        using ST = std::conditional_t<f16, _Float16, float>;
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, g, b, 0, s, reinterpret_cast<const ST*>(A.obs_in), reinterpret_cast<ST*>(A.obs_out), A.n_env,
+                               A.obs_dim, A.n_veh, A.envs_per_tile, A.nv_magic, hot, A.acc_rec, turn_tab, A);
+        };
+        if (variant == 0 && A.rolling) go(rollout_fused_4x8<t, fast, 3, ST>);
+        else if (variant == 0) go(rollout_fused_4x8<t, fast, 8, ST>);
+        else if (variant == 1) go(rollout_fused_4x4<t, fast, 4, ST>);
+        else go(rollout_fused_1x4<t, fast, 4, ST>);
+    }); }); });
     return hipGetLastError();
 }
 

@@ -11,10 +11,12 @@ export TMPDIR=/tmp
 # the hash of the kernel sources these passes measure, stamped HERE, at measurement time (pmc_traffic.py carries it into the JSON;
 # bench.py refuses the bytes of other code)
 python -c "import json; from env_build_amd import build as b; json.dump({k: b.kernel_hash(k) for k in b.KERNEL_SOURCES}, open('$OUT/kernel_hash.json', 'w'))"
+# every pass under a time limit of its own; the first pass that fails, faults or runs out of time ends the script
+run() { local t=$1 name=$2; shift 2; timeout -k 10 $t "$@" > $OUT/$name.log 2>&1 || { echo "$name failed (exit $?): $OUT/$name.log"; exit 1; }; }
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/bench_$c -o p -- python bench.py --steps 50 --warmup 25 --no-cpu-baseline --no-side > $OUT/bench_$c.log 2>&1
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/copy_$c -o p -- scripts/micro/copybench calib > $OUT/copy_$c.log 2>&1
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/envstep_$c -o p -- python bench.py --env-step > $OUT/envstep_$c.log 2>&1
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/f16_$c -o p -- python scripts/time_rollout.py --n-veh 64 --f16 --iters 60 > $OUT/f16_$c.log 2>&1
+  run 900 bench_$c rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/bench_$c -o p -- python bench.py --steps 50 --warmup 25 --no-cpu-baseline --no-side
+  run 300 copy_$c rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/copy_$c -o p -- scripts/micro/copybench calib
+  run 600 envstep_$c rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/envstep_$c -o p -- python bench.py --env-step
+  run 600 f16_$c rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/f16_$c -o p -- python scripts/time_rollout.py --n-veh 64 --f16 --iters 60
 done
 python scripts/pmc_traffic.py $OUT | tee $OUT/pmc_traffic.txt

@@ -89,7 +89,7 @@ def test_every_tile_shape_computes_the_same_bits(task, N, tile):
 def test_every_launch_schedule_computes_the_same_bits(task, N, B, rolling, by_progress):
     """Round 6: the 2048-record tile's two scheduling choices — every record load up front or three in flight per lane with the next
     one requested as a record is done; the hardware's oldest-first issue or a priority that falls as a wave advances — are picked by the
-    grid's size (eb_capi.hip:rollout_fused) and change WHEN things happen, never what is computed: each combination forced on ragged
+    grid's size (eb_capi.hip:rollout_sched) and change WHEN things happen, never what is computed: each combination forced on ragged
     batches (slot counts that do and do not divide the record lanes, more than one block per CU at 8 200 envs), against the oracle."""
     H = 4
     host, dev = _pair(task, n_veh=N)
