@@ -134,6 +134,15 @@ PROTOTYPES = {
     'eb_shield_is_safe': (C.c_int, [_P, _P, _I, _P, _P, _I, _I, _I, C.c_float, _P, _P, _P, _P, _P, _P, _P]),
 }
 
+# include/envbuild_grad.h: the reverse pass of the rollout step.  A table of its own, bound on first use and only where the library
+# exports the symbols (the HIP library does; the CPU oracle and a library built before the reverse pass existed do not).
+EB_GRAD_ABI_VERSION = 1
+GRAD_PROTOTYPES = {
+    'eb_grad_abi_version': (C.c_int, []),
+    'eb_rollout_step_vjp': (C.c_int, [_P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P]),
+    'eb_rollout_chain_vjp': (C.c_int, [_P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
+}
+
 
 class EbError(RuntimeError):
     pass
@@ -153,6 +162,25 @@ class CApi(object):
             raise EbError('%s: ABI version %d, expected %d'
                           % (path, self.lib.eb_abi_version(), EB_ABI_VERSION))
         self.backend = self.lib.eb_backend().decode()
+
+    def grad_fn(self, symbol):
+        """The raw ctypes function of one include/envbuild_grad.h entry, bound on first use; EbError when this library has no
+        reverse pass."""
+        fns = self.__dict__.setdefault('_grad_fns', {})
+        if not fns:
+            missing = [n for n in GRAD_PROTOTYPES if not hasattr(self.lib, n)]
+            if missing:
+                raise EbError('%s (backend %r) does not export %s: this library has no reverse pass (include/envbuild_grad.h is '
+                              'implemented by the HIP library only; rebuild an older one)' % (self.path, self.backend, ', '.join(missing)))
+            for n, (res, args) in GRAD_PROTOTYPES.items():
+                fn = getattr(self.lib, n)
+                fn.restype, fn.argtypes = res, args
+                fns[n] = fn
+            if fns['eb_grad_abi_version']() != EB_GRAD_ABI_VERSION:
+                v = fns['eb_grad_abi_version']()
+                fns.clear()
+                raise EbError('%s: gradient ABI version %d, expected %d' % (self.path, v, EB_GRAD_ABI_VERSION))
+        return fns[symbol]
 
     def check(self, rc):
         if rc != 0:
@@ -199,7 +227,7 @@ class CApi(object):
 
     def __getattr__(self, name):
         # eb_xxx(...) with return-code checking: api.rollout_step(h, ...)
-        fn = getattr(self.lib, 'eb_' + name)
+        fn = self.grad_fn('eb_' + name) if 'eb_' + name in GRAD_PROTOTYPES else getattr(self.lib, 'eb_' + name)
 
         def call(*args):
             self.check(fn(*args))

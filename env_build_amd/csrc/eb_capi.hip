@@ -17,6 +17,8 @@
 #include <vector>
 
 #include "../../include/envbuild.h"
+#include "../../include/envbuild_grad.h"
+#include "eb_grad.h"
 #include "eb_kernels.h"
 
 namespace {
@@ -1730,6 +1732,70 @@ int eb_shield_is_safe(eb_handle h, eb_mlp policy, int32_t n_env, const float* ob
         rc = rollout(h, n_env, r, s);
         if (rc) return rc;
         cur = dst;
+    }
+    return EB_OK;
+}
+
+}  // extern "C"
+
+// ---- include/envbuild_grad.h: the reverse pass of the rollout step (eb_rollout_vjp.hip) ----
+static int step_vjp(eb_handle h, int32_t n_env, const float* obs_in, const float* actions, const int32_t* ref_idx, int32_t path_id,
+                    const float* g_obs_out, int32_t ld_out, const float* g_out5, float* g_obs_in, int32_t ld_in, float* g_actions,
+                    hipStream_t s) {
+    eb::VjpArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.obs = obs_in; A.actions = actions; A.ref_idx = ref_idx; A.g_obs_out = g_obs_out; A.g_out5 = g_out5;
+    A.g_obs_in = g_obs_in; A.g_actions = g_actions;
+    A.n_env = n_env; A.obs_dim = obs_dim(h->cfg); A.n_veh = h->cfg.n_veh; A.n_future = h->cfg.n_future;
+    A.nd = A.obs_dim - 4 * A.n_veh;
+    A.ld_out = ld_out; A.ld_in = ld_in;
+    A.path_id = path_id; A.training = h->cfg.mode == EB_MODE_TRAINING; A.n_paths = h->pt.n_paths;
+    EB_HIP(eb::launch_rollout_step_vjp(h->cfg.task, A, s));
+    return EB_OK;
+}
+
+extern "C" {
+
+int eb_grad_abi_version(void) { return EB_GRAD_ABI_VERSION; }
+
+int eb_rollout_step_vjp(eb_handle h, int32_t n_env, const float* obs_in, const float* actions, const int32_t* ref_idx,
+                        int32_t path_id, const float* g_obs_out, int32_t ld_out, const float* g_out5, float* g_obs_in,
+                        int32_t ld_in, float* g_actions, void* stream) {
+    if (h && n_env == 0) return EB_OK;
+    int rc = check_rollout(h, n_env, ref_idx, path_id, "eb_rollout_step_vjp: null handle");
+    if (rc) return rc;
+    const int D = obs_dim(h->cfg), nd = D - 4 * h->cfg.n_veh;
+    if (n_env < 0 || !obs_in || !actions || !g_obs_in || !g_actions) return fail(EB_EINVAL, "eb_rollout_step_vjp: bad argument");
+    if (g_obs_out && ld_out < nd) return fail(EB_EINVAL, "eb_rollout_step_vjp: ld_out must be at least nd = 6 + 3 * (n_future + 1)");
+    if (ld_in != nd && ld_in != D) return fail(EB_EINVAL, "eb_rollout_step_vjp: ld_in must be nd (compact rows) or obs_dim (full rows)");
+    if (g_obs_in == g_obs_out) return fail(EB_EINVAL, "eb_rollout_step_vjp: in-place update is not supported");
+    EB_HIP(hipSetDevice(h->cfg.device));
+    return step_vjp(h, n_env, obs_in, actions, ref_idx, path_id, g_obs_out, ld_out, g_out5, g_obs_in, ld_in, g_actions, (hipStream_t)stream);
+}
+
+int eb_rollout_chain_vjp(eb_handle h, int32_t n_env, int32_t horizon, const float* obs_steps, const float* action_tape,
+                         const int32_t* ref_idx, int32_t path_id, const float* g_obs_final, int32_t ld_final,
+                         const float* g_out5_steps, float* g_work, float* g_obs0, float* g_action_tape, void* stream) {
+    if (h && n_env == 0) return EB_OK;
+    int rc = check_rollout(h, n_env, ref_idx, path_id, "eb_rollout_chain_vjp: null handle");
+    if (rc) return rc;
+    const int D = obs_dim(h->cfg), nd = D - 4 * h->cfg.n_veh;
+    if (n_env < 0 || horizon < 1 || !obs_steps || !action_tape || !g_work || !g_obs0 || !g_action_tape || g_work == g_obs0)
+        return fail(EB_EINVAL, "eb_rollout_chain_vjp: bad argument");
+    if (g_obs_final && ld_final < nd) return fail(EB_EINVAL, "eb_rollout_chain_vjp: ld_final must be at least nd = 6 + 3 * (n_future + 1)");
+    if (g_obs_final == g_work || g_obs_final == g_obs0) return fail(EB_EINVAL, "eb_rollout_chain_vjp: g_obs_final must not alias g_work / g_obs0");
+    EB_HIP(hipSetDevice(h->cfg.device));
+    const size_t n = (size_t)n_env;
+    // last step first; step t writes g_obs0 when t is even, g_work when odd: step 0 lands in g_obs0
+    const float* g_next = g_obs_final;
+    int ld_next = ld_final;
+    for (int t = horizon - 1; t >= 0; --t) {
+        float* dst = (t & 1) ? g_work : g_obs0;
+        rc = step_vjp(h, n_env, obs_steps + (size_t)t * n * D, action_tape + (size_t)t * n * 2, ref_idx, path_id, g_next, ld_next,
+                      g_out5_steps ? g_out5_steps + (size_t)t * 5 * n : nullptr, dst, nd, g_action_tape + (size_t)t * n * 2,
+                      (hipStream_t)stream);
+        if (rc) return rc;
+        g_next = dst; ld_next = nd;
     }
     return EB_OK;
 }

@@ -1,0 +1,147 @@
+"""CPU (-m "not gpu"): the gradient ABI (include/envbuild_grad.h) is bound and exported, a library without it is refused cleanly,
+the gradient fixtures are self-consistent, the reverse pass's arithmetic (csrc/eb_grad_device.h, run on the host) meets them, and —
+where the reference tree is present — the generator reproduces them."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from env_build_amd import _capi, build as eb_build
+from tests._helpers import ROOT, golden, oracle_lib, _p
+from tests._grad_cases import TASKS, MAX_EXCLUDED, cases, check_columns
+
+HEADER = os.path.join(ROOT, 'include', 'envbuild_grad.h')
+
+
+def header_symbols():
+    src = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
+    return sorted(set(re.findall(r'\b(eb_[a-z0-9_]+)\s*\(', src)))
+
+
+def test_grad_header_declares_what_ctypes_binds():
+    assert sorted(_capi.GRAD_PROTOTYPES) == header_symbols()
+    assert not set(_capi.GRAD_PROTOTYPES) & set(_capi.PROTOTYPES)          # a table of its own: envbuild.h's set is the oracle's too
+    assert _capi.EB_ABI_VERSION == 5
+    src = open(HEADER).read()
+    assert int(re.search(r'#define EB_GRAD_ABI_VERSION (\d+)', src).group(1)) == _capi.EB_GRAD_ABI_VERSION
+
+
+def test_hip_library_exports_the_gradient_entries_and_a_gfx950_vjp_kernel():
+    lib_path = eb_build.build()            # hipcc --offload-arch=gfx950 (cross-compiles without a GPU)
+    import torch  # noqa: F401  (binds the HIP runtime torch ships before ours, as the product does)
+    lib = C.CDLL(lib_path)
+    for name in _capi.GRAD_PROTOTYPES:
+        assert hasattr(lib, name), name
+    assert lib.eb_grad_abi_version() == _capi.EB_GRAD_ABI_VERSION
+    blob = open(lib_path, 'rb').read()
+    assert b'gfx950' in blob and b'rollout_step_vjp_kernel' in blob
+    assert 'eb_rollout_vjp.hip' in eb_build.SOURCES
+    # the forward kernels' hash (profiles/ ties HBM-traffic records to it) does not see the reverse pass
+    assert 'eb_rollout_vjp.hip' not in eb_build.KERNEL_SOURCES['rollout']
+
+
+def test_a_library_without_the_reverse_pass_is_refused_cleanly():
+    api = oracle_lib()                     # CApi binds every PROTOTYPES entry on it, as before
+    assert api.backend == 'oracle'
+    for name in ('rollout_step_vjp', 'rollout_chain_vjp', 'grad_abi_version'):
+        with pytest.raises(_capi.EbError) as e:
+            getattr(api, name)
+        assert 'reverse pass' in str(e.value)
+    with pytest.raises(_capi.EbError):
+        api.grad_fn('eb_rollout_step_vjp')
+
+
+def test_differentiable_model_refuses_fp16_state():
+    from env_build_amd.grad import DifferentiableEnvironmentModel
+    with pytest.raises(_capi.EbError) as e:
+        DifferentiableEnvironmentModel('left', state_dtype='float16')
+    assert 'float16' in str(e.value) and 'reverse pass' in str(e.value)
+
+
+@pytest.mark.parametrize('task', TASKS)
+def test_gradient_fixtures_are_self_consistent(task):
+    for kind in ('g15_grad_step', 'g16_grad_chain'):
+        path = os.path.join(ROOT, 'tests', 'golden', '%s_%s.npz' % (kind, task))
+        assert os.path.getsize(path) <= 591861            # the largest fixture before these (g13_policy_left_2x256_elu.npz)
+        cs = cases(kind, task)
+        rows = sum(len(c['ok']) for c in cs)
+        excluded = sum(int((~c['ok']).sum()) for c in cs)
+        assert excluded <= MAX_EXCLUDED * rows, '%s %s: %d of %d rows excluded' % (kind, task, excluded, rows)
+        assert {c.mode for c in cs} == {'training', 'selecting'} and {c.n_future for c in cs} == {0, 2}
+        assert any(c.n_veh == 32 for c in cs)
+        for c in cs:
+            ok = c['ok']
+            assert float(c['veh_grad_max']) == 0.0                        # stop_gradient: exactly zero in both precisions
+            for g64, g32, E in ((c['g_obs64'], c['g_obs32'], c['E_obs']), (c['g_act64'], c['g_act32'], c['E_act'])):
+                assert g64.dtype == np.float64 and g32.dtype == np.float32 and np.isfinite(g64).all()
+                d = np.abs(g32.astype(np.float64) - g64)
+                d = np.moveaxis(d, 0, 1).reshape(len(ok), -1, len(E)) if d.ndim == 3 else d.reshape(len(ok), 1, len(E))
+                assert np.array_equal(d[ok].max((0, 1)), E)
+            assert c['g_obs64'].shape == (len(ok), c.nd)
+    assert any(c.n_veh == 64 for t in TASKS for c in cases('g15_grad_step', t))
+
+
+@pytest.mark.parametrize('task', TASKS)
+def test_fixture_forward_equals_the_rollout_fixtures(task):
+    """The float32 run of the torch stand-in computes what the NumPy stand-in of the g5 fixtures computed: from the same state
+    the rewards are the same bits; the penalty sums (sin / cos / sqrt of another libm) and the states of a chain agree to the
+    tolerance every reference-generated fixture is held to here (rtol 1e-5 next to atol 5e-6, tests/test_gpu_parity.py)."""
+    def near(a, b):
+        return (np.abs(a.astype(np.float64) - b) <= 5e-6 + 1e-5 * np.abs(b)).all()
+    n = 0
+    for c in cases('g15_grad_step', task):
+        steps = c.meta['g5_steps']
+        if steps is None:
+            continue
+        z = golden('g5_rollout_%s_N%d_%s_nf%d' % (task, c.n_veh, c.mode, c.n_future))
+        want = np.concatenate([z['out5'][t] for t in steps], 1)
+        assert np.array_equal(c['out5_f32'][0], want[0]), c.name
+        assert near(c['out5_f32'], want), c.name
+        assert steps[0] != 0 or np.array_equal(c['obs'][:32], z['obs0'])
+        n += 1
+    for c in cases('g16_grad_chain', task):
+        z = golden('g5_rollout_%s_N%d_%s_nf%d' % (task, c.n_veh, c.mode, c.n_future))
+        assert np.array_equal(c['out5_f32'][0, 0], z['out5'][0, 0]), c.name
+        assert near(c['out5_f32'], z['out5'][:c.meta['horizon']]), c.name
+        assert np.array_equal(c['obs0'], z['obs0']) and np.array_equal(c['tape'], z['actions'][:c.meta['horizon']])
+        n += 1
+    assert n >= 8
+
+
+@pytest.fixture(scope='module')
+def host_harness(tmp_path_factory):
+    """tests/_grad_host_harness.hip: the kernel's __host__ __device__ arithmetic compiled for the host"""
+    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+    out = str(tmp_path_factory.mktemp('grad_host') / 'libgrad_host.so')
+    subprocess.check_call([hipcc, '--offload-arch=gfx950', '-O2', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared',
+                           '-I', eb_build.CSRC, os.path.join(ROOT, 'tests', '_grad_host_harness.hip'), '-o', out])
+    return C.CDLL(out)
+
+
+@pytest.mark.parametrize('task', TASKS)
+def test_reverse_pass_arithmetic_on_the_host_meets_the_step_fixtures(task, host_harness):
+    for c in cases('g15_grad_step', task):
+        obs, act = np.ascontiguousarray(c['obs']), np.ascontiguousarray(c['actions'])
+        n, D = obs.shape
+        ri = c['ref_idx']
+        has_path = np.ascontiguousarray(((ri >= 0) & (ri < 3)) if c.mode == 'training' else np.ones(n, bool), dtype=np.int32)
+        g, g5 = np.ascontiguousarray(c['g_obs_out']), np.ascontiguousarray(c['g_out5'])
+        go, ga = np.full((n, c.nd), np.nan, np.float32), np.full((n, 2), np.nan, np.float32)
+        host_harness.host_step_vjp(_capi.TASK_ID[task], n, D, c.nd, c.n_veh, c.n_future, _p(obs), _p(act), _p(has_path), _p(g), _p(g5),
+                                   _p(go), _p(ga))
+        check_columns(go, c['g_obs64'], c['E_obs'], c['ok'], 'host %s %s obs' % (task, c.name))
+        check_columns(ga, c['g_act64'], c['E_act'], c['ok'], 'host %s %s act' % (task, c.name))
+
+
+def test_generator_reproduces_the_committed_fixtures():
+    from oracle import refload
+    if not refload.available():
+        pytest.skip('reference tree not present (build container only)')
+    # a process of its own: the torch stand-in has to be THE tensorflow module before the reference is imported
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'scripts', 'gen_golden_grad.py'), '--check'], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert r.stdout.count('reproduced') == 6
