@@ -136,11 +136,15 @@ PROTOTYPES = {
 
 # include/envbuild_grad.h: the reverse pass of the rollout step.  A table of its own, bound on first use and only where the library
 # exports the symbols (the HIP library does; the CPU oracle and a library built before the reverse pass existed do not).
-EB_GRAD_ABI_VERSION = 1
+EB_GRAD_ABI_VERSION = 2
 GRAD_PROTOTYPES = {
     'eb_grad_abi_version': (C.c_int, []),
     'eb_rollout_step_vjp': (C.c_int, [_P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P]),
     'eb_rollout_chain_vjp': (C.c_int, [_P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
+    # (h, n_env, horizon, obs0, tape, ref_idx, path_id, g_obs_final, ld_final, g_out5_steps, w5 (host), out5_steps, obs_out, g_obs0,
+    #  g_action_tape, stream)
+    'eb_rollout_tape_vjp': (C.c_int, [_P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    'eb_rollout_tape_vjp_max_horizon': (C.c_int, [_P, C.POINTER(C.c_int32)]),
 }
 
 

@@ -1800,4 +1800,51 @@ int eb_rollout_chain_vjp(eb_handle h, int32_t n_env, int32_t horizon, const floa
     return EB_OK;
 }
 
+int eb_rollout_tape_vjp_max_horizon(eb_handle h, int32_t* max_horizon) {
+    if (!h || !max_horizon) return fail(EB_EINVAL, "eb_rollout_tape_vjp_max_horizon: bad argument");
+    *max_horizon = eb::rollout_tape_vjp_max_horizon(h->cfg.n_veh);
+    return EB_OK;
+}
+
+int eb_rollout_tape_vjp(eb_handle h, int32_t n_env, int32_t horizon, const float* obs0, const float* action_tape,
+                        const int32_t* ref_idx, int32_t path_id, const float* g_obs_final, int32_t ld_final,
+                        const float* g_out5_steps, const float* w5, float* out5_steps, float* obs_out, float* g_obs0,
+                        float* g_action_tape, void* stream) {
+    if (h && n_env == 0) return EB_OK;
+    int rc = check_rollout(h, n_env, ref_idx, path_id, "eb_rollout_tape_vjp: null handle");
+    if (rc) return rc;
+    const int D = obs_dim(h->cfg), nd = D - 4 * h->cfg.n_veh;
+    if (n_env < 0 || horizon < 1 || !obs0 || !action_tape) return fail(EB_EINVAL, "eb_rollout_tape_vjp: bad argument");
+    const int limit = eb::rollout_tape_vjp_max_horizon(h->cfg.n_veh);
+    if (horizon > limit) {
+        char msg[256];
+        std::snprintf(msg, sizeof msg, "eb_rollout_tape_vjp: horizon %d exceeds the kernel's limit of %d steps for %d vehicle slots "
+                                       "(eb_rollout_tape_vjp_max_horizon)", (int)horizon, limit, (int)h->cfg.n_veh);
+        return fail(EB_EINVAL, msg);
+    }
+    if (g_obs_final && ld_final < nd) return fail(EB_EINVAL, "eb_rollout_tape_vjp: ld_final must be at least nd = 6 + 3 * (n_future + 1)");
+    if (obs_out && obs_out == obs0) return fail(EB_EINVAL, "eb_rollout_tape_vjp: obs_out must not alias obs0");
+    if (g_obs0 && g_obs0 == g_obs_final) return fail(EB_EINVAL, "eb_rollout_tape_vjp: g_obs0 must not alias g_obs_final");
+    if (!out5_steps && !obs_out && !g_obs0 && !g_action_tape) return EB_OK;      // nothing asked for
+    EB_HIP(hipSetDevice(h->cfg.device));
+    eb::TapeVjpArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.obs0 = obs0; A.tape = action_tape; A.ref_idx = ref_idx; A.g_obs_final = g_obs_final; A.g_out5_steps = g_out5_steps;
+    for (int k = 0; k < 5; ++k) A.w5[k] = w5 ? w5[k] : 0.0f;
+    A.out5_steps = out5_steps; A.obs_out = obs_out; A.g_obs0 = g_obs0; A.g_action_tape = g_action_tape;
+    A.dt = h->d_pt;
+    A.xy10 = reinterpret_cast<const float*>(h->d_red_all);
+    A.phi10 = h->d_phi10_all;
+    A.rad_all = h->d_rad_all;
+    A.cells = h->d_cells;
+    A.gx0 = h->pt.gx0; A.gy0 = h->pt.gy0; A.gnx = h->pt.gnx; A.gny = h->pt.gny;
+    for (int k = 0; k < 3; ++k) { A.red_off[k] = h->red_off[k]; A.red_len[k] = h->pt.red_len[k]; }
+    A.n_paths = h->pt.n_paths;
+    A.n_env = n_env; A.obs_dim = D; A.nd = nd; A.n_veh = h->cfg.n_veh; A.n_future = h->cfg.n_future;
+    A.horizon = horizon; A.ld_final = ld_final;
+    A.path_id = path_id; A.training = h->cfg.mode == EB_MODE_TRAINING;
+    EB_HIP(eb::launch_rollout_tape_vjp(h->cfg.task, A, h->n_cu, (hipStream_t)stream));
+    return EB_OK;
+}
+
 }  // extern "C"

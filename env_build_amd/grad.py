@@ -15,13 +15,16 @@ forward of one step is the eb_rollout_step launch EnvironmentModel uses, and its
 The gradient contract is the header's: obs[:, :nd] and the raw actions receive a gradient, the vehicle columns exactly zero; clipped
 actions (beyond +-1.05) and a clipped v_x get zero; the closest path point is a constant.  fp32 state only: there is no reverse
 pass for state_dtype='float16'.  No CPU path and no fall-back to eager PyTorch: without the HIP library's reverse pass this raises.
+
+An open-loop rollout over a whole action tape — an MPC cost — is the free function rollout_tape(model, obses, action_tape): forward one
+eb_rollout_tape launch, backward one eb_rollout_tape_vjp launch (csrc/eb_rollout_tape_vjp.hip).
 """
 import torch
 
 from . import _capi
 from .dynamics_and_models import EnvironmentModel, DevArray, _dev, _stream, _unwrap
 
-__all__ = ['DifferentiableEnvironmentModel', 'rollout_step']
+__all__ = ['DifferentiableEnvironmentModel', 'rollout_step', 'rollout_tape', 'tape_vjp_max_horizon']
 
 
 class _RolloutStep(torch.autograd.Function):
@@ -83,6 +86,121 @@ def rollout_step(model, obses, actions):
     return nxt, out5
 
 
+class _RolloutTape(torch.autograd.Function):
+    """(obs [B, D], raw tape [H, B, 2]) -> (final obs [B, D], out5 [H, 5, B]): forward one eb_rollout_tape launch, backward one
+    eb_rollout_tape_vjp launch that recomputes from obs and the tape (nothing else is saved)."""
+
+    @staticmethod
+    def forward(ctx, obs, tape, model, ref_idx, path_id):
+        H, B = tape.shape[0], obs.shape[0]
+        work, out = torch.empty_like(obs), torch.empty_like(obs)
+        out5 = torch.empty((H, 5, B), dtype=torch.float32, device=obs.device)
+        rc = model.api.lib.eb_rollout_tape(model.handle, B, H, obs.data_ptr(), tape.data_ptr(),
+                                           None if ref_idx is None else ref_idx.data_ptr(), path_id, work.data_ptr(), out.data_ptr(),
+                                           out5.data_ptr(), _stream(model.device))
+        if rc != 0:
+            model.api.check(rc)
+        ctx.save_for_backward(obs, tape)
+        ctx.model, ctx.ref_idx, ctx.path_id = model, ref_idx, path_id
+        ctx.set_materialize_grads(False)
+        return out, out5
+
+    @staticmethod
+    def backward(ctx, g_final, g_out5):
+        obs, tape = ctx.saved_tensors
+        model = ctx.model
+        H, (B, D) = tape.shape[0], obs.shape
+        nd = D - 4 * model.veh_num
+        if g_final is not None:
+            g_final = g_final.contiguous()
+        if g_out5 is not None:
+            g_out5 = g_out5.contiguous()
+        g_obs = torch.zeros_like(obs)             # the vehicle columns stay exact zeros (stop_gradient)
+        g_head = torch.empty((B, nd), dtype=torch.float32, device=obs.device)
+        g_tape = torch.empty_like(tape)
+        rc = model.api.grad_fn('eb_rollout_tape_vjp')(
+            model.handle, B, H, obs.data_ptr(), tape.data_ptr(), None if ctx.ref_idx is None else ctx.ref_idx.data_ptr(), ctx.path_id,
+            None if g_final is None else g_final.data_ptr(), D, None if g_out5 is None else g_out5.data_ptr(), None, None, None,
+            g_head.data_ptr(), g_tape.data_ptr(), _stream(model.device))
+        if rc != 0:
+            model.api.check(rc)
+        g_obs[:, :nd] = g_head
+        return g_obs, g_tape, None, None, None
+
+
+class _RolloutTapeComposed(torch.autograd.Function):
+    """The same pair for a horizon beyond eb_rollout_tape_vjp_max_horizon: H eb_rollout_step launches that keep every pre-step
+    obs, and eb_rollout_chain_vjp (H reverse launches) backwards."""
+
+    @staticmethod
+    def forward(ctx, obs, tape, model, ref_idx, path_id):
+        H, (B, D) = tape.shape[0], obs.shape
+        steps = torch.empty((H + 1, B, D), dtype=torch.float32, device=obs.device)
+        steps[0] = obs
+        out5 = torch.empty((H, 5, B), dtype=torch.float32, device=obs.device)
+        scaled = torch.empty((B, 2), dtype=torch.float32, device=obs.device)
+        for t in range(H):
+            rc = model.api.lib.eb_rollout_step(model.handle, B, steps[t].data_ptr(), tape[t].data_ptr(),
+                                               None if ref_idx is None else ref_idx.data_ptr(), path_id, steps[t + 1].data_ptr(),
+                                               out5[t].data_ptr(), scaled.data_ptr(), _stream(model.device))
+            if rc != 0:
+                model.api.check(rc)
+        ctx.save_for_backward(steps, tape)
+        ctx.model, ctx.ref_idx, ctx.path_id = model, ref_idx, path_id
+        ctx.set_materialize_grads(False)
+        return steps[H].clone(), out5
+
+    @staticmethod
+    def backward(ctx, g_final, g_out5):
+        steps, tape = ctx.saved_tensors
+        model = ctx.model
+        H, B, D = tape.shape[0], steps.shape[1], steps.shape[2]
+        nd = D - 4 * model.veh_num
+        if g_final is not None:
+            g_final = g_final.contiguous()
+        if g_out5 is not None:
+            g_out5 = g_out5.contiguous()
+        g_obs = torch.zeros((B, D), dtype=torch.float32, device=steps.device)
+        work, g_head = (torch.empty((B, nd), dtype=torch.float32, device=steps.device) for _ in range(2))
+        g_tape = torch.empty_like(tape)
+        rc = model.api.grad_fn('eb_rollout_chain_vjp')(
+            model.handle, B, H, steps.data_ptr(), tape.data_ptr(), None if ctx.ref_idx is None else ctx.ref_idx.data_ptr(), ctx.path_id,
+            None if g_final is None else g_final.data_ptr(), D, None if g_out5 is None else g_out5.data_ptr(), work.data_ptr(),
+            g_head.data_ptr(), g_tape.data_ptr(), _stream(model.device))
+        if rc != 0:
+            model.api.check(rc)
+        g_obs[:, :nd] = g_head
+        return g_obs, g_tape, None, None, None
+
+
+def tape_vjp_max_horizon(model):
+    """the longest tape eb_rollout_tape_vjp takes for `model` (its slot count decides)"""
+    import ctypes
+    limit = ctypes.c_int32(0)
+    model.api.check(model.api.grad_fn('eb_rollout_tape_vjp_max_horizon')(model.handle, ctypes.byref(limit)))
+    return limit.value
+
+
+def rollout_tape(model, obses, action_tape):
+    """A differentiable open-loop rollout at an explicit state: -> (final obses [B, D], out5_steps [H, 5, B]) on the autograd graph.
+    Forward is one eb_rollout_tape launch, backward one eb_rollout_tape_vjp launch that recomputes from `obses` and the tape;
+    obses[:, :nd] and the tape receive gradients, the vehicle columns exact zeros.  `model` (an EnvironmentModel with fp32 state)
+    supplies the task, the slot modes and the path choice; its own state is not touched.  A tape longer than
+    tape_vjp_max_horizon(model) falls back to H step launches that keep every pre-step obs plus eb_rollout_chain_vjp — the same
+    bits, 2 H launches."""
+    if model.state_dtype != torch.float32:
+        raise _capi.EbError('grad.rollout_tape: fp32 state only (the fp16-state kernels have no reverse pass)')
+    obs = _graph_tensor(obses, model.device, 'obses')
+    if obs.dim() != 2 or obs.shape[1] != model.obs_dim:
+        raise ValueError('obses must be [B, %d]; got %s' % (model.obs_dim, tuple(obs.shape)))
+    tape = _graph_tensor(action_tape, model.device, 'action_tape')
+    if tape.dim() != 3 or tape.shape[1] != obs.shape[0] or tape.shape[2] != 2 or tape.shape[0] < 1:
+        raise ValueError('action_tape must be [H, %d, 2]; got %s' % (obs.shape[0], tuple(tape.shape)))
+    ri, pid = model._path_args()
+    fn = _RolloutTape if tape.shape[0] <= tape_vjp_max_horizon(model) else _RolloutTapeComposed
+    return fn.apply(obs, tape, model, ri, pid)
+
+
 class DifferentiableEnvironmentModel(EnvironmentModel):
     """EnvironmentModel (DAM:90-427) whose reset / add_traj / rollout_out take and return torch.Tensors on the autograd graph.
     `obses` is full width [B, D]; the vehicle columns of its gradient are zero.  Everything else is inherited unchanged."""
@@ -126,4 +244,4 @@ class DifferentiableEnvironmentModel(EnvironmentModel):
 
     def rollout_tape(self, action_tape):
         raise _capi.EbError('DifferentiableEnvironmentModel.rollout_tape: the open-loop tape kernel has no reverse pass; loop over '
-                            'rollout_out, or use EnvironmentModel for a forward-only rollout')
+                            'rollout_out, or use EnvironmentModel for a forward-only rollout')   # (differentiable: grad.rollout_tape)

@@ -1,0 +1,171 @@
+"""Batched, box-constrained open-loop MPC on the model's own cost: OpenLoopMPC.
+
+The reference's mpc/main.py:537-576 solves, for ONE ego at a time, min_u J(u) over 25 x 2 raw actions in [-1, 1] with SciPy's SLSQP
+and finite differences.  Here every env of a batch is solved at once, with the analytic gradient: one evaluation of the cost and its
+gradient for the whole batch is ONE launch of eb_rollout_tape_vjp (include/envbuild_grad.h, csrc/eb_rollout_tape_vjp.hip).
+
+Cost.   J(u) = sum_t  w . out5_t(u)      out5 = (rewards, punish_term_for_training, real_punish_term, veh2veh4real, veh2road4real)
+with w = (-1, lambda, 0, 0, 0) and lambda = 10 by default: the ADP loss of examples/adp_policy_gradient.py, per env and not averaged.
+(mpc/main.py carries a private cost of its own; this project's model is EnvironmentModel.rollout_out, so its outputs are the cost.)
+
+Method. Projected gradient on the box [-1, 1]^(H x 2) (mpc/main.py:549), every env with a step length of its own: a Barzilai-Borwein
+proposal, Armijo backtracking on the projected step  u+ = clip(u - a g),  J(u+) <= J(u) + c1 <g, u+ - u>.  An env whose trials are
+all rejected keeps its iterate (a `where`, not a host loop) and starts the next iteration from the shortened step.  A line-search
+trial is a value-only launch (g_action_tape = NULL); the update is a handful of elementwise torch ops on [H, B, 2]; nothing inside
+an iteration synchronises with the host, except the optional convergence read every `check_every` iterations.
+Launches per iteration: ls_trials + 1.
+
+    mpc = OpenLoopMPC(model, horizon=25)               # model: a (Differentiable)EnvironmentModel, fp32 state
+    u, J, info = mpc.solve(obses, ref_indexes=ref)     # u [H, B, 2] in [-1, 1], J [B]
+    u0 = mpc.warm_start(u)                             # the tape shifted by one step: next control step's u_init
+"""
+import ctypes as C
+
+import torch
+
+from . import _capi
+
+__all__ = ['OpenLoopMPC', 'cost_from_out5', 'projected_gradient', 'DEFAULT_WEIGHTS']
+
+DEFAULT_WEIGHTS = (-1.0, 10.0, 0.0, 0.0, 0.0)
+
+
+def cost_from_out5(out5_steps, weights=DEFAULT_WEIGHTS):
+    """J [B] = sum_t w . out5_steps[t] from out5_steps [H, 5, B], in ONE fixed order: per step the non-zero weights' terms are added
+    in row order (k = 0..4), then one torch reduction over the steps (its order is fixed by the shape and the device, and an env's
+    sum does not involve its neighbours).  The solver and its tests form J with this function only."""
+    w = [float(v) for v in weights]
+    per_step = None
+    for k in range(5):
+        if w[k] != 0.0:
+            term = out5_steps[:, k] * w[k]
+            per_step = term if per_step is None else per_step + term
+    if per_step is None:
+        return torch.zeros_like(out5_steps[0, 0])
+    return per_step.sum(0)
+
+
+def projected_gradient(evaluate, u, iterations, ls_trials=3, c1=1e-4, shrink=0.25, alpha_min=1e-8, alpha_max=1e2, check_every=0,
+                       tol=1e-3):
+    """min J(u) over the box [-1, 1] for a batch of independent problems.
+        evaluate(u [H, B, 2], need_grad) -> (J [B], g [H, B, 2] or None)
+    Tensors of any float dtype and device (the GPU solver runs it in float32 on the device, the fixture generator in float64 on the
+    CPU: the same lines).  -> (u, J, info); info: J_history [iterations + 1, B] (J after every iteration: accepted steps only, so it
+    never increases), accepted [iterations, B], iterations (done), evaluations."""
+    def env(v):
+        return v.view(1, -1, 1)
+    u = u.clamp(-1.0, 1.0)
+    J, g = evaluate(u, True)
+    n_eval = 1
+    # first step: no env moves an action by more than 1 (half the box)
+    alpha = (1.0 / g.abs().amax((0, 2)).clamp_min(1e-12)).clamp(alpha_min, alpha_max)
+    hist, acc = [J], []
+    done_iters = 0
+    for it in range(iterations):
+        a = alpha
+        u_new, J_new = u, J
+        done = torch.zeros_like(J, dtype=torch.bool)
+        for _ in range(ls_trials):
+            u_try = (u - env(a) * g).clamp(-1.0, 1.0)
+            J_try, _g = evaluate(u_try, False)
+            n_eval += 1
+            slope = ((u_try - u) * g).sum((0, 2))                    # <= 0: the projected step is a descent direction
+            ok = (J_try <= J + c1 * slope) & ~done                   # a NaN cost is a rejection
+            u_new = torch.where(env(ok), u_try, u_new)
+            J_new = torch.where(ok, J_try, J_new)
+            done = done | ok
+            a = torch.where(done, a, a * shrink)
+        _J, g_new = evaluate(u_new, True)                            # the same bits as J_new: value-only == the full form's forward
+        n_eval += 1
+        s, y = u_new - u, g_new - g
+        ss, sy = (s * s).sum((0, 2)), (s * y).sum((0, 2))
+        bb = torch.where(sy > 0, ss / sy.clamp_min(1e-30), a * 4.0)  # BB1; non-positive curvature along s: lengthen
+        alpha = torch.where(done, bb, a).clamp(alpha_min, alpha_max)  # a rejected env goes on from its shortened step
+        u, J, g = u_new, J_new, g_new
+        hist.append(J)
+        acc.append(done)
+        done_iters = it + 1
+        if check_every and (it + 1) % check_every == 0 and it + 1 >= check_every:
+            if float((hist[-1 - check_every] - J).max()) <= tol:    # the one host read
+                break
+    info = dict(J_history=torch.stack(hist), accepted=torch.stack(acc) if acc else torch.zeros((0,) + J.shape, dtype=torch.bool),
+                iterations=done_iters, evaluations=n_eval, launches_per_iteration=ls_trials + 1)
+    return u, J, info
+
+
+class OpenLoopMPC(object):
+    """Open-loop MPC over `horizon` steps of `model` (task, slot modes, mode and path tables are the model's).  fp32 state only."""
+
+    def __init__(self, model, horizon=25, weights=DEFAULT_WEIGHTS, iterations=60, ls_trials=3, c1=1e-4):
+        from .dynamics_and_models import _dev, _stream
+        self._dev_fn, self._stream_fn = _dev, _stream
+        if model.state_dtype != torch.float32:
+            raise _capi.EbError('OpenLoopMPC: the reverse pass is fp32-state only')
+        self.model, self.horizon = model, int(horizon)
+        self.weights = tuple(float(v) for v in weights)
+        if len(self.weights) != 5:
+            raise ValueError('weights: five floats, one per out5 row')
+        self.iterations, self.ls_trials, self.c1 = int(iterations), int(ls_trials), float(c1)
+        self._fn = model.api.grad_fn('eb_rollout_tape_vjp')          # EbError here when the library has no reverse pass
+        limit = C.c_int32(0)
+        model.api.check(model.api.grad_fn('eb_rollout_tape_vjp_max_horizon')(model.handle, C.byref(limit)))
+        if self.horizon < 1 or self.horizon > limit.value:
+            raise ValueError('OpenLoopMPC: horizon %d is outside 1..%d (eb_rollout_tape_vjp_max_horizon)' % (self.horizon, limit.value))
+        self._w5 = (C.c_float * 5)(*self.weights)
+        self.launches = 0
+
+    # -- one launch ------------------------------------------------------------------------------
+    def value_and_grad(self, obs, u, ref_idx, path_id, need_grad=True):
+        """-> (J [B], dJ/du [H, B, 2] or None, out5_steps [H, 5, B]): one eb_rollout_tape_vjp launch on the current stream"""
+        m = self.model
+        H, B = u.shape[0], obs.shape[0]
+        out5 = torch.empty((H, 5, B), dtype=torch.float32, device=obs.device)
+        g = torch.empty_like(u) if need_grad else None
+        rc = self._fn(m.handle, B, H, obs.data_ptr(), u.data_ptr(), None if ref_idx is None else ref_idx.data_ptr(), path_id,
+                      None, 0, None, self._w5, out5.data_ptr(), None, None, None if g is None else g.data_ptr(),
+                      self._stream_fn(m.device))
+        if rc != 0:
+            m.api.check(rc)
+        self.launches += 1
+        return cost_from_out5(out5, self.weights), g, out5
+
+    def _paths(self, ref_indexes, path_index):
+        m = self.model
+        if m.mode == 'training':
+            if ref_indexes is None:
+                raise ValueError("OpenLoopMPC.solve: mode='training' needs ref_indexes [B]")
+            return self._dev_fn(ref_indexes, m.device, torch.int32), 0
+        if path_index is None:
+            raise ValueError("OpenLoopMPC.solve: mode='selecting' needs path_index")
+        return None, int(path_index)
+
+    def solve(self, obses, ref_indexes=None, path_index=None, u_init=None, iterations=None, check_every=0, tol=1e-3):
+        """-> (u [H, B, 2] raw actions in [-1, 1], J [B], info).  u_init: None = the zero tape (mpc/main.py:550), or a tape
+        [H, B, 2] (warm_start).  info as projected_gradient's, plus `launches`."""
+        m = self.model
+        obs = self._dev_fn(obses, m.device).detach()
+        if obs.dim() != 2 or obs.shape[1] != m.obs_dim:
+            raise ValueError('obses must be [B, %d]; got %s' % (m.obs_dim, tuple(obs.shape)))
+        B = obs.shape[0]
+        ri, pid = self._paths(ref_indexes, path_index)
+        if u_init is None:
+            u0 = torch.zeros((self.horizon, B, 2), dtype=torch.float32, device=m.device)
+        else:
+            u0 = self._dev_fn(u_init, m.device).detach()
+            if tuple(u0.shape) != (self.horizon, B, 2):
+                raise ValueError('u_init must be [%d, %d, 2]; got %s' % (self.horizon, B, tuple(u0.shape)))
+        first = self.launches
+
+        def evaluate(u, need_grad):
+            J, g, _ = self.value_and_grad(obs, u.contiguous(), ri, pid, need_grad)
+            return J, g
+        u, J, info = projected_gradient(evaluate, u0, self.iterations if iterations is None else int(iterations),
+                                        ls_trials=self.ls_trials, c1=self.c1, check_every=check_every, tol=tol)
+        info['launches'] = self.launches - first
+        return u.contiguous(), J, info
+
+    @staticmethod
+    def warm_start(u):
+        """The tape shifted by one step, its last action repeated: the next control step's u_init (the line mpc/main.py:571 left
+        commented out)."""
+        return torch.cat([u[1:], u[-1:]], 0).contiguous()

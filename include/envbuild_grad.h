@@ -1,5 +1,6 @@
 /*
- * envbuild_grad.h — C-ABI of the reverse pass of the model step (gradients through EnvironmentModel.rollout_out).
+ * envbuild_grad.h — C-ABI of the reverse pass of the model step and of the open-loop rollout (gradients through
+ * EnvironmentModel.rollout_out).
  *
  * A second header next to envbuild.h: these symbols are exported by env_build_amd/lib/libenvbuild_hip.so ONLY (the CPU oracle
  * of envbuild.h has no reverse pass), EB_ABI_VERSION is untouched, and a binding looks them up on demand.  Conventions
@@ -22,8 +23,8 @@
  *   - ONE divergence from the reference: a circle distance (DAM:227) — or, in two2one (DAM:738, 748), the distance of the next
  *     pose to the junction corner — of exactly 0 makes the reference produce NaN (the derivative of sqrt at 0); the term
  *     contributes 0 here;
- *   - fp32 state only.  The fp16-state entry points (eb_rollout_step_f16 / eb_rollout_tape_f16), the gated / tape kernels and
- *     second derivatives have no reverse pass; obs rows here are always fp32.
+ *   - fp32 state only.  The fp16-state entry points (eb_rollout_step_f16 / eb_rollout_tape_f16), the gated kernel and second
+ *     derivatives have no reverse pass; obs rows here are always fp32.  The open-loop tape has one: eb_rollout_tape_vjp.
  */
 #ifndef ENVBUILD_GRAD_H
 #define ENVBUILD_GRAD_H
@@ -34,7 +35,7 @@
 extern "C" {
 #endif
 
-#define EB_GRAD_ABI_VERSION 1
+#define EB_GRAD_ABI_VERSION 2
 
 int eb_grad_abi_version(void);
 
@@ -68,6 +69,31 @@ int eb_rollout_step_vjp(eb_handle h, int32_t n_env, const float* obs_in, const f
 int eb_rollout_chain_vjp(eb_handle h, int32_t n_env, int32_t horizon, const float* obs_steps, const float* action_tape,
                          const int32_t* ref_idx, int32_t path_id, const float* g_obs_final, int32_t ld_final,
                          const float* g_out5_steps, float* g_work, float* g_obs0, float* g_action_tape, void* stream);
+
+/* Value and gradient of an open-loop rollout of `horizon` steps in ONE launch (ABI 2): the forward sweep of eb_rollout_tape and
+ * the reverse sweep of eb_rollout_chain_vjp, with the tape kept in registers and LDS (csrc/eb_rollout_tape_vjp.hip).  What an MPC
+ * solver calls per evaluation of  J(u) = sum_t <w, out5_t(u)>  (the callers' cost_function, mpc/main.py:470-479).
+ *   obs0          [n_env, D];  action_tape [horizon, n_env, 2] raw;  ref_idx / path_id as in eb_rollout_step;
+ *   g_obs_final   cotangent of the obs after the last step, row stride ld_final (>= nd); NULL = zeros;
+ *   g_out5_steps  [horizon, 5, n_env] cotangents of every step's out5, or NULL: then
+ *   w5            HOST pointer to 5 floats — the cotangent of out5 row k at every step and env; NULL = zeros.  Equals a
+ *                 g_out5_steps array filled with those five values;
+ *   out5_steps    [horizon, 5, n_env] or NULL: the forward's outputs — the bits of eb_rollout_tape;
+ *   obs_out       [n_env, D] or NULL: the obs after the last step — the bits of eb_rollout_tape;
+ *   g_obs0        [n_env, nd] or NULL: cotangent of obs0[:, :nd];
+ *   g_action_tape [horizon, n_env, 2] or NULL.  g_obs0 == g_action_tape == NULL is the value-only form: no reverse sweep.
+ * Gradients are the bits of `horizon` calls of eb_rollout_step that keep every pre-step obs followed by eb_rollout_chain_vjp with
+ * the same cotangents; the gradient contract above holds unchanged (vehicle columns are never written).  A row's bits do not depend
+ * on its position in the batch or on its neighbours, and a launch repeats its bits.  No atomics to global memory.
+ * horizon above eb_rollout_tape_vjp_max_horizon (>= 25 for every n_veh <= 64) is EB_EINVAL with the limit in eb_last_error: compose
+ * eb_rollout_step and eb_rollout_chain_vjp instead.  n_env == 0 is a no-op; training mode without ref_idx is EB_EINVAL. */
+int eb_rollout_tape_vjp(eb_handle h, int32_t n_env, int32_t horizon, const float* obs0, const float* action_tape,
+                        const int32_t* ref_idx, int32_t path_id, const float* g_obs_final, int32_t ld_final,
+                        const float* g_out5_steps, const float* w5, float* out5_steps, float* obs_out, float* g_obs0,
+                        float* g_action_tape, void* stream);
+
+/* The longest horizon eb_rollout_tape_vjp takes on this handle (its tile must fit the LDS; depends on n_veh). */
+int eb_rollout_tape_vjp_max_horizon(eb_handle h, int32_t* max_horizon);
 
 #ifdef __cplusplus
 }
