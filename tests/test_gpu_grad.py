@@ -1,6 +1,6 @@
 """GPU (-m gpu): the reverse pass of the rollout step (include/envbuild_grad.h, csrc/eb_rollout_vjp.hip) against the gradient
-fixtures of scripts/gen_golden_grad.py — the reference's own Python under autograd, float64 — and its invariants; the autograd
-façade (env_build_amd/grad.py) against the manual chain of C calls; the ADP example.
+fixtures of scripts/gen_golden_grad.py (G15, G16 and the edge scenes of G18) — the reference's own Python under autograd, float64 —
+and its invariants; the autograd façade (env_build_amd/grad.py) against the manual chain of C calls; the ADP example.
 
 Tolerance and the cap on excluded rows: tests/_grad_cases.py.  Every check prints max |g - g64| / E per column before it asserts."""
 import importlib.util
@@ -11,7 +11,7 @@ import pytest
 
 from env_build_amd import _capi
 from tests._helpers import DeviceModel, ROOT
-from tests._grad_cases import TASKS, MAX_EXCLUDED, cases, check_columns
+from tests._grad_cases import TASKS, MAX_EXCLUDED, cases, check_columns, edge_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -49,20 +49,30 @@ def same_bits(a, b):
     return np.array_equal(np.asarray(a).view(np.uint32), np.asarray(b).view(np.uint32))
 
 
-@pytest.mark.parametrize('task', TASKS)
-def test_step_vjp_meets_the_reference_gradients(task):
-    """g15: single steps.  |g - g64| <= 4 E_c + 2^-20 max|g64| per column over the flagged rows; at most 1 % of the rows excluded."""
-    cs = cases('g15_grad_step', task)
+def step_cases_meet_the_reference(task, cs, tag):
     rows = sum(len(c['ok']) for c in cs)
     assert sum(int((~c['ok']).sum()) for c in cs) <= MAX_EXCLUDED * rows
     for c in cs:
         m = model_for(task, c)
         gi, ga = m.step_vjp(c['obs'], c['actions'], c.ref_idx(), c.path_id, c['g_obs_out'], c['g_out5'])
-        check_columns(gi, c['g_obs64'], c['E_obs'], c['ok'], 'g15 %s %s obs' % (task, c.name))
-        check_columns(ga, c['g_act64'], c['E_act'], c['ok'], 'g15 %s %s act' % (task, c.name))
+        check_columns(gi, c['g_obs64'], c['E_obs'], c['ok'], '%s %s %s obs' % (tag, task, c.name))
+        check_columns(ga, c['g_act64'], c['E_act'], c['ok'], '%s %s %s act' % (tag, task, c.name))
         full, ga2 = m.step_vjp(c['obs'], c['actions'], c.ref_idx(), c.path_id, c['g_obs_out'], c['g_out5'], full=True)
         assert same_bits(full[:, :c.nd], gi) and same_bits(ga2, ga)          # ld_in == D: the same bits ...
         assert not full[:, c.nd:].any() and not np.signbit(full[:, c.nd:]).any()   # ... and +0 in every vehicle column
+
+
+@pytest.mark.parametrize('task', TASKS)
+def test_step_vjp_meets_the_reference_gradients(task):
+    """g15: single steps.  |g - g64| <= 4 E_c + 2^-20 max|g64| per column over the flagged rows; at most 1 % of the rows excluded."""
+    step_cases_meet_the_reference(task, cases('g15_grad_step', task), 'g15')
+
+
+@pytest.mark.parametrize('task', TASKS)
+def test_step_vjp_meets_the_edge_scenes(task):
+    """g18: every wall condition by either circle, every two2one region, both sides of the v_x clip, crowded and empty
+    neighbourhoods at 32 and 64 slots, egos off the cell grid — the same bound, both row forms."""
+    step_cases_meet_the_reference(task, edge_cases(task)[0], 'g18')
 
 
 def forward_states(m, c):
@@ -75,12 +85,7 @@ def forward_states(m, c):
     return np.stack(pre), np.stack(out5)
 
 
-@pytest.mark.parametrize('task', TASKS)
-def test_chain_vjp_meets_the_reference_gradients(task):
-    """g16: chains of 5 and 25 steps through eb_rollout_chain_vjp and through a loop of eb_rollout_step_vjp (same bits).  The
-    forward states are the package's own; a row whose forward out5 leaves the fixture's float32 forward by more than the tolerance
-    reference-generated fixtures are held to here (rtol 1e-5 next to atol 5e-6) counts as excluded, under the same 1 % cap."""
-    cs = cases('g16_grad_chain', task)
+def chain_cases_meet_the_reference(task, cs, tag):
     rows = excluded = 0
     for c in cs:
         m = model_for(task, c)
@@ -93,10 +98,25 @@ def test_chain_vjp_meets_the_reference_gradients(task):
         for t in reversed(range(len(pre))):
             g_next, gts[t] = m.step_vjp(pre[t], c['tape'][t], c.ref_idx(), c.path_id, g_next, c['g_out5_steps'][t])
         assert same_bits(g_next, g0) and same_bits(np.stack(gts), gt), c.name
-        check_columns(g0, c['g_obs64'], c['E_obs'], ok, 'g16 %s %s obs0' % (task, c.name))
-        check_columns(np.moveaxis(gt, 0, 1), np.moveaxis(c['g_act64'], 0, 1), c['E_act'], ok, 'g16 %s %s tape' % (task, c.name))
-    print('g16 %s: %d of %d rows excluded' % (task, excluded, rows))
+        check_columns(g0, c['g_obs64'], c['E_obs'], ok, '%s %s %s obs0' % (tag, task, c.name))
+        check_columns(np.moveaxis(gt, 0, 1), np.moveaxis(c['g_act64'], 0, 1), c['E_act'], ok, '%s %s %s tape' % (tag, task, c.name))
+    print('%s %s: %d of %d rows excluded' % (tag, task, excluded, rows))
     assert excluded <= MAX_EXCLUDED * rows
+
+
+@pytest.mark.parametrize('task', TASKS)
+def test_chain_vjp_meets_the_reference_gradients(task):
+    """g16: chains of 5 and 25 steps through eb_rollout_chain_vjp and through a loop of eb_rollout_step_vjp (same bits).  The
+    forward states are the package's own; a row whose forward out5 leaves the fixture's float32 forward by more than the tolerance
+    reference-generated fixtures are held to here (rtol 1e-5 next to atol 5e-6) counts as excluded, under the same 1 % cap."""
+    chain_cases_meet_the_reference(task, cases('g16_grad_chain', task), 'g16')
+
+
+@pytest.mark.parametrize('task', TASKS)
+def test_chain_vjp_meets_the_edge_chains(task):
+    """g18: a 25-step chain from the junction's exit side and a 5-step one at 32 slots from next to the entry lane's walls, held as
+    the g16 chains are (the 1 % cap over this file's chain rows)."""
+    chain_cases_meet_the_reference(task, edge_cases(task)[1], 'g18')
 
 
 def test_null_cotangents_are_zero_arrays():

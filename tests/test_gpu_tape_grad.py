@@ -1,5 +1,5 @@
 """GPU (-m gpu): eb_rollout_tape_vjp — value and gradient of an open-loop rollout in one launch (include/envbuild_grad.h,
-csrc/eb_rollout_tape_vjp.hip) — against the G16 chain fixtures (bound: tests/_grad_cases.py), bit for bit against the composed path
+csrc/eb_rollout_tape_vjp.hip) — against the G16 chain fixtures and the G18 edge chains (bound: tests/_grad_cases.py), bit for bit against the composed path
 (eb_rollout_step launches that keep every pre-step obs, then eb_rollout_chain_vjp) and against eb_rollout_tape's forward, its
 invariants, its refusals, and grad.rollout_tape against a loop of grad.rollout_step under torch.autograd."""
 import ctypes as C
@@ -10,7 +10,7 @@ import pytest
 from env_build_amd import _capi
 from env_build_amd.synthetic import make_rollout_inputs, assemble_obs
 from tests._helpers import DeviceModel
-from tests._grad_cases import TASKS, MAX_EXCLUDED, cases, check_columns
+from tests._grad_cases import TASKS, MAX_EXCLUDED, NEAR_R, cases, check_columns, check_zero_distance, edge_cases, zero_distance_case
 
 pytestmark = pytest.mark.gpu
 NATIVE = {'left': 8, 'straight': 9, 'right': 5}
@@ -36,6 +36,14 @@ class TapeModel(DeviceModel):
                                   0 if g_final is None else g_final.shape[1], self._ptr(g5), w, self._ptr(o5), self._ptr(oo),
                                   self._ptr(g0), self._ptr(gt), self.stream)
         return o5, oo, g0, gt
+
+    def t_step_vjp(self, obs, actions, ri, path_id, g_obs_out, g_out5):
+        """eb_rollout_step_vjp, ld_in == nd -> g_obs_in [n, nd], g_actions [n, 2]"""
+        n, nd = obs.shape[0], self.D - 4 * self.n_veh
+        gi, ga = self.torch.full((n, nd), float('nan'), device=self.dev), self.torch.full((n, 2), float('nan'), device=self.dev)
+        self.api.rollout_step_vjp(self.h, n, self._ptr(obs), self._ptr(actions), self._ptr(ri), int(path_id), self._ptr(g_obs_out),
+                                  g_obs_out.shape[1], self._ptr(g_out5), self._ptr(gi), nd, self._ptr(ga), self.stream)
+        return gi, ga
 
     def t_composed(self, obs0, tape, ri, path_id, g_final=None, g5=None):
         """what a user had to do before: H eb_rollout_step launches that keep every pre-step obs, then eb_rollout_chain_vjp"""
@@ -107,12 +115,7 @@ def model_for(task, c):
     return TapeModel(task, n_veh=c.n_veh, n_future=c.n_future, mode=c.mode)
 
 
-@pytest.mark.parametrize('task', TASKS)
-def test_tape_vjp_meets_the_reference_gradients_and_forward(task):
-    """g16: every chain case.  Gradients: |g - g64| <= 4 E_c + 2^-20 max|g64| per column over the flagged rows.  Forward: out5_steps
-    against the fixtures' float32 forward as tests/test_gpu_grad.py holds it (rtol 1e-5 next to atol 5e-6; a row beyond it counts as
-    excluded, under the same 1 % cap)."""
-    cs = cases('g16_grad_chain', task)
+def tape_meets_the_reference(task, cs, tag):
     rows = excluded = 0
     for c in cs:
         m = model_for(task, c)
@@ -122,10 +125,95 @@ def test_tape_vjp_meets_the_reference_gradients_and_forward(task):
         want = c['out5_f32'].astype(np.float64)
         ok = c['ok'] & (np.abs(out5 - want) <= 5e-6 + 1e-5 * np.abs(want)).all((0, 1))
         rows += len(ok); excluded += int((~ok).sum())
-        check_columns(g0, c['g_obs64'], c['E_obs'], ok, 'g16 tape %s %s obs0' % (task, c.name))
-        check_columns(np.moveaxis(gt, 0, 1), np.moveaxis(c['g_act64'], 0, 1), c['E_act'], ok, 'g16 tape %s %s tape' % (task, c.name))
-    print('g16 tape %s: %d of %d rows excluded' % (task, excluded, rows))
+        check_columns(g0, c['g_obs64'], c['E_obs'], ok, '%s tape %s %s obs0' % (tag, task, c.name))
+        check_columns(np.moveaxis(gt, 0, 1), np.moveaxis(c['g_act64'], 0, 1), c['E_act'], ok, '%s tape %s %s tape' % (tag, task, c.name))
+    print('%s tape %s: %d of %d rows excluded' % (tag, task, excluded, rows))
     assert excluded <= MAX_EXCLUDED * rows
+
+
+@pytest.mark.parametrize('task', TASKS)
+def test_tape_vjp_meets_the_reference_gradients_and_forward(task):
+    """g16: every chain case.  Gradients: |g - g64| <= 4 E_c + 2^-20 max|g64| per column over the flagged rows.  Forward: out5_steps
+    against the fixtures' float32 forward as tests/test_gpu_grad.py holds it (rtol 1e-5 next to atol 5e-6; a row beyond it counts as
+    excluded, under the same 1 % cap)."""
+    tape_meets_the_reference(task, cases('g16_grad_chain', task), 'g16')
+
+
+@pytest.mark.parametrize('task', TASKS)
+def test_tape_vjp_meets_the_edge_chains(task):
+    """g18: the chains that start on the junction's exit side and next to the entry lane's walls, held as the g16 chains are"""
+    tape_meets_the_reference(task, edge_cases(task)[1], 'g18')
+
+
+def edge_synthetic_case(m, task, B, H, seed):
+    """synthetic_case with every vehicle within 4.5 m of its ego (each record in the near queue: the queue of a tile is full), a
+    third of the egos up to 400 m away (off the closest-point cell grid), a third shifted sideways onto the lane's walls"""
+    import torch
+    inp = make_rollout_inputs(task, B, m.n_veh, H, seed=seed, n_future=m.n_future)
+    rng = np.random.default_rng(seed + 1)
+    ego, kind = inp['ego'], np.arange(B) % 3
+    far, wall = kind == 1, kind == 2
+    ego[far, 3:5] += rng.choice([-1.0, 1.0], (int(far.sum()), 2)) * rng.uniform(60.0, 380.0, (int(far.sum()), 2))
+    ego[wall, 3:5] += rng.choice([-1.0, 1.0], (int(wall.sum()), 2)) * rng.uniform(0.8, 1.8, (int(wall.sum()), 2))
+    rad, ang = 0.3 + 4.2 * np.sqrt(rng.random((B, m.n_veh))), rng.uniform(-np.pi, np.pi, (B, m.n_veh))
+    veh = inp['veh'].reshape(B, m.n_veh, 4)
+    veh[:, :, 0], veh[:, :, 1] = ego[:, 3:4] + rad * np.cos(ang), ego[:, 4:5] + rad * np.sin(ang)
+    assert (np.hypot(veh[:, :, 0] - ego[:, 3:4], veh[:, :, 1] - ego[:, 4:5]) < NEAR_R - 1.0).all() and np.abs(ego[:, 3:5]).max() > 300.0
+    training = m.mode == 'training'
+    ri = inp['ref_idx'].copy()
+    if training:
+        ri[::37] = 5
+    trk = m.tracking_error(ego[:, 3], ego[:, 4], ego[:, 5], ego[:, 0], m.n_future, ref_idx=np.clip(ri, 0, 2) if training else None, path_id=1)
+    obs0 = assemble_obs(ego, trk, veh.reshape(B, -1))
+    tape = inp['actions'].astype(np.float32)
+    tape[:, ::11] *= 1.3
+    g = torch.Generator(device='cuda').manual_seed(seed)
+    nd = m.D - 4 * m.n_veh
+    g_final = torch.randn((B, nd), device='cuda', generator=g)
+    g5 = torch.randn((H, 5, B), device='cuda', generator=g)
+    return m.to_dev(obs0), m.to_dev(tape), (m.to_dev(ri, np.int32) if training else None), 1, g_final, g5
+
+
+@pytest.mark.parametrize('task', TASKS)
+@pytest.mark.parametrize('mode', ['training', 'selecting'])
+def test_tape_vjp_has_the_bits_of_the_composed_path_in_crowded_remote_and_near_wall_scenes(task, mode):
+    """32 and 64 slots, every record near, in every tile shape the launch picks by batch size (csrc/eb_rollout_tape_vjp.hip:
+    tv_pick_tile — 32 envs per block from 2 * CUs blocks of 32 on, 16 from 2 * CUs blocks of 16 on, 8 below; 64 slots: 16 and 8), each
+    batch leaving idle env lanes in its last block: the bits of the composed path and of eb_rollout_tape's forward."""
+    import torch
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    n = 0
+    for n_veh, tiles in ((32, (32, 16, 8)), (64, (16, 8))):
+        m = TapeModel(task, n_veh=n_veh, n_future=0, mode=mode)
+        for E in tiles:
+            B = 2 * n_cu * E + 11 if E > 8 else 211
+            H = 5 if E > 8 else 25
+            obs0, tape, ri, pid, g_final, g5 = edge_synthetic_case(m, task, B, H, seed=1000 * n_veh + E)
+            got = m.t_tape_vjp(obs0, tape, ri, pid, g_final, g5)
+            want = m.t_composed(obs0, tape, ri, pid, g_final, g5)
+            what = '%s %s N%d E%d B%d H%d' % (task, mode, n_veh, E, B, H)
+            all_same(got, want, what)
+            f5, fo = m.t_forward_tape(obs0, tape, ri, pid)
+            assert same(got[0], f5) and same(got[1], fo), what + ': forward differs from eb_rollout_tape'
+            assert bool(torch.isfinite(got[2]).all()) and bool(torch.isfinite(got[3]).all()), what
+            assert bool((got[0][0, 3] > 0).all()), what       # every row has circle pairs below 2.5 m at the first step
+            n += 1
+    assert n == 5
+
+
+@pytest.mark.parametrize('task', TASKS)
+def test_zero_circle_distance_is_finite_and_the_same_in_both_kernels(task):
+    """A vehicle whose circle centres coincide with the ego's (distance exactly 0: NaN in the reference, a contribution of 0 here):
+    finite, the closed form of tests/_grad_cases.py:zero_distance_case within the case's column tolerance, and the same bits from
+    eb_rollout_step_vjp and from a one-step eb_rollout_tape_vjp."""
+    c, rows, obs, want = zero_distance_case(task)
+    m = model_for(task, c)
+    ri = None if c.ref_idx() is None else m.to_dev(c.ref_idx(), np.int32)
+    ob, ac, g, g5 = m.to_dev(obs), m.to_dev(c['actions']), m.to_dev(c['g_obs_out']), m.to_dev(c['g_out5'])
+    gi, ga = m.t_step_vjp(ob, ac, ri, c.path_id, g, g5)
+    _o5, _oo, g0, gt = m.t_tape_vjp(ob, ac[None].contiguous(), ri, c.path_id, g, g5[None].contiguous())
+    assert same(gi, g0) and same(ga, gt[0])
+    check_zero_distance(c, rows, gi.cpu().numpy(), ga.cpu().numpy(), want, 'g18 %s zero distance' % task)
 
 
 @pytest.mark.parametrize('task', TASKS)

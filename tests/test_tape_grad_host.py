@@ -1,6 +1,6 @@
 """CPU (-m "not gpu"): the one-launch value and gradient of an open-loop rollout (eb_rollout_tape_vjp) is declared, bound and
 exported; a library without it is refused cleanly; its per-env reverse sweep (csrc/eb_tape_grad_device.h, the text the kernel runs,
-compiled for the host) meets every G16 chain fixture under the bound of tests/_grad_cases.py; the solver's update rule
+compiled for the host) meets every G16 chain fixture and every G18 edge chain under the bound of tests/_grad_cases.py; the solver's update rule
 (env_build_amd/mpc.py, device-agnostic torch) does what it promises on a problem with a known answer; the MPC fixtures
 (scripts/gen_golden_mpc.py) are self-consistent."""
 import ctypes as C
@@ -14,7 +14,7 @@ import pytest
 
 from env_build_amd import _capi, build as eb_build
 from tests._helpers import ROOT, HostModel, golden, oracle_lib, _p
-from tests._grad_cases import TASKS, MAX_EXCLUDED, cases, check_columns
+from tests._grad_cases import TASKS, MAX_EXCLUDED, cases, chain_and_edge_cases, check_columns
 
 HEADER = os.path.join(ROOT, 'include', 'envbuild_grad.h')
 NEW = ('eb_rollout_tape_vjp', 'eb_rollout_tape_vjp_max_horizon')
@@ -95,8 +95,9 @@ def host_tape_vjp(h, task, c, pre, g_final, g5, w5=None):
 
 @pytest.mark.parametrize('task', TASKS)
 def test_tape_reverse_sweep_on_the_host_meets_the_chain_fixtures(task, host_harness):
-    """every G16 case: |g - g64| <= 4 E_c + 2^-20 max|g64| per column (tests/_grad_cases.py), at most 1 % of the rows excluded"""
-    cs = cases('g16_grad_chain', task)
+    """every G16 case and every chain of G18: |g - g64| <= 4 E_c + 2^-20 max|g64| per column (tests/_grad_cases.py), at most 1 % of
+    the rows excluded"""
+    cs = chain_and_edge_cases(task)
     rows = excluded = 0
     for c in cs:
         pre, out5 = oracle_forward(task, c)
