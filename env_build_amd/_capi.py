@@ -147,6 +147,17 @@ GRAD_PROTOTYPES = {
     'eb_rollout_tape_vjp_max_horizon': (C.c_int, [_P, C.POINTER(C.c_int32)]),
 }
 
+# include/envbuild_cand.h: K candidate tapes per env from one shared scene.  A third table with a version of its own, bound on first
+# use like the gradient table (the HIP library exports the symbols; the CPU oracle does not).
+EB_CAND_ABI_VERSION = 1
+CAND_PROTOTYPES = {
+    'eb_cand_abi_version': (C.c_int, []),
+    # (h, n_env, n_cand, horizon, obs0, action_tapes, ref_idx, ref_ld, path_ids (host), path_id, retrack, w5 (host), out5_steps, cost,
+    #  stream)
+    'eb_rollout_tape_cand': (C.c_int, [_P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
+    'eb_rollout_tape_cand_max': (C.c_int, [_P, _I, C.POINTER(C.c_int32)]),
+}
+
 
 class EbError(RuntimeError):
     pass
@@ -184,6 +195,25 @@ class CApi(object):
                 v = fns['eb_grad_abi_version']()
                 fns.clear()
                 raise EbError('%s: gradient ABI version %d, expected %d' % (self.path, v, EB_GRAD_ABI_VERSION))
+        return fns[symbol]
+
+    def cand_fn(self, symbol):
+        """The raw ctypes function of one include/envbuild_cand.h entry, bound on first use; EbError when this library has no
+        candidate-tape rollout."""
+        fns = self.__dict__.setdefault('_cand_fns', {})
+        if not fns:
+            missing = [n for n in CAND_PROTOTYPES if not hasattr(self.lib, n)]
+            if missing:
+                raise EbError('%s (backend %r) does not export %s: this library has no candidate-tape rollout (include/envbuild_cand.h '
+                              'is implemented by the HIP library only; rebuild an older one)' % (self.path, self.backend, ', '.join(missing)))
+            for n, (res, args) in CAND_PROTOTYPES.items():
+                fn = getattr(self.lib, n)
+                fn.restype, fn.argtypes = res, args
+                fns[n] = fn
+            if fns['eb_cand_abi_version']() != EB_CAND_ABI_VERSION:
+                v = fns['eb_cand_abi_version']()
+                fns.clear()
+                raise EbError('%s: candidate ABI version %d, expected %d' % (self.path, v, EB_CAND_ABI_VERSION))
         return fns[symbol]
 
     def check(self, rc):
@@ -231,7 +261,9 @@ class CApi(object):
 
     def __getattr__(self, name):
         # eb_xxx(...) with return-code checking: api.rollout_step(h, ...)
-        fn = self.grad_fn('eb_' + name) if 'eb_' + name in GRAD_PROTOTYPES else getattr(self.lib, 'eb_' + name)
+        sym = 'eb_' + name
+        fn = (self.grad_fn(sym) if sym in GRAD_PROTOTYPES else self.cand_fn(sym) if sym in CAND_PROTOTYPES
+              else getattr(self.lib, sym))
 
         def call(*args):
             self.check(fn(*args))

@@ -1,0 +1,100 @@
+"""K candidate action tapes per env from ONE shared scene, in one launch: rollout_tape_candidates.
+
+Everything that plans on the model asks "what do these K tapes cost from this one state?": the reference's decision loop scores one
+candidate per path of the task (hier_decision.py:113-121), a line search several step lengths, a multi-start solver its starts.  The
+vehicles of a scene do not depend on the ego (DAM:195, 331, 402), so eb_rollout_tape_cand (include/envbuild_cand.h,
+csrc/eb_rollout_tape_cand.hip) advances a scene's vehicle records once per env and runs only the ego's chain per candidate.
+
+    out5, cost = rollout_tape_candidates(model, obses, tapes, ref_indexes=ref)        # tapes [K, H, B, 2] -> out5 [K, H, 5, B]
+    _, cost = rollout_tape_candidates(model, obses, tapes, ref_indexes=ref, weights=(-1, 10, 0, 0, 0), want_out5=False)   # [K, B]
+
+out5[k] is bit for bit EnvironmentModel.rollout_tape's out5 for (obses, tapes[k], candidate k's path).  fp32 state only; no CPU path
+and no fall-back to K separate rollouts: without the HIP library's entry this raises.
+"""
+import ctypes as C
+
+import torch
+
+from . import _capi
+from .dynamics_and_models import _dev, _stream
+
+__all__ = ['rollout_tape_candidates', 'tape_cand_max']
+
+
+def tape_cand_max(model, horizon):
+    """the most candidates one eb_rollout_tape_cand launch takes for `model` (its slot count decides); larger sets go in chunks"""
+    limit = C.c_int32(0)
+    model.api.check(model.api.cand_fn('eb_rollout_tape_cand_max')(model.handle, int(horizon), C.byref(limit)))
+    return limit.value
+
+
+def launch_chunks(model, obs, tapes, ref_idx, path_ids, retrack, weights, want_out5):
+    """The launches behind rollout_tape_candidates on prepared device tensors: obs [B, D], tapes [K, H, B, 2], ref_idx int32 [B] or
+    [K, B] (training) or None, path_ids a list of K ints (selecting) or None.  -> (out5 or None, cost or None, launches).  A set
+    beyond tape_cand_max goes in chunks of the limit: candidates are independent, so the bits are those of one launch."""
+    K, H, B = tapes.shape[0], tapes.shape[1], obs.shape[0]
+    fn = model.api.cand_fn('eb_rollout_tape_cand')
+    out5 = torch.empty((K, H, 5, B), dtype=torch.float32, device=obs.device) if want_out5 else None
+    cost = torch.empty((K, B), dtype=torch.float32, device=obs.device) if weights is not None else None
+    if K == 0 or B == 0:
+        return out5, cost, 0
+    w5 = None if weights is None else (C.c_float * 5)(*[float(v) for v in weights])
+    limit = tape_cand_max(model, H)
+    per_cand = ref_idx is not None and ref_idx.dim() == 2
+    launches = 0
+    for k0 in range(0, K, limit):
+        k1 = min(K, k0 + limit)
+        ri = None if ref_idx is None else (ref_idx[k0:k1] if per_cand else ref_idx)
+        ids = None if path_ids is None else (C.c_int32 * (k1 - k0))(*path_ids[k0:k1])
+        rc = fn(model.handle, B, k1 - k0, H, obs.data_ptr(), tapes[k0:k1].data_ptr(), None if ri is None else ri.data_ptr(),
+                B if per_cand else 0, None if ids is None else C.cast(ids, C.c_void_p), 0, 1 if retrack else 0, w5,
+                None if out5 is None else out5[k0:k1].data_ptr(), None if cost is None else cost[k0:k1].data_ptr(),
+                _stream(model.device))
+        if rc != 0:
+            model.api.check(rc)
+        launches += 1
+    return out5, cost, launches
+
+
+def rollout_tape_candidates(model, obses, action_tapes, ref_indexes=None, path_indexes=None, retrack=False, weights=None,
+                            want_out5=True):
+    """Value-only open-loop rollout of K tapes per env from the shared rows `obses` [B, D]: action_tapes [K, H, B, 2] raw ->
+    (out5 [K, H, 5, B] or None, cost [K, B] or None).
+      ref_indexes   mode='training': [B] (every candidate on the env's path) or [K, B]; None = the model's own (reset);
+      path_indexes  mode='selecting': an int (all candidates) or K ints; None = the model's current path;
+      retrack       True: every (env, candidate) starts from the tracking error of the row's own pose on the CANDIDATE's path instead
+                    of obses' columns 6-8 (the reference builds one obs per path, hier_decision.py:113-117);
+      weights       five floats: cost[k] = sum_t w . out5[k][t] in the order include/envbuild_cand.h fixes; None = no cost;
+      want_out5     False: the cost only.
+    `model` (an EnvironmentModel with fp32 state) supplies the task, the slot modes and the tables; its own state is not touched."""
+    if model.state_dtype != torch.float32:
+        raise _capi.EbError('cand.rollout_tape_candidates: fp32 state only (the fp16-state kernels have no candidate form)')
+    model.api.cand_fn('eb_rollout_tape_cand')              # EbError before any work when the library has no such entry
+    if weights is None and not want_out5:
+        raise ValueError('rollout_tape_candidates: nothing asked for (weights is None and want_out5 is False)')
+    if weights is not None and len(tuple(weights)) != 5:
+        raise ValueError('weights: five floats, one per out5 row')
+    obs = _dev(obses, model.device).detach()
+    if obs.dim() != 2 or obs.shape[1] != model.obs_dim:
+        raise ValueError('obses must be [B, %d]; got %s' % (model.obs_dim, tuple(obs.shape)))
+    B = obs.shape[0]
+    tapes = _dev(action_tapes, model.device).detach()
+    if tapes.dim() != 4 or tapes.shape[2] != B or tapes.shape[3] != 2 or tapes.shape[1] < 1:
+        raise ValueError('action_tapes must be [K, H, %d, 2]; got %s' % (B, tuple(tapes.shape)))
+    K = tapes.shape[0]
+    ri, ids = None, None
+    if model.mode == 'training':
+        if ref_indexes is None:
+            ri = model._path_args()[0]
+        else:
+            ri = _dev(ref_indexes, model.device, torch.int32)
+        if tuple(ri.shape) not in ((B,), (K, B)):
+            raise ValueError('ref_indexes must be [%d] or [%d, %d]; got %s' % (B, K, B, tuple(ri.shape)))
+    else:
+        if path_indexes is None:
+            path_indexes = model._path_args()[1]
+        ids = [int(path_indexes)] * K if isinstance(path_indexes, int) else [int(v) for v in path_indexes]
+        if len(ids) != K:
+            raise ValueError('path_indexes must be an int or %d ints; got %d' % (K, len(ids)))
+    out5, cost, _ = launch_chunks(model, obs, tapes, ri, ids, retrack, weights, want_out5)
+    return out5, cost

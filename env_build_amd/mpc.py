@@ -13,11 +13,15 @@ proposal, Armijo backtracking on the projected step  u+ = clip(u - a g),  J(u+) 
 all rejected keeps its iterate (a `where`, not a host loop) and starts the next iteration from the shortened step.  A line-search
 trial is a value-only launch (g_action_tape = NULL); the update is a handful of elementwise torch ops on [H, B, 2]; nothing inside
 an iteration synchronises with the host, except the optional convergence read every `check_every` iterations.
-Launches per iteration: ls_trials + 1.
+Launches per iteration: ls_trials + 1.  With fused_line_search=True the trial tapes of an iteration — they depend on u, g and the
+step length only, not on each other's results — are scored by ONE eb_rollout_tape_cand launch (include/envbuild_cand.h: the scene's
+vehicle records advance once for all trials): 2 launches per iteration, the same bits.  Off by default.
 
     mpc = OpenLoopMPC(model, horizon=25)               # model: a (Differentiable)EnvironmentModel, fp32 state
     u, J, info = mpc.solve(obses, ref_indexes=ref)     # u [H, B, 2] in [-1, 1], J [B]
     u0 = mpc.warm_start(u)                             # the tape shifted by one step: next control step's u_init
+    u, J, info = mpc.solve(obses, ref_indexes=ref, u_init=torch.stack([u0, torch.zeros_like(u0)]))   # K starts: the best one per env
+    J_paths, best = mpc.select_path(obses)             # the model cost of every path of the task (hier_decision.py:113-121)
 """
 import ctypes as C
 
@@ -25,7 +29,7 @@ import torch
 
 from . import _capi
 
-__all__ = ['OpenLoopMPC', 'cost_from_out5', 'projected_gradient', 'DEFAULT_WEIGHTS']
+__all__ = ['OpenLoopMPC', 'cost_from_out5', 'projected_gradient', 'best_start', 'DEFAULT_WEIGHTS']
 
 DEFAULT_WEIGHTS = (-1.0, 10.0, 0.0, 0.0, 0.0)
 
@@ -45,13 +49,40 @@ def cost_from_out5(out5_steps, weights=DEFAULT_WEIGHTS):
     return per_step.sum(0)
 
 
+def first_minimum(J):
+    """index [B] of every env's lowest cost in J [K, B]: the first minimum; a NaN never wins; all NaN gives 0"""
+    best = torch.where(torch.isnan(J[0]), torch.full_like(J[0], float('inf')), J[0])
+    idx = torch.zeros(J.shape[1], dtype=torch.long, device=J.device)
+    for k in range(1, J.shape[0]):
+        better = J[k] < best                                         # strict: the first minimum; False for NaN
+        idx = torch.where(better, torch.full_like(idx, k), idx)
+        best = torch.where(better, J[k], best)
+    return idx
+
+
+def best_start(U, evaluate_many):
+    """Of K starts U [K, H, B, 2] every env's lowest-cost one, scored by ONE evaluate_many call: -> (u [H, B, 2], index [B], J [K, B]).
+    The first minimum wins; a NaN cost never wins; an env whose costs are all NaN gets start 0."""
+    U = U.clamp(-1.0, 1.0)
+    J = evaluate_many(U)
+    idx = first_minimum(J)
+    u = U.gather(0, idx.view(1, 1, -1, 1).expand(1, U.shape[1], U.shape[2], 2))[0]
+    return u.contiguous(), idx, J
+
+
 def projected_gradient(evaluate, u, iterations, ls_trials=3, c1=1e-4, shrink=0.25, alpha_min=1e-8, alpha_max=1e2, check_every=0,
-                       tol=1e-3):
+                       tol=1e-3, evaluate_many=None):
     """min J(u) over the box [-1, 1] for a batch of independent problems.
         evaluate(u [H, B, 2], need_grad) -> (J [B], g [H, B, 2] or None)
     Tensors of any float dtype and device (the GPU solver runs it in float32 on the device, the fixture generator in float64 on the
     CPU: the same lines).  -> (u, J, info); info: J_history [iterations + 1, B] (J after every iteration: accepted steps only, so it
-    never increases), accepted [iterations, B], iterations (done), evaluations."""
+    never increases), accepted [iterations, B], iterations (done), evaluations.
+        evaluate_many(U [K, H, B, 2]) -> J [K, B]   (optional)
+    With it the ls_trials trial tapes of an iteration are formed up front — their step lengths a, a shrink, (a shrink) shrink, ... by
+    repeated multiplication, as the sequential loop forms them for an env that has not accepted yet — scored by ONE call and accepted
+    by the same rule in trial order.  A trial after an env's accepted one is scored and ignored (sequentially it would have been
+    scored at the accepted step length and ignored), so u, J, J_history and accepted are those of the sequential loop bit for bit
+    whenever evaluate_many(U)[k] == evaluate(U[k], False)[0]."""
     def env(v):
         return v.view(1, -1, 1)
     u = u.clamp(-1.0, 1.0)
@@ -61,20 +92,34 @@ def projected_gradient(evaluate, u, iterations, ls_trials=3, c1=1e-4, shrink=0.2
     alpha = (1.0 / g.abs().amax((0, 2)).clamp_min(1e-12)).clamp(alpha_min, alpha_max)
     hist, acc = [J], []
     done_iters = 0
+    U = None
     for it in range(iterations):
         a = alpha
         u_new, J_new = u, J
         done = torch.zeros_like(J, dtype=torch.bool)
-        for _ in range(ls_trials):
-            u_try = (u - env(a) * g).clamp(-1.0, 1.0)
-            J_try, _g = evaluate(u_try, False)
+        J_many = None
+        if evaluate_many is not None:
+            if U is None:                                            # the trial tapes' buffer [K, H, B, 2]: one for the whole solve
+                U = torch.empty((ls_trials,) + tuple(u.shape), dtype=u.dtype, device=u.device)
+            steps = [a]
+            for k in range(ls_trials):
+                torch.clamp(u - env(steps[k]) * g, -1.0, 1.0, out=U[k])
+                steps.append(steps[k] * shrink)
+            tries = [U[k] for k in range(ls_trials)]
+            J_many = evaluate_many(U)
+        for k in range(ls_trials):
+            if J_many is None:
+                u_try = (u - env(a) * g).clamp(-1.0, 1.0)
+                J_try, _g = evaluate(u_try, False)
+            else:
+                u_try, J_try = tries[k], J_many[k]
             n_eval += 1
             slope = ((u_try - u) * g).sum((0, 2))                    # <= 0: the projected step is a descent direction
             ok = (J_try <= J + c1 * slope) & ~done                   # a NaN cost is a rejection
             u_new = torch.where(env(ok), u_try, u_new)
             J_new = torch.where(ok, J_try, J_new)
             done = done | ok
-            a = torch.where(done, a, a * shrink)
+            a = torch.where(done, a, a * shrink if J_many is None else steps[k + 1])   # (an env not done yet: a == steps[k])
         _J, g_new = evaluate(u_new, True)                            # the same bits as J_new: value-only == the full form's forward
         n_eval += 1
         s, y = u_new - u, g_new - g
@@ -89,14 +134,14 @@ def projected_gradient(evaluate, u, iterations, ls_trials=3, c1=1e-4, shrink=0.2
             if float((hist[-1 - check_every] - J).max()) <= tol:    # the one host read
                 break
     info = dict(J_history=torch.stack(hist), accepted=torch.stack(acc) if acc else torch.zeros((0,) + J.shape, dtype=torch.bool),
-                iterations=done_iters, evaluations=n_eval, launches_per_iteration=ls_trials + 1)
+                iterations=done_iters, evaluations=n_eval, launches_per_iteration=ls_trials + 1 if evaluate_many is None else 2)
     return u, J, info
 
 
 class OpenLoopMPC(object):
     """Open-loop MPC over `horizon` steps of `model` (task, slot modes, mode and path tables are the model's).  fp32 state only."""
 
-    def __init__(self, model, horizon=25, weights=DEFAULT_WEIGHTS, iterations=60, ls_trials=3, c1=1e-4):
+    def __init__(self, model, horizon=25, weights=DEFAULT_WEIGHTS, iterations=60, ls_trials=3, c1=1e-4, fused_line_search=False):
         from .dynamics_and_models import _dev, _stream
         self._dev_fn, self._stream_fn = _dev, _stream
         if model.state_dtype != torch.float32:
@@ -112,6 +157,9 @@ class OpenLoopMPC(object):
         if self.horizon < 1 or self.horizon > limit.value:
             raise ValueError('OpenLoopMPC: horizon %d is outside 1..%d (eb_rollout_tape_vjp_max_horizon)' % (self.horizon, limit.value))
         self._w5 = (C.c_float * 5)(*self.weights)
+        self.fused_line_search = bool(fused_line_search)
+        if self.fused_line_search:
+            model.api.cand_fn('eb_rollout_tape_cand')                # EbError here when the library has no candidate-tape rollout
         self.launches = 0
 
     # -- one launch ------------------------------------------------------------------------------
@@ -129,6 +177,40 @@ class OpenLoopMPC(object):
         self.launches += 1
         return cost_from_out5(out5, self.weights), g, out5
 
+    def values_many(self, obs, U, ref_idx, path_id):
+        """-> J [K, B] of K tapes U [K, H, B, 2] from the shared rows `obs`: one eb_rollout_tape_cand launch (per tape_cand_max
+        candidates) with out5_steps, and cost_from_out5 per candidate slice — J is formed by the lines value_and_grad forms it with"""
+        from .cand import launch_chunks
+        ids = None if ref_idx is not None else [path_id] * U.shape[0]
+        out5, _cost, launches = launch_chunks(self.model, obs, U.contiguous(), ref_idx, ids, False, None, True)
+        self.launches += launches
+        return torch.stack([cost_from_out5(out5[k], self.weights) for k in range(U.shape[0])])
+
+    def select_path(self, obses, tapes=None):
+        """The model cost of every path of the task from the shared rows `obses` [B, D] — the model-cost twin of
+        hier_decision.py:113-121 -> (J [P, B], best [B]: the first minimum).  Candidate p follows path p for every env and starts from
+        the row's tracking error on THAT path (retrack: the reference builds one obs per path, hier_decision.py:113-117); tapes
+        [P, H, B, 2] or None = the zero tapes.  J is eb_rollout_tape_cand's `cost` with this solver's weights.  One launch; the
+        hysteresis of hier_decision.py:121 stays with the caller."""
+        from .cand import launch_chunks
+        m = self.model
+        obs = self._dev_fn(obses, m.device).detach()
+        if obs.dim() != 2 or obs.shape[1] != m.obs_dim:
+            raise ValueError('obses must be [B, %d]; got %s' % (m.obs_dim, tuple(obs.shape)))
+        P, B = len(m.ref_path.path_list), obs.shape[0]
+        if tapes is None:
+            U = torch.zeros((P, self.horizon, B, 2), dtype=torch.float32, device=m.device)
+        else:
+            U = self._dev_fn(tapes, m.device).detach()
+            if tuple(U.shape) != (P, self.horizon, B, 2):
+                raise ValueError('tapes must be [%d, %d, %d, 2]; got %s' % (P, self.horizon, B, tuple(U.shape)))
+        ri, ids = None, list(range(P))
+        if m.mode == 'training':
+            ri, ids = torch.arange(P, dtype=torch.int32, device=m.device).view(P, 1).expand(P, B).contiguous(), None
+        _out5, J, launches = launch_chunks(m, obs, U, ri, ids, True, self.weights, False)
+        self.launches += launches
+        return J, first_minimum(J)
+
     def _paths(self, ref_indexes, path_index):
         m = self.model
         if m.mode == 'training':
@@ -141,7 +223,8 @@ class OpenLoopMPC(object):
 
     def solve(self, obses, ref_indexes=None, path_index=None, u_init=None, iterations=None, check_every=0, tol=1e-3):
         """-> (u [H, B, 2] raw actions in [-1, 1], J [B], info).  u_init: None = the zero tape (mpc/main.py:550), or a tape
-        [H, B, 2] (warm_start).  info as projected_gradient's, plus `launches`."""
+        [H, B, 2] (warm_start), or K starts [K, H, B, 2]: they are scored by one eb_rollout_tape_cand launch and every env starts
+        from its lowest-cost one (best_start; info['start_index'] [B]).  info as projected_gradient's, plus `launches`."""
         m = self.model
         obs = self._dev_fn(obses, m.device).detach()
         if obs.dim() != 2 or obs.shape[1] != m.obs_dim:
@@ -152,16 +235,22 @@ class OpenLoopMPC(object):
             u0 = torch.zeros((self.horizon, B, 2), dtype=torch.float32, device=m.device)
         else:
             u0 = self._dev_fn(u_init, m.device).detach()
-            if tuple(u0.shape) != (self.horizon, B, 2):
-                raise ValueError('u_init must be [%d, %d, 2]; got %s' % (self.horizon, B, tuple(u0.shape)))
+            if tuple(u0.shape[-3:]) != (self.horizon, B, 2) or u0.dim() not in (3, 4) or (u0.dim() == 4 and u0.shape[0] < 1):
+                raise ValueError('u_init must be [%d, %d, 2] or [K, %d, %d, 2]; got %s' % (self.horizon, B, self.horizon, B, tuple(u0.shape)))
         first = self.launches
+        start_index = None
+        if u0.dim() == 4:
+            u0, start_index, _ = best_start(u0, lambda U: self.values_many(obs, U, ri, pid))
 
         def evaluate(u, need_grad):
             J, g, _ = self.value_and_grad(obs, u.contiguous(), ri, pid, need_grad)
             return J, g
         u, J, info = projected_gradient(evaluate, u0, self.iterations if iterations is None else int(iterations),
-                                        ls_trials=self.ls_trials, c1=self.c1, check_every=check_every, tol=tol)
+                                        ls_trials=self.ls_trials, c1=self.c1, check_every=check_every, tol=tol,
+                                        evaluate_many=(lambda U: self.values_many(obs, U, ri, pid)) if self.fused_line_search else None)
         info['launches'] = self.launches - first
+        if start_index is not None:
+            info['start_index'] = start_index
         return u.contiguous(), J, info
 
     @staticmethod

@@ -1,0 +1,432 @@
+"""GPU (-m gpu): eb_rollout_tape_cand — K candidate action tapes per env from one shared scene in one launch
+(include/envbuild_cand.h, csrc/eb_rollout_tape_cand.hip) — bit for bit against eb_rollout_tape candidate by candidate, its `cost`
+against the order the header fixes, per-candidate paths with retrack, its independence properties, the reference's own rollouts
+(the g5 fixtures), its refusals, and the consumers: cand.rollout_tape_candidates, OpenLoopMPC with fused_line_search, K starts,
+select_path, examples/mpc_candidates.py."""
+import ctypes as C
+import glob
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+
+from env_build_amd import _capi
+from env_build_amd.dynamics_and_models import _unwrap
+from tests import _golden_checks as CK
+from tests._helpers import GOLDEN, ROOT, close, golden
+from tests._grad_cases import TASKS, edge_cases
+from tests.test_gpu_tape_grad import TapeModel, bits, same, synthetic_case, edge_synthetic_case
+from tests.test_gpu_mpc import setup as mpc_setup
+
+pytestmark = pytest.mark.gpu
+NATIVE = {'left': 8, 'straight': 9, 'right': 5}
+# weights of `cost`: zeros in different rows, and all zero.  Every set weighs the reward row (<= 0: minus sums of squares, DAM:198-207)
+# negatively and the penalty rows (>= 0: squared overlaps, DAM:218-295) positively, as every cost of this project does
+# (mpc.DEFAULT_WEIGHTS, examples/adp_policy_gradient.py): the terms of J then share one sign, and the bound on the difference between
+# two summation orders — relative to |J| — means what it says; weights that let the terms cancel would test the bound's form, not
+# the kernel.
+WEIGHTS = ((-1.0, 10.0, 0.0, 0.0, 0.0), (0.0, 0.0, 2.0, 0.0, 1.0), (-0.5, 0.0, 0.0, 0.25, 0.0), (-1.0, 10.0, 0.5, 0.25, 2.0),
+           (0.0, 0.0, 0.0, 0.0, 0.0))
+
+
+class CandModel(TapeModel):
+    """TapeModel + the entries of include/envbuild_cand.h; t_cand takes and returns torch tensors on the device"""
+
+    def cand_max(self, horizon=25):
+        v = C.c_int32(0)
+        self.api.rollout_tape_cand_max(self.h, int(horizon), C.byref(v))
+        return v.value
+
+    def t_cand(self, obs0, tapes, ri=None, ref_ld=0, path_ids=None, path_id=1, retrack=False, w5=None, out5=True, cost=None):
+        torch = self.torch
+        K, H, n = tapes.shape[0], tapes.shape[1], obs0.shape[0]
+        cost = (w5 is not None) if cost is None else cost
+        o5 = torch.full((K, H, 5, n), float('nan'), device=self.dev) if out5 else None
+        J = torch.full((K, n), float('nan'), device=self.dev) if cost else None
+        w = None if w5 is None else (C.c_float * 5)(*[float(v) for v in w5])
+        ids = None if path_ids is None else (C.c_int32 * len(path_ids))(*[int(v) for v in path_ids])
+        self.api.rollout_tape_cand(self.h, n, K, H, self._ptr(obs0), self._ptr(tapes), self._ptr(ri), int(ref_ld),
+                                   None if ids is None else C.cast(ids, C.c_void_p), int(path_id), int(bool(retrack)), w,
+                                   self._ptr(o5), self._ptr(J), self.stream)
+        return o5, J
+
+
+def cost_in_the_headers_order(out5, w5):
+    """include/envbuild_cand.h: cost = sum over ascending t from +0 of s_t; s_t = the rows with w != 0 in row order; float32, one
+    rounding per operation"""
+    o, w = out5.cpu().numpy(), np.asarray(w5, np.float32)
+    K, H, _, B = o.shape
+    J = np.zeros((K, B), np.float32)
+    rows = [r for r in range(5) if w[r] != 0]
+    for t in range(H if rows else 0):
+        s = None
+        for r in rows:
+            term = o[:, t, r] * w[r]
+            s = term if s is None else s + term
+        J = J + s
+    assert J.dtype == np.float32
+    return J
+
+
+def candidate_tapes(m, tape, K, seed):
+    """K tapes next to `tape` [H, B, 2]: candidate 0 is the tape itself, the others seeded perturbations (some beyond the +-1.05 clip)"""
+    torch = m.torch
+    g = torch.Generator(device='cuda').manual_seed(seed)
+    out = [tape]
+    for k in range(1, K):
+        out.append(tape * (1.0 - 0.2 * k) + 0.4 * torch.randn(tape.shape, device='cuda', generator=g))
+    return torch.stack(out).contiguous()
+
+
+def check_against_the_tape_kernel(m, obs0, tapes, ri, pid, what, w5=None):
+    """every candidate's out5 == eb_rollout_tape's on (obs0, tapes[k]); cost == the header's order over the returned out5, and within
+    rounding of mpc.cost_from_out5"""
+    from env_build_amd.mpc import cost_from_out5
+    o5, J = m.t_cand(obs0, tapes, ri, 0, None, pid, False, w5)
+    for k in range(tapes.shape[0]):
+        f5, _ = m.t_forward_tape(obs0, tapes[k], ri, pid)
+        assert same(o5[k], f5), '%s: candidate %d differs from eb_rollout_tape in %d of %d words' % (
+            what, k, int((bits(o5[k]) != bits(f5)).sum()), f5.numel())
+    if w5 is not None:
+        want = cost_in_the_headers_order(o5, w5)
+        got = J.cpu().numpy()
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), '%s: cost differs from the stated order, weights %s' % (what, w5)
+        ref = np.stack([cost_from_out5(o5[k], w5).cpu().numpy() for k in range(tapes.shape[0])])
+        assert np.allclose(got, ref, rtol=1e-5, atol=5e-6 * float(np.abs(w5).sum())), '%s: cost vs cost_from_out5, weights %s' % (what, w5)
+        if not any(w5):
+            assert not got.any() and not np.signbit(got).any()            # all weights zero: +0
+    return o5, J
+
+
+@pytest.mark.parametrize('task', TASKS)
+@pytest.mark.parametrize('mode', ['training', 'selecting'])
+def test_every_candidate_has_the_bits_of_the_tape_kernel(task, mode):
+    """n_veh in {native, 16, 32, 64} x H in {1, 5, 25} x n_future in {0, 2} x K in {1, 2, 3, 4, the reported limit}; batches that leave
+    idle lanes in the last block; actions beyond +-1.05; out-of-range ref_idx (synthetic_case)"""
+    n = 0
+    for n_veh in (NATIVE[task], 16, 32, 64):
+        for nf in (0, 2):
+            m = CandModel(task, n_veh=n_veh, n_future=nf, mode=mode)
+            limit = m.cand_max(25)
+            assert limit >= (8 if n_veh <= 32 else 4) and m.cand_max(128) == limit
+            for H in (1, 5, 25):
+                B = 211 if n_veh < 64 else 77           # not a multiple of any tile: a last block with idle env lanes
+                obs0, tape, ri, pid, _g, _g5 = synthetic_case(m, task, B, H, seed=100 * n_veh + 10 * nf + H)
+                for K in sorted({1, 2, 3, 4, limit}):
+                    tapes = candidate_tapes(m, tape, K, seed=K)
+                    assert bool((tapes.abs() > 1.05).any())
+                    o5, _ = check_against_the_tape_kernel(m, obs0, tapes, ri, pid, '%s %s N%d nf%d H%d K%d' % (task, mode, n_veh, nf, H, K),
+                                                          WEIGHTS[n % len(WEIGHTS)])
+                    assert bool(o5[:, :, 1].abs().sum() > 0)
+                    n += 1
+    assert n >= 24 * 5
+
+
+@pytest.mark.parametrize('task', TASKS)
+@pytest.mark.parametrize('mode', ['training', 'selecting'])
+def test_crowded_remote_and_near_wall_scenes_in_every_tile_shape(task, mode):
+    """32 and 64 slots, every vehicle within 4.5 m of its ego (every (record, candidate) pair in the near queue: the queue of a tile is
+    full), a third of the egos off the closest-point cell grid, a third on the lane's walls (edge_synthetic_case), with the batch sizes
+    that make the launch pick each of its tile shapes (tc_pick_tile: 32, 16 or 8 envs per block, E * K <= 64), each batch leaving idle
+    lanes in its last block"""
+    import torch
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    n = 0
+    for n_veh in (32, 64):
+        m = CandModel(task, n_veh=n_veh, n_future=0, mode=mode)
+        limit = m.cand_max()
+        for E, K in ((32, 2), (16, 2), (16, 3), (16, 4), (8, 3), (8, limit)):
+            if E * n_veh > 1024 or E * K * n_veh * 22 > 65536:
+                continue
+            B = 2 * n_cu * E + 11 if E > 8 else 211
+            H = 5 if E > 8 else 25
+            obs0, tape, ri, pid, _g, _g5 = edge_synthetic_case(m, task, B, H, seed=1000 * n_veh + E + K)
+            tapes = candidate_tapes(m, tape, K, seed=E)
+            o5, _ = check_against_the_tape_kernel(m, obs0, tapes, ri, pid, '%s %s N%d E%d K%d B%d' % (task, mode, n_veh, E, K, B), WEIGHTS[n % 4])
+            assert bool((o5[0, 0, 3] > 0).all())          # every row has circle pairs below 2.5 m at the first step
+            n += 1
+    assert n == 9
+
+
+@pytest.mark.parametrize('task', TASKS)
+def test_the_edge_chains_as_candidates(task):
+    """the G18 chains (tests/_grad_cases.py: starts on the junction's exit side and next to the entry lane's walls) as candidate 1 of 3"""
+    for c in edge_cases(task)[1]:
+        m = CandModel(task, n_veh=c.n_veh, n_future=c.n_future, mode=c.mode)
+        ri = None if c.ref_idx() is None else m.to_dev(c.ref_idx(), np.int32)
+        tape = m.to_dev(c['tape'])
+        tapes = candidate_tapes(m, tape, 3, seed=18)[[1, 0, 2]].contiguous()
+        check_against_the_tape_kernel(m, m.to_dev(c['obs0']), tapes, ri, c.path_id, 'g18 %s %s' % (task, c.name), WEIGHTS[0])
+
+
+def test_large_batch_every_row_and_candidate():
+    """65 536 x 32 x 25 x 3: every row's and candidate's bits; a second launch repeats them"""
+    m = CandModel('left', n_veh=32, n_future=0, mode='training')
+    obs0, tape, ri, pid, _g, _g5 = synthetic_case(m, 'left', 65536, 25, seed=7)
+    tapes = candidate_tapes(m, tape, 3, seed=7)
+    o5, J = check_against_the_tape_kernel(m, obs0, tapes, ri, pid, '65536 x 32 x 25 x 3', WEIGHTS[0])
+    o5b, Jb = m.t_cand(obs0, tapes, ri, 0, None, pid, False, WEIGHTS[0])
+    assert same(o5, o5b) and same(J, Jb)
+
+
+def retracked_rows(model, obs0, nf, ref_idx=None):
+    """obs0 with its tracking columns replaced through ReferencePath.tracking_error_vector_batched (eb_tracking_error) for ref_idx
+    [B] (training) or the model's current path (selecting)"""
+    trk = model.ref_path.tracking_error_vector_batched(obs0[:, 3].contiguous(), obs0[:, 4].contiguous(), obs0[:, 5].contiguous(),
+                                                       obs0[:, 0].contiguous(), nf, ref_indexes=ref_idx)
+    rows = obs0.clone()
+    rows[:, 6:9 + 3 * nf] = _unwrap(trk)
+    return rows
+
+
+@pytest.mark.parametrize('task', TASKS)
+@pytest.mark.parametrize('mode', ['training', 'selecting'])
+def test_per_candidate_paths_with_retrack(task, mode):
+    """[K, B] ref_idx (training, with out-of-range ids) and path_ids (selecting) with retrack=True, against eb_rollout_tape on rows
+    whose tracking columns were replaced for that candidate's path.  obs0's own tracking columns are NaN: retrack reads none of them."""
+    import torch
+    from env_build_amd.cand import rollout_tape_candidates
+    from env_build_amd.dynamics_and_models import EnvironmentModel
+    for n_veh, nf in ((None, 0), (16, 2), (64, 0)):
+        model = EnvironmentModel(task, nf, mode=mode, n_veh=n_veh)
+        tm = CandModel(task, n_veh=model.veh_num, n_future=nf, mode=mode)
+        B, H, K = 203, 25, 4
+        obs0, tape, _ri, _pid, _g, _g5 = synthetic_case(tm, task, B, H, seed=31 + nf)
+        tapes = candidate_tapes(tm, tape, K, seed=5)
+        shared = obs0.clone()
+        shared[:, 6:9 + 3 * nf] = float('nan')
+        if mode == 'training':
+            g = torch.Generator(device='cuda').manual_seed(2)
+            ri = torch.randint(0, 3, (K, B), device='cuda', generator=g, dtype=torch.int32)
+            ri[1, ::9], ri[3, ::13] = 5, -1                # out of range: zero tracking (DAM:342, 352)
+            out5, cost = rollout_tape_candidates(model, shared, tapes, ref_indexes=ri, retrack=True, weights=WEIGHTS[0])
+        else:
+            ids = [2, 0, 1, 2]
+            out5, cost = rollout_tape_candidates(model, shared, tapes, path_indexes=ids, retrack=True, weights=WEIGHTS[0])
+        assert bool(torch.isfinite(out5).all())
+        for k in range(K):
+            if mode == 'training':
+                rows = retracked_rows(model, obs0, nf, ri[k].contiguous())
+                model.reset(rows, ri[k].contiguous())
+            else:
+                model.ref_path.set_path(ids[k])
+                rows = retracked_rows(model, obs0, nf)
+                model.add_traj(rows, ids[k])
+            _final, want = model.rollout_tape(tapes[k])
+            assert same(out5[k], _unwrap(want)), '%s %s N%d nf%d: candidate %d' % (task, mode, model.veh_num, nf, k)
+        assert np.array_equal(cost.cpu().numpy().view(np.uint32), cost_in_the_headers_order(out5, WEIGHTS[0]).view(np.uint32))
+        if mode == 'training':
+            # without retrack the [K, B] ids only choose the path the LATER steps track: obs0's columns are used as they are
+            plain, _ = rollout_tape_candidates(model, obs0, tapes, ref_indexes=ri)
+            for k in range(K):
+                model.reset(obs0, ri[k].contiguous())
+                _final, want = model.rollout_tape(tapes[k])
+                assert same(plain[k], _unwrap(want))
+
+
+def test_independence():
+    """a permuted batch gives permuted bits, a slice the slice; permuting the candidates permutes the outputs; two launches repeat
+    their bits; a candidate's bits do not depend on its neighbours in the set (NaN tapes next to it)"""
+    import torch
+    m = CandModel('right', n_veh=16, n_future=2, mode='training')
+    B, H, K = 300, 25, 4
+    obs0, tape, ri, pid, _g, _g5 = synthetic_case(m, 'right', B, H, seed=3)
+    tapes = candidate_tapes(m, tape, K, seed=3)
+    w5 = WEIGHTS[3]
+    full = m.t_cand(obs0, tapes, ri, 0, None, pid, False, w5)
+    again = m.t_cand(obs0, tapes, ri, 0, None, pid, False, w5)
+    assert same(full[0], again[0]) and same(full[1], again[1])
+    perm = torch.randperm(B, device='cuda', generator=torch.Generator(device='cuda').manual_seed(1))
+    p = m.t_cand(obs0[perm].contiguous(), tapes[:, :, perm].contiguous(), ri[perm].contiguous(), 0, None, pid, False, w5)
+    assert same(p[0], full[0][:, :, :, perm]) and same(p[1], full[1][:, perm])
+    for first, n in ((0, 1), (77, 1), (5, 63), (100, 200)):
+        s = slice(first, first + n)
+        q = m.t_cand(obs0[s].contiguous(), tapes[:, :, s].contiguous(), ri[s].contiguous(), 0, None, pid, False, w5)
+        assert same(q[0], full[0][:, :, :, s]) and same(q[1], full[1][:, s]), 'slice %d+%d' % (first, n)
+    order = [2, 0, 3, 1]
+    c = m.t_cand(obs0, tapes[order].contiguous(), ri, 0, None, pid, False, w5)
+    assert same(c[0], full[0][order]) and same(c[1], full[1][order])
+    for k in range(K):                                    # alone among NaN tapes, and alone in a set of one
+        lonely = torch.full_like(tapes, float('nan'))
+        lonely[k] = tapes[k]
+        a = m.t_cand(obs0, lonely, ri, 0, None, pid, False, w5)
+        one = m.t_cand(obs0, tapes[k:k + 1].contiguous(), ri, 0, None, pid, False, w5)
+        assert same(a[0][k], full[0][k]) and same(a[1][k], full[1][k]) and same(one[0][0], full[0][k]) and same(one[1][0], full[1][k])
+    # the cost alone, out5 alone: the same bits
+    only_cost = m.t_cand(obs0, tapes, ri, 0, None, pid, False, w5, out5=False)
+    only_out5 = m.t_cand(obs0, tapes, ri, 0, None, pid, False, None)
+    assert only_cost[0] is None and same(only_cost[1], full[1]) and only_out5[1] is None and same(only_out5[0], full[0])
+    # ref_ld = B with K copies of the ids == one shared array
+    shared = m.t_cand(obs0, tapes, ri.view(1, B).expand(K, B).contiguous(), B, None, pid, False, w5)
+    assert same(shared[0], full[0]) and same(shared[1], full[1])
+
+
+G5 = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(GOLDEN, 'g5_rollout_*.npz')))
+
+
+@pytest.mark.parametrize('name', G5)
+def test_reference_rollouts_as_one_of_three_candidates(name):
+    """Every g5 fixture (obs0, actions [25, B, 2], ref_idx, out5 [25, 5, B] from the reference's own code): its tape replayed as one
+    of K = 3 candidates, in each of the three positions, next to perturbed copies, meets the tolerance the oracle's 25-step replay is
+    held to (tests/test_oracle_golden.py: RTOL 1e-5 + ATOL['g5_closed_loop'] 5e-6) on every row: 0 rows excluded."""
+    _, _, task, N, mode, nf = name.split('_')
+    g = golden(name)
+    m = CandModel(task, n_veh=int(N[1:]), n_future=int(nf[2:]), mode=mode, modes=[str(v) for v in g['modes']])
+    obs0, tape = m.to_dev(g['obs0']), m.to_dev(g['actions'])
+    ri = m.to_dev(g['ref_idx'], np.int32) if mode == 'training' else None
+    assert len(G5) >= 6 and g['out5'].shape == (tape.shape[0], 5, obs0.shape[0])
+    others = candidate_tapes(m, tape, 3, seed=55)
+    for pos in range(3):
+        order = [1, 2]
+        order.insert(pos, 0)
+        o5, _ = m.t_cand(obs0, others[order].contiguous(), ri, 0, None, 1, False, None)
+        close(o5[pos].cpu().numpy(), g['out5'], CK.RTOL, CK.ATOL['g5_closed_loop'], 'GPU G5 closed loop x25 as candidate %d of 3: out5' % pos)
+
+
+def test_refusals_and_chunks():
+    import torch
+    from env_build_amd.cand import rollout_tape_candidates, tape_cand_max
+    from env_build_amd.dynamics_and_models import EnvironmentModel
+    m = CandModel('left', n_veh=64, n_future=0, mode='training')
+    limit = m.cand_max()
+    assert 4 <= limit <= 8
+    B, H = 40, 5
+    obs0, tape, ri, pid, _g, _g5 = synthetic_case(m, 'left', B, H, seed=1)
+    tapes = candidate_tapes(m, tape, limit + 3, seed=1)
+    with pytest.raises(ValueError) as e:                                   # over the limit: EB_EINVAL, the limit in the message
+        m.t_cand(obs0, tapes, ri, 0, None, pid, False, None)
+    assert str(limit) in str(e.value) and 'candidates' in str(e.value)
+    m.t_cand(obs0, tapes[:limit].contiguous(), ri, 0, None, pid, False, None)      # at the limit it runs
+    with pytest.raises(ValueError):                                        # nothing asked for
+        m.t_cand(obs0, tapes[:2].contiguous(), ri, 0, None, pid, False, None, out5=False)
+    with pytest.raises(ValueError):                                        # cost without w5
+        m.t_cand(obs0, tapes[:2].contiguous(), ri, 0, None, pid, False, None, cost=True)
+    for ld in (1, B - 1, -1):                                              # ref_ld between 1 and n_env - 1 (and negative)
+        with pytest.raises(ValueError):
+            m.t_cand(obs0, tapes[:2].contiguous(), ri.view(1, B).expand(2, B).contiguous(), ld, None, pid, False, None)
+    with pytest.raises(ValueError) as e:                                   # training mode without ref_idx
+        m.t_cand(obs0, tapes[:2].contiguous(), None, 0, None, pid, False, None)
+    assert 'ref_idx' in str(e.value)
+    with pytest.raises(ValueError):                                        # horizon beyond 128
+        m.t_cand(obs0, torch.zeros((1, 129, B, 2), device='cuda'), ri, 0, None, pid, False, None)
+    sel = CandModel('left', n_veh=8, n_future=0, mode='selecting')
+    o8, t8, _ri, _pid, _g, _g5 = synthetic_case(sel, 'left', B, H, seed=2)
+    with pytest.raises(ValueError):                                        # a path id out of range in selecting mode
+        sel.t_cand(o8, candidate_tapes(sel, t8, 2, seed=1), None, 0, [0, 3], 0, False, None)
+    with pytest.raises(ValueError):
+        sel.t_cand(o8, candidate_tapes(sel, t8, 2, seed=1), None, 0, None, 7, False, None)
+    # n_env == 0 and n_cand == 0: no-ops that succeed
+    m.api.rollout_tape_cand(m.h, 0, 3, 5, None, None, None, 0, None, 0, 0, None, None, None, m.stream)
+    m.api.rollout_tape_cand(m.h, 8, 0, 5, None, None, None, 0, None, 0, 0, None, None, None, m.stream)
+    # the facade evaluates a set beyond the limit in chunks: the bits of the per-chunk launches
+    model = EnvironmentModel('left', 0, mode='training', n_veh=64)
+    assert tape_cand_max(model, H) == limit
+    out5, cost = rollout_tape_candidates(model, obs0, tapes, ref_indexes=ri, weights=WEIGHTS[0])
+    assert out5.shape == (limit + 3, H, 5, B) and cost.shape == (limit + 3, B)
+    a = m.t_cand(obs0, tapes[:limit].contiguous(), ri, 0, None, pid, False, WEIGHTS[0])
+    b = m.t_cand(obs0, tapes[limit:].contiguous(), ri, 0, None, pid, False, WEIGHTS[0])
+    assert same(out5, torch.cat([a[0], b[0]])) and same(cost, torch.cat([a[1], b[1]]))
+    with pytest.raises(_capi.EbError):                                     # fp16 state has no candidate form
+        rollout_tape_candidates(EnvironmentModel('left', 0, mode='training', state_dtype='float16'), obs0, tapes)
+    with pytest.raises(ValueError):
+        rollout_tape_candidates(model, obs0, tapes, ref_indexes=ri, want_out5=False)
+
+
+# ---- the solver ----
+@pytest.mark.parametrize('task', TASKS)
+def test_fused_line_search_has_the_bits_of_the_default_solver(task):
+    """On the G17 start states: u, J, J_history, accepted bit for bit; launches == 1 + 2 * iterations; and the agreement rule of
+    tests/test_gpu_mpc.py restated for the fused solver: at most one quarter of a file's rows may have J > J_ref + 0.1 (0.1 is the
+    reference optimiser's own stopping tolerance, mpc/main.py:558), and the count equals the default solver's (measured on an MI355X
+    for the default solver: 2 of 9, 2 of 16, 3 of 16)."""
+    import torch
+    from env_build_amd.mpc import OpenLoopMPC
+    z, model, mpc, obs0, ref = mpc_setup(task)
+    fused = OpenLoopMPC(model, horizon=int(z['horizon']), fused_line_search=True)
+    assert mpc.fused_line_search is False
+    u, J, info = mpc.solve(obs0, ref_indexes=ref)
+    uf, Jf, inf = fused.solve(obs0, ref_indexes=ref)
+    assert same(u, uf) and same(J, Jf) and same(info['J_history'], inf['J_history']) and torch.equal(info['accepted'], inf['accepted'])
+    assert bool(torch.isfinite(Jf).all())
+    assert inf['launches_per_iteration'] == 2 and inf['launches'] == 1 + 2 * inf['iterations'] and inf['iterations'] == info['iterations']
+    assert info['launches'] == 1 + 4 * info['iterations']
+    B = obs0.shape[0]
+    disagree = int((Jf.double().cpu().numpy() > z['J_ref'] + 0.1).sum())
+    default = int((J.double().cpu().numpy() > z['J_ref'] + 0.1).sum())
+    print('g17 %s fused line search: %d of %d rows disagree (default solver: %d, reference alone: %d)'
+          % (task, disagree, B, default, int((~z['ref_alone_ok']).sum())))
+    assert 4 * disagree <= B and disagree == default
+
+
+@pytest.mark.parametrize('task', TASKS)
+@pytest.mark.parametrize('fused', [False, True])
+def test_k_start_solve(task, fused):
+    """K = 3 starts (zero tape, a seeded random tape, the warm start of a 10-iteration solve): J_history[0] is, bit for bit, the minimum
+    over the starts of their independently evaluated cost; J never increases; the final J <= J(0)"""
+    import torch
+    from env_build_amd.mpc import OpenLoopMPC
+    z, model, mpc0, obs0, ref = mpc_setup(task)
+    H, B = int(z['horizon']), obs0.shape[0]
+    mpc = OpenLoopMPC(model, horizon=H, iterations=15, fused_line_search=fused)
+    u10, _J10, _ = mpc0.solve(obs0, ref_indexes=ref, iterations=10)
+    g = torch.Generator(device='cuda').manual_seed(4)
+    starts = torch.stack([torch.zeros_like(u10), torch.rand(u10.shape, device='cuda', generator=g) * 2.0 - 1.0, mpc.warm_start(u10)])
+    alone = torch.stack([mpc.value_and_grad(obs0, starts[k].contiguous(), ref, 0, need_grad=False)[0] for k in range(3)])
+    first = mpc.launches
+    u, J, info = mpc.solve(obs0, ref_indexes=ref, u_init=starts)
+    hist = info['J_history']
+    best = torch.minimum(torch.minimum(alone[0], alone[1]), alone[2])
+    assert same(hist[0], best)
+    idx = info['start_index']
+    assert idx.shape == (B,) and same(alone.gather(0, idx.view(1, B))[0], best)
+    assert bool(((alone < best.view(1, B)).sum(0) == 0).all()) and bool((idx.cpu() == (alone == best.view(1, B)).int().cpu().argmax(0)).all())
+    assert bool((hist[1:] <= hist[:-1]).all()) and same(hist[-1], J) and bool((J <= hist[0]).all())
+    assert bool((J <= info['J_history'][0]).all()) and float(u.abs().max()) <= 1.0
+    zero_cost = alone[0]
+    assert bool((J <= zero_cost).all())                                    # no worse than the solve's own zero-tape start
+    assert mpc.launches - first == info['launches'] == 2 + info['iterations'] * info['launches_per_iteration']
+
+
+@pytest.mark.parametrize('task', TASKS)
+@pytest.mark.parametrize('mode', ['training', 'selecting'])
+def test_select_path(task, mode):
+    import torch
+    from env_build_amd.cand import rollout_tape_candidates
+    from env_build_amd.dynamics_and_models import EnvironmentModel
+    from env_build_amd.mpc import OpenLoopMPC
+    model = EnvironmentModel(task, 0, mode=mode)
+    tm = CandModel(task, n_veh=model.veh_num, n_future=0, mode=mode)
+    B, H = 150, 25
+    obs0, tape, _ri, _pid, _g, _g5 = synthetic_case(tm, task, B, H, seed=9)
+    mpc = OpenLoopMPC(model, horizon=H)
+    P = len(model.ref_path.path_list)
+    assert P == 3
+    for tapes in (None, candidate_tapes(tm, tape, P, seed=9)):
+        first = mpc.launches
+        J, best = mpc.select_path(obs0, tapes)
+        assert mpc.launches == first + 1 and J.shape == (P, B) and best.shape == (B,)
+        U = torch.zeros((P, H, B, 2), device='cuda') if tapes is None else tapes
+        if mode == 'training':
+            ri = torch.arange(P, dtype=torch.int32, device='cuda').view(P, 1).expand(P, B).contiguous()
+            _o, want = rollout_tape_candidates(model, obs0, U, ref_indexes=ri, retrack=True, weights=mpc.weights, want_out5=False)
+        else:
+            _o, want = rollout_tape_candidates(model, obs0, U, path_indexes=[0, 1, 2], retrack=True, weights=mpc.weights, want_out5=False)
+        assert same(J, want) and bool(torch.isfinite(J).all())
+        lowest = J.min(0).values
+        assert bool((J.gather(0, best.view(1, B))[0] == lowest).all())
+        assert bool((best.cpu() == (J == lowest.view(1, B)).int().cpu().argmax(0)).all())       # the first minimum
+    assert len(set(best.tolist())) > 1                                      # the paths do compete
+
+
+def test_candidates_example_runs_a_few_control_steps():
+    spec = importlib.util.spec_from_file_location('mpc_candidates', os.path.join(ROOT, 'examples', 'mpc_candidates.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    r = mod.run(n_env=128, control_steps=3, iterations=8)
+    import torch
+    assert torch.isfinite(r['J_first']).all() and bool((r['J_first'] <= r['J0_first']).all())
+    assert bool((r['J_first'] < r['J0_first']).any()) and torch.isfinite(r['reward_sum']).all()
+    assert torch.isfinite(r['J_last']).all() and bool((r['J_last'] <= r['J0_last']).all())
+    # a first solve from the zero tape (1 + 8 * 2), then two solves with one launch for the two starts in front (1 + 1 + 8 * 2)
+    assert r['launches'] == (1 + 8 * 2) + 2 * (2 + 8 * 2)
