@@ -158,6 +158,17 @@ CAND_PROTOTYPES = {
     'eb_rollout_tape_cand_max': (C.c_int, [_P, _I, C.POINTER(C.c_int32)]),
 }
 
+# include/envbuild_cand_grad.h: value AND gradient of K candidate tapes per env.  A fourth table with a version of its own, bound on
+# first use like the other two (the HIP library exports the symbols; the CPU oracle does not).
+EB_CAND_GRAD_ABI_VERSION = 1
+CAND_GRAD_PROTOTYPES = {
+    'eb_cand_grad_abi_version': (C.c_int, []),
+    # (h, n_env, n_cand, horizon, obs0, action_tapes, ref_idx, ref_ld, path_ids (host), path_id, retrack, w5 (host), out5_steps, cost,
+    #  g_obs0, g_action_tapes, stream)
+    'eb_rollout_tape_cand_vjp': (C.c_int, [_P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    'eb_rollout_tape_cand_vjp_max': (C.c_int, [_P, _I, C.POINTER(C.c_int32)]),
+}
+
 
 class EbError(RuntimeError):
     pass
@@ -216,6 +227,26 @@ class CApi(object):
                 raise EbError('%s: candidate ABI version %d, expected %d' % (self.path, v, EB_CAND_ABI_VERSION))
         return fns[symbol]
 
+    def cand_grad_fn(self, symbol):
+        """The raw ctypes function of one include/envbuild_cand_grad.h entry, bound on first use; EbError when this library has no
+        candidate-tape gradient."""
+        fns = self.__dict__.setdefault('_cand_grad_fns', {})
+        if not fns:
+            missing = [n for n in CAND_GRAD_PROTOTYPES if not hasattr(self.lib, n)]
+            if missing:
+                raise EbError('%s (backend %r) does not export %s: this library has no candidate-tape gradient '
+                              '(include/envbuild_cand_grad.h is implemented by the HIP library only; rebuild an older one)'
+                              % (self.path, self.backend, ', '.join(missing)))
+            for n, (res, args) in CAND_GRAD_PROTOTYPES.items():
+                fn = getattr(self.lib, n)
+                fn.restype, fn.argtypes = res, args
+                fns[n] = fn
+            if fns['eb_cand_grad_abi_version']() != EB_CAND_GRAD_ABI_VERSION:
+                v = fns['eb_cand_grad_abi_version']()
+                fns.clear()
+                raise EbError('%s: candidate-gradient ABI version %d, expected %d' % (self.path, v, EB_CAND_GRAD_ABI_VERSION))
+        return fns[symbol]
+
     def check(self, rc):
         if rc != 0:
             msg = self.lib.eb_last_error()
@@ -263,7 +294,7 @@ class CApi(object):
         # eb_xxx(...) with return-code checking: api.rollout_step(h, ...)
         sym = 'eb_' + name
         fn = (self.grad_fn(sym) if sym in GRAD_PROTOTYPES else self.cand_fn(sym) if sym in CAND_PROTOTYPES
-              else getattr(self.lib, sym))
+              else self.cand_grad_fn(sym) if sym in CAND_GRAD_PROTOTYPES else getattr(self.lib, sym))
 
         def call(*args):
             self.check(fn(*args))

@@ -20,6 +20,8 @@
 #include "../../include/envbuild_cand.h"
 #include "../../include/envbuild_grad.h"
 #include "eb_cand.h"
+#include "../../include/envbuild_cand_grad.h"
+#include "eb_cand_grad.h"
 #include "eb_grad.h"
 #include "eb_kernels.h"
 
@@ -1851,6 +1853,31 @@ int eb_rollout_tape_vjp(eb_handle h, int32_t n_env, int32_t horizon, const float
 
 }  // extern "C"
 
+// the launch arguments both candidate entries share, after their checks
+static eb::TapeCandArgs cand_args(eb_handle h, int32_t n_env, int32_t n_cand, int32_t horizon, const float* obs0, const float* action_tapes,
+                                  const int32_t* ref_idx, int32_t ref_ld, int32_t retrack, unsigned path_bits, const float* w5,
+                                  float* out5_steps, float* cost) {
+    const bool training = h->cfg.mode == EB_MODE_TRAINING;
+    eb::TapeCandArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.obs0 = obs0; A.tapes = action_tapes; A.ref_idx = training ? ref_idx : nullptr;
+    for (int k = 0; k < 5; ++k) A.w5[k] = w5 ? w5[k] : 0.0f;
+    A.out5_steps = out5_steps; A.cost = cost;
+    A.dt = h->d_pt;
+    A.xy10 = reinterpret_cast<const float*>(h->d_red_all);
+    A.phi10 = h->d_phi10_all;
+    A.rad_all = h->d_rad_all;
+    A.cells = h->d_cells;
+    A.gx0 = h->pt.gx0; A.gy0 = h->pt.gy0; A.gnx = h->pt.gnx; A.gny = h->pt.gny;
+    for (int k = 0; k < 3; ++k) { A.red_off[k] = h->red_off[k]; A.red_len[k] = h->pt.red_len[k]; }
+    A.n_paths = h->pt.n_paths;
+    A.n_env = n_env; A.n_cand = n_cand; A.obs_dim = obs_dim(h->cfg); A.n_veh = h->cfg.n_veh; A.nd = A.obs_dim - 4 * A.n_veh;
+    A.horizon = horizon;
+    A.ref_ld = ref_ld; A.training = training; A.retrack = retrack != 0;
+    A.path_bits = path_bits;
+    return A;
+}
+
 // ---- include/envbuild_cand.h: K candidate tapes per env from one shared scene (eb_rollout_tape_cand.hip) ----
 extern "C" {
 
@@ -1894,24 +1921,62 @@ int eb_rollout_tape_cand(eb_handle h, int32_t n_env, int32_t n_cand, int32_t hor
         }
     }
     EB_HIP(hipSetDevice(h->cfg.device));
-    eb::TapeCandArgs A;
-    std::memset(&A, 0, sizeof A);
-    A.obs0 = obs0; A.tapes = action_tapes; A.ref_idx = training ? ref_idx : nullptr;
-    for (int k = 0; k < 5; ++k) A.w5[k] = w5 ? w5[k] : 0.0f;
-    A.out5_steps = out5_steps; A.cost = cost;
-    A.dt = h->d_pt;
-    A.xy10 = reinterpret_cast<const float*>(h->d_red_all);
-    A.phi10 = h->d_phi10_all;
-    A.rad_all = h->d_rad_all;
-    A.cells = h->d_cells;
-    A.gx0 = h->pt.gx0; A.gy0 = h->pt.gy0; A.gnx = h->pt.gnx; A.gny = h->pt.gny;
-    for (int k = 0; k < 3; ++k) { A.red_off[k] = h->red_off[k]; A.red_len[k] = h->pt.red_len[k]; }
-    A.n_paths = h->pt.n_paths;
-    A.n_env = n_env; A.n_cand = n_cand; A.obs_dim = obs_dim(h->cfg); A.n_veh = h->cfg.n_veh; A.nd = A.obs_dim - 4 * A.n_veh;
-    A.horizon = horizon;
-    A.ref_ld = ref_ld; A.training = training; A.retrack = retrack != 0;
-    A.path_bits = path_bits;
+    const eb::TapeCandArgs A = cand_args(h, n_env, n_cand, horizon, obs0, action_tapes, ref_idx, ref_ld, retrack, path_bits, w5, out5_steps, cost);
     EB_HIP(eb::launch_rollout_tape_cand(h->cfg.task, A, h->n_cu, (hipStream_t)stream));
+    return EB_OK;
+}
+
+}  // extern "C"
+
+// ---- include/envbuild_cand_grad.h: value and gradient of K candidate tapes per env (eb_rollout_tape_cand_vjp.hip) ----
+extern "C" {
+
+int eb_cand_grad_abi_version(void) { return EB_CAND_GRAD_ABI_VERSION; }
+
+int eb_rollout_tape_cand_vjp_max(eb_handle h, int32_t horizon, int32_t* max_cand) {
+    if (!h || !max_cand || horizon < 1 || horizon > eb::TC_MAX_HORIZON) return fail(EB_EINVAL, "eb_rollout_tape_cand_vjp_max: bad argument");
+    *max_cand = eb::rollout_tape_cand_vjp_max(h->cfg.n_veh, horizon);
+    return EB_OK;
+}
+
+int eb_rollout_tape_cand_vjp(eb_handle h, int32_t n_env, int32_t n_cand, int32_t horizon, const float* obs0, const float* action_tapes,
+                             const int32_t* ref_idx, int32_t ref_ld, const int32_t* path_ids, int32_t path_id, int32_t retrack,
+                             const float* w5, float* out5_steps, float* cost, float* g_obs0, float* g_action_tapes, void* stream) {
+    if (h && (n_env == 0 || n_cand == 0)) return EB_OK;
+    int rc = check_paths(h, "eb_rollout_tape_cand_vjp: null handle");
+    if (rc) return rc;
+    rc = check_modes(h);
+    if (rc) return rc;
+    if (n_env < 0 || n_cand < 0 || horizon < 1 || horizon > eb::TC_MAX_HORIZON || !obs0 || !action_tapes)
+        return fail(EB_EINVAL, "eb_rollout_tape_cand_vjp: bad argument");
+    if (!g_action_tapes)
+        return fail(EB_EINVAL, "eb_rollout_tape_cand_vjp: g_action_tapes is required; the value-only form is eb_rollout_tape_cand "
+                               "(include/envbuild_cand.h)");
+    if (!w5) return fail(EB_EINVAL, "eb_rollout_tape_cand_vjp: w5 is required (the weights of cost and the cotangent of out5)");
+    const int limit = eb::rollout_tape_cand_vjp_max(h->cfg.n_veh, horizon);
+    if (n_cand > limit) {
+        char msg[256];
+        std::snprintf(msg, sizeof msg, "eb_rollout_tape_cand_vjp: %d candidates exceed the kernel's limit of %d for %d vehicle slots and "
+                                       "%d steps (eb_rollout_tape_cand_vjp_max): evaluate the set in chunks",
+                      (int)n_cand, limit, (int)h->cfg.n_veh, (int)horizon);
+        return fail(EB_EINVAL, msg);
+    }
+    unsigned path_bits = 0u;
+    if (h->cfg.mode == EB_MODE_TRAINING) {
+        if (!ref_idx) return fail(EB_EINVAL, "training mode needs ref_idx (EnvironmentModel.reset(obses, ref_indexes))");
+        if (ref_ld < 0 || (ref_ld > 0 && ref_ld < n_env)) return fail(EB_EINVAL, "eb_rollout_tape_cand_vjp: ref_ld must be 0 or at least n_env");
+    } else {
+        for (int k = 0; k < n_cand; ++k) {
+            const int p = path_ids ? path_ids[k] : path_id;
+            if (p < 0 || p >= h->pt.n_paths) return fail(EB_EINVAL, "bad path_id");
+            path_bits |= (unsigned)p << (2 * k);                                // n_paths <= 3, n_cand <= 8
+        }
+    }
+    EB_HIP(hipSetDevice(h->cfg.device));
+    eb::TapeCandVjpArgs A;
+    A.F = cand_args(h, n_env, n_cand, horizon, obs0, action_tapes, ref_idx, ref_ld, retrack, path_bits, w5, out5_steps, cost);
+    A.g_obs0 = g_obs0; A.g_tapes = g_action_tapes;
+    EB_HIP(eb::launch_rollout_tape_cand_vjp(h->cfg.task, A, h->n_cu, (hipStream_t)stream));
     return EB_OK;
 }
 

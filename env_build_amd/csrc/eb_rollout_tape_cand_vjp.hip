@@ -1,0 +1,355 @@
+// eb_rollout_tape_cand_vjp.hip — value AND gradient of K candidate action tapes per env (eb_rollout_tape_cand_vjp) in ONE launch, gfx950.
+//
+// eb_rollout_tape_cand.hip scores K tapes from one shared scene; a caller that wants to IMPROVE them (the starts of a multi-start
+// solver, one tape per path of the task) needs K gradients from that scene.  This kernel is that file's forward with what
+// eb_rollout_tape_vjp.hip adds to its own: a block of 256 threads owns E consecutive envs (E = 32, 16 or 8; E * K <= 64) for the
+// whole horizon,
+//
+//   records    every lane keeps up to RPT 16-byte (env, vehicle) records in registers and advances them ONCE per step, whatever K is
+//              (the vehicles do not depend on the ego: DAM:195, 331, 402);
+//   env role   lane c < E * K of wave 0 is (env = c mod E, candidate = c / E): its own copy of the row's first nine columns;
+//   per step t   (A) the env role publishes its pose (x, y, sin, cos) to LDS;
+//              (B) every lane tests its records against the K poses of the record's env; a near record (6.31 m, DAM:228) goes into
+//                  the block's queue as an (env, candidate, slot) entry; then the lane predicts its records;
+//              (C) waves 1..3 take the queue, one entry per thread: the penalty terms (DAM:218-229) and, scaled by the step's two
+//                  penalty cotangents — w5[1] and w5[2] + w5[3], known at launch — the record's three ego partials (x, y, heading);
+//                  meanwhile the env role runs the env's own forward chain;
+//              (D) the env role sums penalties and partials in SLOT order per (env, candidate), writes the step's out5, adds the
+//                  step's weighted sum to its cost and leaves the 12 floats of grad::TapeStep in the LDS tape;
+//   reverse    after the last step every env-role lane runs grad::tape_reverse (eb_tape_grad_device.h) on its own tape: up to 64
+//              lanes of the wave instead of the E <= 32 of eb_rollout_tape_vjp.hip, at the same instruction time.
+//
+// Forward arithmetic and order are those of eb_rollout_tape_cand.hip (out5, cost) and of the gradient form of
+// eb_rollout_tape_vjp.hip (partials, tape), restated here as those files restate eb_rollout.hip's; the reverse is the shared device
+// function fed the same values.  tests/test_gpu_cand_grad.py holds every output to those entries bit for bit.  The queue's order
+// varies from run to run; the sums do not.  A (row, candidate)'s bits depend on nothing but the row and that candidate's tape and
+// path.  No atomics to global memory, no scratch; fp32 state only.
+#include <hip/hip_runtime.h>
+
+#include "eb_cand_grad.h"
+#include "eb_tape_grad_device.h"
+
+namespace eb {
+namespace {
+
+constexpr int CG_THREADS = 256;
+constexpr int CG_ENV_LANES = 64;                        // the env role is wave 0
+constexpr int CG_TAPE_FLOATS = 12;                      // floats per (env, candidate, step) in the LDS tape
+constexpr size_t CG_LDS_BUDGET = 64 * 1024;             // dynamic LDS per block: two blocks per CU at least
+constexpr int CG_RPT_MAX = 4;                           // records a lane keeps in registers: a tile holds at most 1024
+typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));
+
+struct CgSmem {
+    float4 ego[CG_ENV_LANES];             // x, y, sin phi, cos phi of the pre-step pose of (env, candidate)
+    unsigned long long mask[CG_ENV_LANES];   // per (env, candidate): slots with a near record
+    unsigned char turn[64];               // TURN_* per slot
+    int count;                            // entries in the near-record queue
+};
+// dynamic LDS: [tape: 12 x horizon x (E * K) floats] [queue: E * K * n_veh float4] [2.5 m sums: E * K * n_veh floats]
+// [queue position of every (env, candidate, slot): 16 bits]
+inline size_t cg_tape_bytes(int E, int K, int horizon) { return (size_t)CG_TAPE_FLOATS * horizon * E * K * sizeof(float); }
+inline size_t cg_lds_bytes(int E, int K, int n_veh, int horizon) {
+    return cg_tape_bytes(E, K, horizon) + (size_t)E * K * n_veh * (sizeof(float4) + sizeof(float) + sizeof(unsigned short));
+}
+
+// closest point of (px, py) on path p: eb_rollout.hip:closest_cell_index<0, false>, restated (DAM:702-715)
+__device__ __forceinline__ int cg_closest(const TapeCandArgs& A, int p, int roff, float px, float py, float& rx, float& ry, float& rphi) {
+    const float* xy = A.xy10 + 2 * roff;
+    const float* ph = A.phi10 + roff;
+    const float fx = (px - A.gx0) * CELL_INV, fy = (py - A.gy0) * CELL_INV;
+    unsigned c = 0xffffffffu;
+    if (fx >= 0.0f && fx < (float)A.gnx && fy >= 0.0f && fy < (float)A.gny) c = A.cells[(p * A.gny + (int)fy) * A.gnx + (int)fx];
+    if (c == 0xffffffffu) {                                                    // off the corridor's grid: the pruned full search
+        const int n = p == 0 ? A.red_len[0] : p == 1 ? A.red_len[1] : A.red_len[2];
+        const int bi = closest_reduced_index(reinterpret_cast<const float2*>(xy), A.rad_all + 32 * p, n, px, py, 0, 1 << 30);
+        rx = xy[2 * bi]; ry = xy[2 * bi + 1]; rphi = ph[bi];
+        return bi;
+    }
+    return closest_in_range<0>(xy, ph, (int)(c & 0xffffu), (int)(c >> 16), px, py, rx, ry, rphi);
+}
+
+template <int TASK, int RPT>
+__global__ __launch_bounds__(CG_THREADS, 3) void rollout_tape_cand_vjp_kernel(const TapeCandVjpArgs AA) {
+    __shared__ CgSmem S;
+    extern __shared__ __align__(16) unsigned char cg_dyn[];
+    const TapeCandArgs& A = AA.F;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int E = A.envs_per_tile, K = A.n_cand, NV = A.n_veh, D = A.obs_dim, nd = A.nd, H = A.horizon;
+    const int EK = E * K;
+    const int e0 = blockIdx.x * E, nE = min(E, A.n_env - e0), items = nE * NV;
+    const size_t n = (size_t)A.n_env;
+    // (read once, up front: a select between a global load and a member of the argument block would put the block in scratch)
+    const float w5_0 = A.w5[0], w5_1 = A.w5[1], w5_2 = A.w5[2], w5_3 = A.w5[3], w5_4 = A.w5[4];
+    const float w35 = w5_1, w25 = w5_2 + w5_3;                                 // DAM:299-300 and veh2veh4real itself
+    float* const tapeL = reinterpret_cast<float*>(cg_dyn);                      // [12][H][E * K]
+    unsigned char* const qbase = cg_dyn + (size_t)CG_TAPE_FLOATS * H * EK * sizeof(float);   // a multiple of 16 bytes: E >= 8
+    float4* const queue = reinterpret_cast<float4*>(qbase);
+    float* const q25 = reinterpret_cast<float*>(qbase + (size_t)EK * NV * sizeof(float4));
+    unsigned short* const qpos = reinterpret_cast<unsigned short*>(qbase + (size_t)EK * NV * (sizeof(float4) + sizeof(float)));
+
+    // ---- the block's records: item = k * 256 + tid -> (env, slot); requested before anything else ----
+    f4u rec[RPT];
+    int where[RPT];                                      // env | slot << 8 of record k
+#pragma unroll
+    for (int k = 0; k < RPT; ++k) {
+        const int item = k * CG_THREADS + tid;
+        const bool valid = item < items;
+        const int env = valid ? item / NV : 0, slot = valid ? item - env * NV : 0;
+        where[k] = env | slot << 8;
+        rec[k] = *reinterpret_cast<const f4u*>(A.obs0 + (size_t)(e0 + env) * D + nd + 4 * slot);
+        if (!valid) rec[k].x = 1e30f;                    // never near an ego, never predicted
+    }
+    if (tid < 64) S.turn[tid] = A.dt->turn[tid];
+    const SinCosK SK = sincos_consts();
+
+    // ---- the env role's state: lane c = candidate * E + env ----
+    const bool env_lane = tid < EK;                      // E * K <= 64: wave 0
+    const int my_env = tid & (E - 1), my_cand = env_lane ? tid / E : 0;        // E is a power of two
+    const bool act = env_lane && my_env < nE;
+    const int ge = e0 + (act ? my_env : 0);              // idle lanes shadow the tile's first env (in bounds), store nothing
+    float st[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, trk[3] = {0.0f, 0.0f, 0.0f};
+    int p = -1, roff = 0;
+    f2u araw = f2u{0.0f, 0.0f};
+    const size_t tape_off = 2 * ((size_t)my_cand * H * n + ge);                // of this lane's tape and of its gradient
+    const float* const my_tape = A.tapes + tape_off;
+    if (env_lane) {
+        const float* o = A.obs0 + (size_t)ge * D;
+        const f4u h0 = *reinterpret_cast<const f4u*>(o), h1 = *reinterpret_cast<const f4u*>(o + 4);
+        st[0] = h0.x; st[1] = h0.y; st[2] = h0.z; st[3] = h0.w; st[4] = h1.x; st[5] = h1.y;
+        trk[0] = h1.z; trk[1] = h1.w; trk[2] = o[8];
+        p = (int)((A.path_bits >> (2 * my_cand)) & 3u);
+        if (A.training) {
+            const int pr = A.ref_idx[(size_t)my_cand * A.ref_ld + ge];
+            p = (pr >= 0 && pr < A.n_paths) ? pr : -1;                          // DAM:342, 352
+        }
+        roff = p == 1 ? A.red_off[1] : p == 2 ? A.red_off[2] : A.red_off[0];
+        araw = *reinterpret_cast<const f2u*>(my_tape);
+        if (A.retrack) {                                 // the row's own pose on this candidate's path (DAM:735-760; the reference
+            float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;       // builds one obs per path, hier_decision.py:113-117)
+            if (p >= 0) {
+                float rx = 0.0f, ry = 0.0f, rphi = 0.0f;
+                cg_closest(A, p, roff, st[3], st[4], rx, ry, rphi);
+                t0 = two2one<TASK>(st[3], st[4], rx, ry);                       // DAM:758
+                t1 = deal_with_phi_diff(st[5] - rphi);                          // DAM:759
+                t2 = st[0] - EXP_V;                                             // DAM:760
+            }
+            trk[0] = t0; trk[1] = t1; trk[2] = t2;
+        }
+    }
+    float hv[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    float J = 0.0f;
+
+    for (int t = 0; t < H; ++t) {
+        // ---- (A) env role: the pose ----
+        float es = 0.0f, ec = 0.0f, phi_rad = 0.0f;
+        f2u araw_next = araw;
+        if (env_lane) {
+            if (t + 1 < H) araw_next = *reinterpret_cast<const f2u*>(my_tape + 2 * (size_t)(t + 1) * n);   // prefetch
+            phi_rad = deg2rad(st[5]);
+            sincos_det(phi_rad, es, ec);                                        // DAM:211 and DAM:79-80
+            S.ego[tid] = make_float4(st[3], st[4], es, ec);
+            S.mask[tid] = 0ull;
+            if (tid == 0) S.count = 0;
+        }
+        __syncthreads();
+
+        // ---- (B) near records into the queue, candidate by candidate; then the prediction ----
+#pragma unroll
+        for (int k = 0; k < RPT; ++k) {
+            if (k * CG_THREADS >= items) break;                                 // block-uniform
+            const int env = where[k] & 255, slot = where[k] >> 8;
+            for (int c = 0; c < K; ++c) {
+                const int cell = c * E + env;                                   // < E * K
+                const float2 eg = *reinterpret_cast<const float2*>(&S.ego[cell]);
+                const bool near = grad::record_near(eg.x, eg.y, rec[k].x, rec[k].y);
+                const unsigned long long b = __ballot(near);
+                if (b != 0ull) {                         // wave-uniform; every lane of the wave is here
+                    int base = 0;
+                    if (lane == 0) base = atomicAdd(&S.count, __popcll(b));     // an LDS add: one per wave, pass and candidate
+                    base = __builtin_amdgcn_readfirstlane(base);
+                    if (near) {
+                        const int pos = base + __popcll(b & ((1ull << lane) - 1ull));   // < nE * K * n_veh: one entry per (record, candidate) at most
+                        const int idx = cell * NV + slot;                       // < E * K * n_veh: inside qpos
+                        queue[pos] = make_float4(rec[k].x, rec[k].y, rec[k].w, __int_as_float(idx));
+                        qpos[idx] = (unsigned short)pos;
+                        atomicOr(&S.mask[cell], 1ull << slot);                  // LDS
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < RPT; ++k) {
+            if (k * CG_THREADS + tid < items) {
+                float sn_, cs_;
+                rec[k] = predict_record_tc<float>(rec[k], turn_consts(S.turn[where[k] >> 8]), SK, sn_, cs_);
+            }
+            __builtin_amdgcn_sched_barrier(0);           // one record at a time: interleaved, their temporaries would all be live
+        }
+        __syncthreads();
+
+        // ---- (C) waves 1..3: the queue, one entry per thread | the env role: the env's own forward chain ----
+        float rew = 0.0f, road_t = 0.0f, road_r = 0.0f;
+        if (tid >= CG_ENV_LANES) {
+            const int cnt = S.count;
+            for (int q = tid - CG_ENV_LANES; q < cnt; q += CG_THREADS - CG_ENV_LANES) {
+                const float4 e = queue[q];
+                const int cell = __float_as_int(e.w) / NV;
+                const float4 eg = S.ego[cell];
+                float vs, vc;
+                sincos_det(deg2rad(e.z), vs, vc);                               // DAM:221
+                float t35[4], t25[4];
+                const float4 pts = make_float4(eg.x + LWS * eg.w, eg.y + LWS * eg.z, eg.x - LWS * eg.w, eg.y - LWS * eg.z);
+                veh2veh_terms(pts, e.x, e.y, vs, vc, t35, t25);                 // DAM:218-229
+                const float p35 = ((t35[0] + t35[1]) + t35[2]) + t35[3];
+                const float p25 = ((t25[0] + t25[1]) + t25[2]) + t25[3];
+                float px = 0.0f, py = 0.0f, pphi = 0.0f;
+                grad::record_partials(eg.x, eg.y, eg.z, eg.w, e.x, e.y, vs, vc, w35, w25, px, py, pphi);
+                queue[q] = make_float4(px, py, pphi, p35);
+                q25[q] = p25;
+            }
+        } else if (env_lane) {
+            float steer, a_x;
+            action_transform(araw.x, araw.y, steer, a_x);                       // DAM:120
+            const float punish_steer = -sq(steer), punish_a_x = -sq(a_x);       // DAM:198-199
+            const float punish_yaw_rate = -sq(st[2]);                           // DAM:202
+            const float devi_y = -sq(trk[0]);                                   // DAM:205
+            const float devi_phi = -sq(deg2rad(trk[1]));                        // DAM:206
+            const float devi_v = -sq(trk[2]);                                   // DAM:207
+            rew = 0.05f * devi_v + 0.8f * devi_y + 30.0f * devi_phi + 0.02f * punish_yaw_rate + 5.0f * punish_steer +
+                  0.05f * punish_a_x;                                           // DAM:297-298
+            float nx[6];
+            f_xu_core(st, steer, a_x, TAU10, phi_rad, es, ec, nx);              // DAM:387
+            nx[0] = __builtin_fminf(__builtin_fmaxf(nx[0], 0.0f), 35.0f);       // DAM:390
+            float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;
+            if (p >= 0) {                                                       // DAM:334-353
+                float rx = 0.0f, ry = 0.0f, rphi = 0.0f;
+                cg_closest(A, p, roff, nx[3], nx[4], rx, ry, rphi);
+                t0 = two2one<TASK>(nx[3], nx[4], rx, ry);                       // DAM:758
+                t1 = deal_with_phi_diff(nx[5] - rphi);                          // DAM:759
+                t2 = nx[0] - EXP_V;                                             // DAM:760
+            }
+#pragma unroll
+            for (int c = 0; c < 6; ++c) hv[c] = nx[c];
+            hv[6] = t0; hv[7] = t1; hv[8] = t2;
+            road_terms<TASK>(st[3] + LWS * ec, st[4] + LWS * es, road_t, road_r);   // DAM:231-295
+            road_terms<TASK>(st[3] - LWS * ec, st[4] - LWS * es, road_t, road_r);
+        }
+        __syncthreads();
+
+        // ---- (D) env role: sums in slot order, the step's outputs, the cost, the tape ----
+        if (env_lane) {
+            float a35 = 0.0f, a25 = 0.0f, px = 0.0f, py = 0.0f, pphi = 0.0f;
+            for (unsigned long long m = S.mask[tid]; m; m &= m - 1ull) {        // slot order: the same sum wherever the row sits
+                const int q = qpos[tid * NV + (__ffsll((long long)m) - 1)];
+                const float4 r = queue[q];
+                a35 += r.w; a25 += q25[q];                                      // DAM:218-229: far records add exact zeros
+                px += r.x; py += r.y; pphi += r.z;
+            }
+            const float o1 = a35 + road_t, o2 = a25 + road_r;                   // DAM:299-300
+            if (act && A.out5_steps) {
+                float* out5 = A.out5_steps + ((size_t)my_cand * H + t) * 5 * n + ge;
+                out5[0] = rew;
+                out5[n] = o1;
+                out5[2 * n] = o2;
+                out5[3 * n] = a25;
+                out5[4 * n] = road_r;
+            }
+            // s_t: the rows with a non-zero weight, in row order; J: ascending t from +0 (include/envbuild_cand.h)
+            float s = 0.0f;
+            bool any = false;
+            if (w5_0 != 0.0f) { s = rew * w5_0; any = true; }
+            if (w5_1 != 0.0f) { const float v = o1 * w5_1; s = any ? s + v : v; any = true; }
+            if (w5_2 != 0.0f) { const float v = o2 * w5_2; s = any ? s + v : v; any = true; }
+            if (w5_3 != 0.0f) { const float v = a25 * w5_3; s = any ? s + v : v; any = true; }
+            if (w5_4 != 0.0f) { const float v = road_r * w5_4; s = any ? s + v : v; any = true; }
+            if (any) J += s;
+            {
+                float* T = tapeL + (size_t)t * EK + tid;                        // tid < E * K, t < H: inside the tape
+                const size_t cs = (size_t)H * EK;
+#pragma unroll
+                for (int c = 0; c < 6; ++c) T[c * cs] = st[c];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) T[(6 + c) * cs] = trk[c];
+                T[9 * cs] = px; T[10 * cs] = py; T[11 * cs] = pphi;
+            }
+#pragma unroll
+            for (int c = 0; c < 6; ++c) st[c] = hv[c];
+            trk[0] = hv[6]; trk[1] = hv[7]; trk[2] = hv[8];
+            araw = araw_next;
+        }
+        // (the next step's (A) writes ego / mask / count, which (D) of this step is through with in program order on the env
+        //  role; the other waves are past their last read of them since the barrier above)
+    }
+    if (!act) return;
+    if (A.cost) A.cost[(size_t)my_cand * n + ge] = J;
+
+    // ---- the reverse sweep: every (env, candidate) lane on its own tape, out of LDS (each lane reads what it wrote itself) ----
+    const float g_final[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // no cotangent of the final obs in this entry
+    const size_t cs = (size_t)H * EK;
+    float* const my_g = AA.g_tapes + tape_off;
+    const float* const mine = tapeL + tid;
+    auto load = [=](int t, grad::TapeStep& T) {
+        const float* L = mine + (size_t)t * EK;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) T.st[c] = L[c * cs];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) T.trk[c] = L[(6 + c) * cs];
+        T.px = L[9 * cs]; T.py = L[10 * cs]; T.pphi = L[11 * cs];
+        const f2u a = *reinterpret_cast<const f2u*>(my_tape + 2 * (size_t)t * n);
+        T.a0 = a.x; T.a1 = a.y;
+        T.w[0] = w5_0; T.w[1] = w5_1; T.w[2] = w5_2; T.w[3] = w5_3; T.w[4] = w5_4;
+    };
+    auto store = [=](int t, const float (&ga)[2]) {
+        *reinterpret_cast<f2u*>(my_g + 2 * (size_t)t * n) = f2u{ga[0], ga[1]};
+    };
+    float go[9];
+    grad::tape_reverse<TASK>(H, p >= 0, g_final, 0.0f, 0.0f, 0.0f, load, store, go);
+    if (AA.g_obs0) {
+        float* gi = AA.g_obs0 + ((size_t)my_cand * n + ge) * nd;
+        *reinterpret_cast<f4u*>(gi) = f4u{go[0], go[1], go[2], go[3]};
+        *reinterpret_cast<f4u*>(gi + 4) = f4u{go[4], go[5], go[6], go[7]};
+        gi[8] = go[8];
+        for (int c = 9; c < nd; ++c) gi[c] = 0.0f;       // the pre-step look-ahead columns feed nothing (DAM:189-207, 322-333)
+    }
+}
+
+// the tile: the most envs per block (32, 16, 8) whose (env, candidate) lanes fit one wave, whose LDS fits the budget and whose grid
+// still gives every CU two blocks
+int cg_pick_tile(int n_env, int n_cand, int n_veh, int horizon, int n_cu) {
+    int fit = 0;
+    for (int E = 32; E >= 8; E >>= 1) {
+        if (E * n_cand > CG_ENV_LANES || E * n_veh > CG_THREADS * CG_RPT_MAX || cg_lds_bytes(E, n_cand, n_veh, horizon) > CG_LDS_BUDGET)
+            continue;
+        if (!fit) fit = E;
+        if ((n_env + E - 1) / E >= 2 * n_cu) return E;
+    }
+    return fit ? 8 : 0;
+}
+
+}  // namespace
+
+int rollout_tape_cand_vjp_max(int n_veh, int horizon) {
+    const size_t k = CG_LDS_BUDGET / cg_lds_bytes(8, 1, n_veh < 1 ? 1 : n_veh, horizon < 1 ? 1 : horizon);
+    return (int)(k < (size_t)TC_MAX_CAND ? k : (size_t)TC_MAX_CAND);
+}
+
+hipError_t launch_rollout_tape_cand_vjp(int task, const TapeCandVjpArgs& A_in, int n_cu, hipStream_t s) {
+    if (A_in.F.n_env <= 0 || A_in.F.n_cand <= 0) return hipSuccess;
+    TapeCandVjpArgs A = A_in;
+    TapeCandArgs& F = A.F;
+    F.envs_per_tile = cg_pick_tile(F.n_env, F.n_cand, F.n_veh, F.horizon, n_cu);
+    if (F.envs_per_tile == 0) return hipErrorInvalidValue;      // beyond rollout_tape_cand_vjp_max: refused by the caller before
+    const int grid = (F.n_env + F.envs_per_tile - 1) / F.envs_per_tile;
+    const size_t lds = cg_lds_bytes(F.envs_per_tile, F.n_cand, F.n_veh, F.horizon);
+    const bool small = F.envs_per_tile * F.n_veh <= 2 * CG_THREADS;
+    const int dev = current_device_index();
+    const hipError_t e = with_task(task, [&](auto t) {
+        return with_bool(small, [&](auto sm) {
+            constexpr int RPT = decltype(sm)::value ? 2 : CG_RPT_MAX;
+            return launch_lds<rollout_tape_cand_vjp_kernel<decltype(t)::value, RPT>>(dim3(grid), dim3(CG_THREADS), lds, dev, s, A);
+        });
+    });
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
+}  // namespace eb

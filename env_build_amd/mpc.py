@@ -22,6 +22,16 @@ vehicle records advance once for all trials): 2 launches per iteration, the same
     u0 = mpc.warm_start(u)                             # the tape shifted by one step: next control step's u_init
     u, J, info = mpc.solve(obses, ref_indexes=ref, u_init=torch.stack([u0, torch.zeros_like(u0)]))   # K starts: the best one per env
     J_paths, best = mpc.select_path(obses)             # the model cost of every path of the task (hier_decision.py:113-121)
+
+Multi-start.  The cost is non-convex (collision discs), so a descent ends in the basin it starts in.  solve(..., u_init=[K, H, B, 2],
+starts='all') runs EVERY start through all iterations and returns, per env, the one with the lowest final cost; solve_paths does the
+same with one start per path of the task, candidate p on path p (the model-cost twin of hier_decision.py:113-121 with a tape
+optimised per path).  The K gradients of an iteration are ONE eb_rollout_tape_cand_vjp launch (include/envbuild_cand_grad.h) and a
+line-search trial of the K starts ONE eb_rollout_tape_cand launch, both from the shared scene: ls_trials + 1 launches per iteration
+whatever K is, up to the launch limits (cand.tape_cand_grad_max, cand.tape_cand_max); see OpenLoopMPC.launch_count.
+
+    u, J, info = mpc.solve(obses, ref_indexes=ref, u_init=starts, starts='all')   # info['J_starts'] [K, B], info['start_index'] [B]
+    u, J, info = mpc.solve_paths(obses)                # info['path_index'] [B], info['J_paths'] [P, B], info['u_paths'] [P, H, B, 2]
 """
 import ctypes as C
 
@@ -74,22 +84,26 @@ def projected_gradient(evaluate, u, iterations, ls_trials=3, c1=1e-4, shrink=0.2
                        tol=1e-3, evaluate_many=None):
     """min J(u) over the box [-1, 1] for a batch of independent problems.
         evaluate(u [H, B, 2], need_grad) -> (J [B], g [H, B, 2] or None)
+    or, with a leading start dimension, K * B independent problems, each with its own step length, Armijo state and BB proposal:
+        evaluate(U [K, H, B, 2], need_grad) -> (J [K, B], g [K, H, B, 2] or None)
+    (J_history is then [iterations + 1, K, B], accepted [iterations, K, B]; the reduced dimensions are counted from the end, so the
+    [H, B, 2] form runs the lines it always ran).
     Tensors of any float dtype and device (the GPU solver runs it in float32 on the device, the fixture generator in float64 on the
     CPU: the same lines).  -> (u, J, info); info: J_history [iterations + 1, B] (J after every iteration: accepted steps only, so it
     never increases), accepted [iterations, B], iterations (done), evaluations.
-        evaluate_many(U [K, H, B, 2]) -> J [K, B]   (optional)
+        evaluate_many(U [T, H, B, 2]) -> J [T, B]   (optional; with a start dimension U [T, K, H, B, 2] -> J [T, K, B])
     With it the ls_trials trial tapes of an iteration are formed up front — their step lengths a, a shrink, (a shrink) shrink, ... by
     repeated multiplication, as the sequential loop forms them for an env that has not accepted yet — scored by ONE call and accepted
     by the same rule in trial order.  A trial after an env's accepted one is scored and ignored (sequentially it would have been
     scored at the accepted step length and ignored), so u, J, J_history and accepted are those of the sequential loop bit for bit
     whenever evaluate_many(U)[k] == evaluate(U[k], False)[0]."""
-    def env(v):
-        return v.view(1, -1, 1)
+    def env(v):                                                      # [B] -> [1, B, 1]; [K, B] -> [K, 1, B, 1]
+        return v.unsqueeze(-1).unsqueeze(-3)
     u = u.clamp(-1.0, 1.0)
     J, g = evaluate(u, True)
     n_eval = 1
     # first step: no env moves an action by more than 1 (half the box)
-    alpha = (1.0 / g.abs().amax((0, 2)).clamp_min(1e-12)).clamp(alpha_min, alpha_max)
+    alpha = (1.0 / g.abs().amax((-3, -1)).clamp_min(1e-12)).clamp(alpha_min, alpha_max)
     hist, acc = [J], []
     done_iters = 0
     U = None
@@ -99,7 +113,7 @@ def projected_gradient(evaluate, u, iterations, ls_trials=3, c1=1e-4, shrink=0.2
         done = torch.zeros_like(J, dtype=torch.bool)
         J_many = None
         if evaluate_many is not None:
-            if U is None:                                            # the trial tapes' buffer [K, H, B, 2]: one for the whole solve
+            if U is None:                                            # the trial tapes' buffer [T, ...]: one for the whole solve
                 U = torch.empty((ls_trials,) + tuple(u.shape), dtype=u.dtype, device=u.device)
             steps = [a]
             for k in range(ls_trials):
@@ -114,7 +128,7 @@ def projected_gradient(evaluate, u, iterations, ls_trials=3, c1=1e-4, shrink=0.2
             else:
                 u_try, J_try = tries[k], J_many[k]
             n_eval += 1
-            slope = ((u_try - u) * g).sum((0, 2))                    # <= 0: the projected step is a descent direction
+            slope = ((u_try - u) * g).sum((-3, -1))                   # <= 0: the projected step is a descent direction
             ok = (J_try <= J + c1 * slope) & ~done                   # a NaN cost is a rejection
             u_new = torch.where(env(ok), u_try, u_new)
             J_new = torch.where(ok, J_try, J_new)
@@ -123,7 +137,7 @@ def projected_gradient(evaluate, u, iterations, ls_trials=3, c1=1e-4, shrink=0.2
         _J, g_new = evaluate(u_new, True)                            # the same bits as J_new: value-only == the full form's forward
         n_eval += 1
         s, y = u_new - u, g_new - g
-        ss, sy = (s * s).sum((0, 2)), (s * y).sum((0, 2))
+        ss, sy = (s * s).sum((-3, -1)), (s * y).sum((-3, -1))
         bb = torch.where(sy > 0, ss / sy.clamp_min(1e-30), a * 4.0)  # BB1; non-positive curvature along s: lengthen
         alpha = torch.where(done, bb, a).clamp(alpha_min, alpha_max)  # a rejected env goes on from its shortened step
         u, J, g = u_new, J_new, g_new
@@ -186,6 +200,85 @@ class OpenLoopMPC(object):
         self.launches += launches
         return torch.stack([cost_from_out5(out5[k], self.weights) for k in range(U.shape[0])])
 
+    def _many(self, obs, U, ri, ids, retrack, need_grad):
+        """Cost (and gradient) of N tapes U [N, H, B, 2] from the shared rows `obs`, tape i on path ri[i] ([N, B]; [B]: one path for
+        all) or ids[i] -> (J [N, B], g [N, H, B, 2] or None).  need_grad: eb_rollout_tape_cand_vjp, else eb_rollout_tape_cand, in
+        chunks of their limits; J is cost_from_out5 per candidate slice of out5_steps — the lines value_and_grad forms it with."""
+        from .cand import launch_chunks, launch_grad_chunks
+        g = None
+        if need_grad:
+            _cost, g, out5, _g_obs, launches = launch_grad_chunks(self.model, obs, U, ri, ids, retrack, self.weights, True, False)
+        else:
+            out5, _cost, launches = launch_chunks(self.model, obs, U, ri, ids, retrack, None, True)
+        self.launches += launches
+        return torch.stack([cost_from_out5(out5[k], self.weights) for k in range(U.shape[0])]), g
+
+    def launch_count(self, n_starts, iterations):
+        """Launches of a solve(starts='all') / solve_paths over n_starts starts that runs `iterations` iterations:
+            G + iterations * (V + G),   G = ceil(K / tape_cand_grad_max),
+            V = ls_trials * ceil(K / tape_cand_max)   or, with fused_line_search,   ceil(K * ls_trials / tape_cand_max)
+        (one gradient evaluation in front, then per iteration the line search's value-only launches and one gradient evaluation).
+        For K up to tape_cand_grad_max that is 1 + iterations * (ls_trials + 1), independent of K."""
+        from .cand import tape_cand_grad_max, tape_cand_max
+        K = int(n_starts)
+        G = -(-K // max(1, tape_cand_grad_max(self.model, self.horizon)))
+        lim = tape_cand_max(self.model, self.horizon)
+        V = -(-K * self.ls_trials // lim) if self.fused_line_search else self.ls_trials * -(-K // lim)
+        return G + int(iterations) * (V + G)
+
+    def _solve_all(self, obs, U0, ri, ids, retrack, iterations, check_every, tol):
+        """every start of U0 [K, H, B, 2] through projected_gradient at once -> (U [K, H, B, 2], J [K, B], info)"""
+        K = U0.shape[0]
+        per_cand = ri is not None and ri.dim() == 2
+
+        def evaluate(U, need_grad):
+            return self._many(obs, U.contiguous(), ri, ids, retrack, need_grad)
+
+        def evaluate_many(UU):                                       # [T, K, H, B, 2]: trial t of start k is candidate t * K + k
+            T = UU.shape[0]
+            J, _g = self._many(obs, UU.reshape((T * K,) + tuple(UU.shape[2:])), ri.repeat(T, 1) if per_cand else ri,
+                               None if ids is None else ids * T, retrack, False)
+            return J.view(T, K, -1)
+        first = self.launches
+        U, J, info = projected_gradient(evaluate, U0, self.iterations if iterations is None else int(iterations),
+                                        ls_trials=self.ls_trials, c1=self.c1, check_every=check_every, tol=tol,
+                                        evaluate_many=evaluate_many if self.fused_line_search else None)
+        info['launches'] = self.launches - first
+        return U, J, info
+
+    @staticmethod
+    def _pick(U, J):
+        """per env the start with the lowest cost (first_minimum) -> (u [H, B, 2], J [B], index [B])"""
+        idx = first_minimum(J)
+        u = U.gather(0, idx.view(1, 1, -1, 1).expand(1, U.shape[1], U.shape[2], 2))[0]
+        return u.contiguous(), J.gather(0, idx.view(1, -1))[0], idx
+
+    def solve_paths(self, obses, u_init=None, iterations=None, check_every=0, tol=1e-3):
+        """One start per path of the task, candidate p on path p from the row's tracking error on THAT path (retrack; the reference
+        builds one obs per path, hier_decision.py:113-117), all optimised together; the best path per env is returned — "optimise a
+        tape per path, then compare" (hier_decision.py:113-121 on the model cost) -> (u [H, B, 2], J [B], info).
+        u_init: None = the zero tapes, or [P, H, B, 2].  info as projected_gradient's with a start dimension, plus path_index [B] (the
+        first minimum; a NaN never wins), J_paths [P, B], u_paths [P, H, B, 2], launches (launch_count(P, iterations)).  The
+        hysteresis of hier_decision.py:121 stays with the caller."""
+        m = self.model
+        obs = self._dev_fn(obses, m.device).detach()
+        if obs.dim() != 2 or obs.shape[1] != m.obs_dim:
+            raise ValueError('obses must be [B, %d]; got %s' % (m.obs_dim, tuple(obs.shape)))
+        P, B = len(m.ref_path.path_list), obs.shape[0]
+        if u_init is None:
+            U0 = torch.zeros((P, self.horizon, B, 2), dtype=torch.float32, device=m.device)
+        else:
+            U0 = self._dev_fn(u_init, m.device).detach()
+            if tuple(U0.shape) != (P, self.horizon, B, 2):
+                raise ValueError('u_init must be [%d, %d, %d, 2]; got %s' % (P, self.horizon, B, tuple(U0.shape)))
+        ri, ids = None, list(range(P))
+        if m.mode == 'training':
+            ri, ids = torch.arange(P, dtype=torch.int32, device=m.device).view(P, 1).expand(P, B).contiguous(), None
+        U, J, info = self._solve_all(obs, U0, ri, ids, True, iterations, check_every, tol)
+        u, J_best, idx = self._pick(U, J)
+        info.update(path_index=idx, J_paths=J, u_paths=U.contiguous())
+        return u, J_best, info
+
     def select_path(self, obses, tapes=None):
         """The model cost of every path of the task from the shared rows `obses` [B, D] — the model-cost twin of
         hier_decision.py:113-121 -> (J [P, B], best [B]: the first minimum).  Candidate p follows path p for every env and starts from
@@ -221,10 +314,16 @@ class OpenLoopMPC(object):
             raise ValueError("OpenLoopMPC.solve: mode='selecting' needs path_index")
         return None, int(path_index)
 
-    def solve(self, obses, ref_indexes=None, path_index=None, u_init=None, iterations=None, check_every=0, tol=1e-3):
+    def solve(self, obses, ref_indexes=None, path_index=None, u_init=None, iterations=None, check_every=0, tol=1e-3, starts='best'):
         """-> (u [H, B, 2] raw actions in [-1, 1], J [B], info).  u_init: None = the zero tape (mpc/main.py:550), or a tape
-        [H, B, 2] (warm_start), or K starts [K, H, B, 2]: they are scored by one eb_rollout_tape_cand launch and every env starts
-        from its lowest-cost one (best_start; info['start_index'] [B]).  info as projected_gradient's, plus `launches`."""
+        [H, B, 2] (warm_start), or K starts [K, H, B, 2].  starts='best' (the default): the K starts are scored by one
+        eb_rollout_tape_cand launch and every env starts ONE descent from its lowest-cost one (best_start; info['start_index'] [B]).
+        starts='all': every start runs through all iterations (one eb_rollout_tape_cand_vjp launch per gradient evaluation of the K
+        starts) and every env gets the start with the lowest FINAL cost — the first minimum, a NaN never wins; info then has
+        J_history [iterations + 1, K, B], accepted [iterations, K, B], J_starts [K, B], start_index [B] and launches ==
+        launch_count(K, iterations).  info otherwise as projected_gradient's, plus `launches`."""
+        if starts not in ('best', 'all'):
+            raise ValueError("starts must be 'best' or 'all'; got %r" % (starts,))
         m = self.model
         obs = self._dev_fn(obses, m.device).detach()
         if obs.dim() != 2 or obs.shape[1] != m.obs_dim:
@@ -237,6 +336,14 @@ class OpenLoopMPC(object):
             u0 = self._dev_fn(u_init, m.device).detach()
             if tuple(u0.shape[-3:]) != (self.horizon, B, 2) or u0.dim() not in (3, 4) or (u0.dim() == 4 and u0.shape[0] < 1):
                 raise ValueError('u_init must be [%d, %d, 2] or [K, %d, %d, 2]; got %s' % (self.horizon, B, self.horizon, B, tuple(u0.shape)))
+        if starts == 'all':
+            if u0.dim() != 4:
+                raise ValueError("starts='all' needs u_init [K, %d, %d, 2]" % (self.horizon, B))
+            U, J_starts, info = self._solve_all(obs, u0, ri, None if ri is not None else [pid] * u0.shape[0], False, iterations,
+                                                check_every, tol)
+            u, J, idx = self._pick(U, J_starts)
+            info.update(J_starts=J_starts, start_index=idx)
+            return u, J, info
         first = self.launches
         start_index = None
         if u0.dim() == 4:
