@@ -169,6 +169,18 @@ CAND_GRAD_PROTOTYPES = {
     'eb_rollout_tape_cand_vjp_max': (C.c_int, [_P, _I, C.POINTER(C.c_int32)]),
 }
 
+# include/envbuild_sample.h: S sampled tapes per env drawn, scored and averaged in one launch.  A fifth table with a version of its
+# own, bound on first use like the others (the HIP library exports the symbols; the CPU oracle does not).
+EB_SAMPLE_ABI_VERSION = 1
+SAMPLE_PROTOTYPES = {
+    'eb_sample_abi_version': (C.c_int, []),
+    # (h, n_env, n_samples, horizon, obs0, nominal, ref_idx, path_id, env_ids, seed, counter, sigma2 (host), beta, inv_lambda, w5 (host),
+    #  cost, best_tape, best_cost, best_index, mean_tape, samples_out, stream)
+    'eb_rollout_tape_sample': (C.c_int, [_P, _I, _I, _I, _P, _P, _P, _I, _P, C.c_uint64, C.c_uint64, _P, C.c_float, C.c_float, _P,
+                                         _P, _P, _P, _P, _P, _P, _P]),
+    'eb_rollout_tape_sample_max': (C.c_int, [_P, _I, C.POINTER(C.c_int32)]),
+}
+
 
 class EbError(RuntimeError):
     pass
@@ -247,6 +259,25 @@ class CApi(object):
                 raise EbError('%s: candidate-gradient ABI version %d, expected %d' % (self.path, v, EB_CAND_GRAD_ABI_VERSION))
         return fns[symbol]
 
+    def sample_fn(self, symbol):
+        """The raw ctypes function of one include/envbuild_sample.h entry, bound on first use; EbError when this library has no
+        sampled-tape rollout."""
+        fns = self.__dict__.setdefault('_sample_fns', {})
+        if not fns:
+            missing = [n for n in SAMPLE_PROTOTYPES if not hasattr(self.lib, n)]
+            if missing:
+                raise EbError('%s (backend %r) does not export %s: this library has no sampled-tape rollout (include/envbuild_sample.h '
+                              'is implemented by the HIP library only; rebuild an older one)' % (self.path, self.backend, ', '.join(missing)))
+            for n, (res, args) in SAMPLE_PROTOTYPES.items():
+                fn = getattr(self.lib, n)
+                fn.restype, fn.argtypes = res, args
+                fns[n] = fn
+            if fns['eb_sample_abi_version']() != EB_SAMPLE_ABI_VERSION:
+                v = fns['eb_sample_abi_version']()
+                fns.clear()
+                raise EbError('%s: sampled-tape ABI version %d, expected %d' % (self.path, v, EB_SAMPLE_ABI_VERSION))
+        return fns[symbol]
+
     def check(self, rc):
         if rc != 0:
             msg = self.lib.eb_last_error()
@@ -294,7 +325,8 @@ class CApi(object):
         # eb_xxx(...) with return-code checking: api.rollout_step(h, ...)
         sym = 'eb_' + name
         fn = (self.grad_fn(sym) if sym in GRAD_PROTOTYPES else self.cand_fn(sym) if sym in CAND_PROTOTYPES
-              else self.cand_grad_fn(sym) if sym in CAND_GRAD_PROTOTYPES else getattr(self.lib, sym))
+              else self.cand_grad_fn(sym) if sym in CAND_GRAD_PROTOTYPES else self.sample_fn(sym) if sym in SAMPLE_PROTOTYPES
+              else getattr(self.lib, sym))
 
         def call(*args):
             self.check(fn(*args))

@@ -22,6 +22,8 @@
 #include "eb_cand.h"
 #include "../../include/envbuild_cand_grad.h"
 #include "eb_cand_grad.h"
+#include "../../include/envbuild_sample.h"
+#include "eb_sample.h"
 #include "eb_grad.h"
 #include "eb_kernels.h"
 
@@ -1977,6 +1979,74 @@ int eb_rollout_tape_cand_vjp(eb_handle h, int32_t n_env, int32_t n_cand, int32_t
     A.F = cand_args(h, n_env, n_cand, horizon, obs0, action_tapes, ref_idx, ref_ld, retrack, path_bits, w5, out5_steps, cost);
     A.g_obs0 = g_obs0; A.g_tapes = g_action_tapes;
     EB_HIP(eb::launch_rollout_tape_cand_vjp(h->cfg.task, A, h->n_cu, (hipStream_t)stream));
+    return EB_OK;
+}
+
+}  // extern "C"
+
+// ---- include/envbuild_sample.h: S sampled tapes per env drawn, scored and averaged in one launch (eb_rollout_tape_sample.hip) ----
+extern "C" {
+
+int eb_sample_abi_version(void) { return EB_SAMPLE_ABI_VERSION; }
+
+int eb_rollout_tape_sample_max(eb_handle h, int32_t horizon, int32_t* max_samples) {
+    if (!h || !max_samples || horizon < 1 || horizon > eb::TS_MAX_HORIZON) return fail(EB_EINVAL, "eb_rollout_tape_sample_max: bad argument");
+    *max_samples = eb::TS_MAX_SAMPLES;
+    return EB_OK;
+}
+
+int eb_rollout_tape_sample(eb_handle h, int32_t n_env, int32_t n_samples, int32_t horizon, const float* obs0, const float* nominal,
+                           const int32_t* ref_idx, int32_t path_id, const int32_t* env_ids, uint64_t seed, uint64_t counter,
+                           const float* sigma2, float beta, float inv_lambda, const float* w5, float* cost, float* best_tape,
+                           float* best_cost, int32_t* best_index, float* mean_tape, float* samples_out, void* stream) {
+    if (h && (n_env == 0 || n_samples == 0)) return EB_OK;
+    int rc = check_paths(h, "eb_rollout_tape_sample: null handle");
+    if (rc) return rc;
+    rc = check_modes(h);
+    if (rc) return rc;
+    if (n_env < 0 || n_samples < 0 || !obs0 || !nominal) return fail(EB_EINVAL, "eb_rollout_tape_sample: bad argument");
+    if (horizon < 1 || horizon > eb::TS_MAX_HORIZON) return fail(EB_EINVAL, "eb_rollout_tape_sample: horizon must be in 1..128");
+    if (!cost && !best_tape && !best_cost && !best_index && !mean_tape && !samples_out)
+        return fail(EB_EINVAL, "eb_rollout_tape_sample: no output is asked for");
+    if (!w5) return fail(EB_EINVAL, "eb_rollout_tape_sample: w5 is required (the weights of cost)");
+    if (!sigma2 || !(sigma2[0] >= 0.0f) || !(sigma2[1] >= 0.0f))
+        return fail(EB_EINVAL, "eb_rollout_tape_sample: sigma2 must be two floats >= 0");
+    if (!(beta >= 0.0f && beta < 1.0f)) return fail(EB_EINVAL, "eb_rollout_tape_sample: beta must be in [0, 1)");
+    if (!(inv_lambda >= 0.0f) || !std::isfinite(inv_lambda)) return fail(EB_EINVAL, "eb_rollout_tape_sample: inv_lambda must be finite and >= 0");
+    if (n_samples > eb::TS_MAX_SAMPLES) {
+        char msg[256];
+        std::snprintf(msg, sizeof msg, "eb_rollout_tape_sample: %d samples exceed the kernel's limit of %d (eb_rollout_tape_sample_max)",
+                      (int)n_samples, eb::TS_MAX_SAMPLES);
+        return fail(EB_EINVAL, msg);
+    }
+    const bool training = h->cfg.mode == EB_MODE_TRAINING;
+    if (training) {
+        if (!ref_idx) return fail(EB_EINVAL, "training mode needs ref_idx (EnvironmentModel.reset(obses, ref_indexes))");
+    } else if (path_id < 0 || path_id >= h->pt.n_paths) {
+        return fail(EB_EINVAL, "bad path_id");
+    }
+    EB_HIP(hipSetDevice(h->cfg.device));
+    eb::TapeSampleArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.obs0 = obs0; A.nominal = nominal; A.ref_idx = training ? ref_idx : nullptr; A.env_ids = env_ids;
+    A.seed = seed; A.counter = counter;
+    A.sigma0 = sigma2[0]; A.sigma1 = sigma2[1]; A.beta = beta; A.inv_lambda = inv_lambda;
+    A.gain = (float)std::sqrt(1.0 - (double)beta * (double)beta);
+    for (int k = 0; k < 5; ++k) A.w5[k] = w5[k];
+    A.cost = cost; A.best_tape = best_tape; A.best_cost = best_cost; A.best_index = best_index; A.mean_tape = mean_tape;
+    A.samples_out = samples_out;
+    A.dt = h->d_pt;
+    A.xy10 = reinterpret_cast<const float*>(h->d_red_all);
+    A.phi10 = h->d_phi10_all;
+    A.rad_all = h->d_rad_all;
+    A.cells = h->d_cells;
+    A.gx0 = h->pt.gx0; A.gy0 = h->pt.gy0; A.gnx = h->pt.gnx; A.gny = h->pt.gny;
+    for (int k = 0; k < 3; ++k) { A.red_off[k] = h->red_off[k]; A.red_len[k] = h->pt.red_len[k]; }
+    A.n_paths = h->pt.n_paths;
+    A.n_env = n_env; A.n_samples = n_samples; A.obs_dim = obs_dim(h->cfg); A.n_veh = h->cfg.n_veh; A.nd = A.obs_dim - 4 * A.n_veh;
+    A.horizon = horizon;
+    A.training = training; A.path_id = training ? 0 : path_id;
+    EB_HIP(eb::launch_rollout_tape_sample(h->cfg.task, A, (hipStream_t)stream));
     return EB_OK;
 }
 

@@ -32,6 +32,15 @@ whatever K is, up to the launch limits (cand.tape_cand_grad_max, cand.tape_cand_
 
     u, J, info = mpc.solve(obses, ref_indexes=ref, u_init=starts, starts='all')   # info['J_starts'] [K, B], info['start_index'] [B]
     u, J, info = mpc.solve_paths(obses)                # info['path_index'] [B], info['J_paths'] [P, B], info['u_paths'] [P, H, B, 2]
+
+Sampling.  SamplingMPC needs no gradient: per iteration ONE eb_rollout_tape_sample launch (include/envbuild_sample.h) draws S
+perturbed tapes per env around the nominal, scores them from the shared scene and returns their soft-min average, which becomes the
+next nominal (MPPI); the lowest-cost tape seen so far is kept per env.  With polish=OpenLoopMPC(...) it is the global stage in front
+of the gradient solver: the sampled tape and the zero tape both descend (starts='all'), so the result is never above the default
+solver's.
+
+    smpc = SamplingMPC(model, horizon=25, n_samples=256)
+    u, J, info = smpc.solve(obses, ref_indexes=ref)    # info['J_history'] [iterations + 1, B], info['counter_next']
 """
 import ctypes as C
 
@@ -39,7 +48,7 @@ import torch
 
 from . import _capi
 
-__all__ = ['OpenLoopMPC', 'cost_from_out5', 'projected_gradient', 'best_start', 'DEFAULT_WEIGHTS']
+__all__ = ['OpenLoopMPC', 'SamplingMPC', 'cost_from_out5', 'projected_gradient', 'sampling_loop', 'best_start', 'DEFAULT_WEIGHTS']
 
 DEFAULT_WEIGHTS = (-1.0, 10.0, 0.0, 0.0, 0.0)
 
@@ -150,6 +159,17 @@ def projected_gradient(evaluate, u, iterations, ls_trials=3, c1=1e-4, shrink=0.2
     info = dict(J_history=torch.stack(hist), accepted=torch.stack(acc) if acc else torch.zeros((0,) + J.shape, dtype=torch.bool),
                 iterations=done_iters, evaluations=n_eval, launches_per_iteration=ls_trials + 1 if evaluate_many is None else 2)
     return u, J, info
+
+
+def _solve_path_args(model, dev_fn, ref_indexes, path_index, who):
+    """the path arguments of a solve -> (ref_idx int32 [B] on the device or None, path id)"""
+    if model.mode == 'training':
+        if ref_indexes is None:
+            raise ValueError("%s: mode='training' needs ref_indexes [B]" % who)
+        return dev_fn(ref_indexes, model.device, torch.int32), 0
+    if path_index is None:
+        raise ValueError("%s: mode='selecting' needs path_index" % who)
+    return None, int(path_index)
 
 
 class OpenLoopMPC(object):
@@ -305,14 +325,7 @@ class OpenLoopMPC(object):
         return J, first_minimum(J)
 
     def _paths(self, ref_indexes, path_index):
-        m = self.model
-        if m.mode == 'training':
-            if ref_indexes is None:
-                raise ValueError("OpenLoopMPC.solve: mode='training' needs ref_indexes [B]")
-            return self._dev_fn(ref_indexes, m.device, torch.int32), 0
-        if path_index is None:
-            raise ValueError("OpenLoopMPC.solve: mode='selecting' needs path_index")
-        return None, int(path_index)
+        return _solve_path_args(self.model, self._dev_fn, ref_indexes, path_index, 'OpenLoopMPC.solve')
 
     def solve(self, obses, ref_indexes=None, path_index=None, u_init=None, iterations=None, check_every=0, tol=1e-3, starts='best'):
         """-> (u [H, B, 2] raw actions in [-1, 1], J [B], info).  u_init: None = the zero tape (mpc/main.py:550), or a tape
@@ -365,3 +378,110 @@ class OpenLoopMPC(object):
         """The tape shifted by one step, its last action repeated: the next control step's u_init (the line mpc/main.py:571 left
         commented out)."""
         return torch.cat([u[1:], u[-1:]], 0).contiguous()
+
+
+def sampling_loop(step, u0, iterations, sigma, sigma_decay=1.0, counter=0):
+    """The MPPI iteration on a batch of independent problems, free of the device:
+        step(nominal [H, B, 2], counter, (sigma_0, sigma_1)) -> (cost0 [B], best_tape [H, B, 2], best_cost [B], mean_tape [H, B, 2])
+    is one sampling step around `nominal` (cost0: the cost of the nominal itself, sample 0).  Per iteration: one step; the nominal
+    becomes mean_tape; the lowest-cost tape seen so far is kept per env with a `where` (elitist; a NaN never replaces anything, so an
+    env whose costs are all NaN keeps its start); the counter advances by one and sigma is multiplied by sigma_decay.  Nothing here
+    reads a value on the host.  -> (u [H, B, 2], J [B], info): J_history [iterations + 1, B] (J_history[0]: the start's cost; it
+    never increases), counter_next."""
+    nominal = u0.clamp(-1.0, 1.0)
+    u_best, J_best = nominal, None
+    sig = (float(sigma[0]), float(sigma[1]))
+    hist = []
+    for it in range(int(iterations)):
+        cost0, best_tape, best_cost, mean_tape = step(nominal, int(counter) + it, sig)
+        if J_best is None:
+            J_best = cost0
+            hist.append(J_best)
+        floor = torch.where(torch.isnan(J_best), torch.full_like(J_best, float('inf')), J_best)
+        better = best_cost < floor                                   # strict; False for a NaN
+        u_best = torch.where(better.view(1, -1, 1), best_tape, u_best)
+        J_best = torch.where(better, best_cost, J_best)
+        hist.append(J_best)
+        nominal = mean_tape
+        sig = (sig[0] * float(sigma_decay), sig[1] * float(sigma_decay))
+    info = dict(J_history=torch.stack(hist) if hist else None, counter_next=int(counter) + int(iterations))
+    return u_best, J_best, info
+
+
+class SamplingMPC(object):
+    """Sampling MPC (MPPI) over `horizon` steps of `model`: n_samples perturbed tapes per env and iteration, one
+    eb_rollout_tape_sample launch each.  sigma: the noise scale per action component (raw actions live in [-1, 1]), multiplied by
+    sigma_decay after every iteration; beta: AR(1) smoothing of the noise over the steps; lam: the soft-min temperature in units of
+    the cost; seed: with solve's `counter` it keys every draw, so a solve repeats its bits.  polish: an OpenLoopMPC on the same
+    model, horizon and weights, or None.  fp32 state only."""
+
+    def __init__(self, model, horizon=25, weights=DEFAULT_WEIGHTS, n_samples=256, iterations=8, sigma=(0.4, 0.4), beta=0.7, lam=1.0,
+                 sigma_decay=0.85, seed=0, polish=None):
+        from .dynamics_and_models import _dev
+        from . import sample as _sample
+        self._dev_fn, self._sample = _dev, _sample
+        if model.state_dtype != torch.float32:
+            raise _capi.EbError('SamplingMPC: fp32 state only')
+        model.api.sample_fn('eb_rollout_tape_sample')                # EbError here when the library has no sampled-tape rollout
+        self.model, self.horizon = model, int(horizon)
+        self.weights = tuple(float(v) for v in weights)
+        if len(self.weights) != 5:
+            raise ValueError('weights: five floats, one per out5 row')
+        self.n_samples, self.iterations = int(n_samples), int(iterations)
+        limit = _sample.tape_sample_max(model, self.horizon)         # ValueError for a horizon outside 1..128
+        if self.n_samples < 1 or self.n_samples > limit:
+            raise ValueError('SamplingMPC: n_samples %d is outside 1..%d (eb_rollout_tape_sample_max)' % (self.n_samples, limit))
+        if self.iterations < 1:
+            raise ValueError('SamplingMPC: at least one iteration')
+        self.sigma = (float(sigma[0]), float(sigma[1]))
+        self.beta, self.lam, self.sigma_decay, self.seed = float(beta), float(lam), float(sigma_decay), int(seed)
+        if not self.lam > 0:
+            raise ValueError('SamplingMPC: lam must be positive')
+        self.polish = polish
+        if polish is not None and (polish.model is not model or polish.horizon != self.horizon or polish.weights != self.weights):
+            raise ValueError('SamplingMPC: polish must be an OpenLoopMPC on the same model, horizon and weights')
+        self._value = OpenLoopMPC(model, horizon=self.horizon, weights=self.weights)      # the independent evaluation of the result
+        self.launches = 0
+
+    def solve(self, obses, ref_indexes=None, path_index=None, u_init=None, counter=0):
+        """-> (u [H, B, 2] raw actions in [-1, 1], J [B], info).  u_init: None = the zero tape, or a tape [H, B, 2] (warm_start).
+        J is cost_from_out5 of ONE independent value-only evaluation of the returned u (the contract of OpenLoopMPC.solve).
+        info: J_history [iterations + 1, B] (the best cost after every iteration, as the sampling kernel formed it: it never
+        increases), J_kernel [B] (= J_history[-1]; it agrees with J to the rounding of the two summation orders), launches
+        (iterations + 1), counter_next (the counter a following solve continues from).  With polish the sampled tape and the zero
+        tape go through polish.solve(u_init=stack([zero, u_sampled]), starts='all') — start 0 is the zero tape on purpose: its
+        descent is the default solver's — and u, J are the polished ones; info then also has u_sampled, J_sampled and `polish`
+        (polish.solve's info), and launches counts both stages."""
+        m = self.model
+        obs = self._dev_fn(obses, m.device).detach()
+        if obs.dim() != 2 or obs.shape[1] != m.obs_dim:
+            raise ValueError('obses must be [B, %d]; got %s' % (m.obs_dim, tuple(obs.shape)))
+        B = obs.shape[0]
+        ri, pid = _solve_path_args(m, self._dev_fn, ref_indexes, path_index, 'SamplingMPC.solve')
+        if u_init is None:
+            u0 = torch.zeros((self.horizon, B, 2), dtype=torch.float32, device=m.device)
+        else:
+            u0 = self._dev_fn(u_init, m.device).detach()
+            if tuple(u0.shape) != (self.horizon, B, 2):
+                raise ValueError('u_init must be [%d, %d, 2]; got %s' % (self.horizon, B, tuple(u0.shape)))
+        inv = 0.0 if self.lam == float('inf') else 1.0 / self.lam
+        first = self.launches
+
+        def step(nominal, cnt, sig):
+            out = self._sample.launch(m, obs, nominal.contiguous(), self.n_samples, self.seed, cnt, sig, self.beta, inv, ri, pid, None,
+                                      self.weights, ('cost', 'best', 'mean'))
+            self.launches += 1
+            return out['cost'][0], out['best_tape'], out['best_cost'], out['mean_tape']
+        u, J_kernel, info = sampling_loop(step, u0, self.iterations, self.sigma, self.sigma_decay, counter)
+        u = u.contiguous()
+        J = self._value.value_and_grad(obs, u, ri, pid, need_grad=False)[0]
+        self.launches += 1
+        info.update(J_kernel=J_kernel, launches=self.launches - first)
+        if self.polish is not None:
+            starts = torch.stack([torch.zeros_like(u), u])
+            up, Jp, pinfo = self.polish.solve(obs, ref_indexes=ri, path_index=None if ri is not None else pid, u_init=starts, starts='all')
+            info.update(u_sampled=u, J_sampled=J, polish=pinfo, launches=info['launches'] + pinfo['launches'])
+            u, J = up, Jp
+        return u, J, info
+
+    warm_start = staticmethod(OpenLoopMPC.warm_start)
