@@ -181,6 +181,17 @@ SAMPLE_PROTOTYPES = {
     'eb_rollout_tape_sample_max': (C.c_int, [_P, _I, C.POINTER(C.c_int32)]),
 }
 
+# include/envbuild_ilqr.h: one iLQR iteration on the model rollout in one launch.  A sixth table with a version of its own, bound on
+# first use like the others (the HIP library exports the symbols; the CPU oracle does not).
+EB_ILQR_ABI_VERSION = 1
+ILQR_PROTOTYPES = {
+    'eb_ilqr_abi_version': (C.c_int, []),
+    # (h, n_env, horizon, n_alpha, obs0, u_nom, x_nom, gains, ref_idx, path_id, alphas (host), mu, w5 (host), cost, best_index,
+    #  best_cost, u_out, x_out, gains_out, dv, cand_out, lq_out, stream)
+    'eb_rollout_tape_ilqr': (C.c_int, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'eb_rollout_tape_ilqr_max': (C.c_int, [_P, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+}
+
 
 class EbError(RuntimeError):
     pass
@@ -278,6 +289,25 @@ class CApi(object):
                 raise EbError('%s: sampled-tape ABI version %d, expected %d' % (self.path, v, EB_SAMPLE_ABI_VERSION))
         return fns[symbol]
 
+    def ilqr_fn(self, symbol):
+        """The raw ctypes function of one include/envbuild_ilqr.h entry, bound on first use; EbError when this library has no
+        iLQR iteration."""
+        fns = self.__dict__.setdefault('_ilqr_fns', {})
+        if not fns:
+            missing = [n for n in ILQR_PROTOTYPES if not hasattr(self.lib, n)]
+            if missing:
+                raise EbError('%s (backend %r) does not export %s: this library has no iLQR iteration (include/envbuild_ilqr.h '
+                              'is implemented by the HIP library only; rebuild an older one)' % (self.path, self.backend, ', '.join(missing)))
+            for n, (res, args) in ILQR_PROTOTYPES.items():
+                fn = getattr(self.lib, n)
+                fn.restype, fn.argtypes = res, args
+                fns[n] = fn
+            if fns['eb_ilqr_abi_version']() != EB_ILQR_ABI_VERSION:
+                v = fns['eb_ilqr_abi_version']()
+                fns.clear()
+                raise EbError('%s: iLQR ABI version %d, expected %d' % (self.path, v, EB_ILQR_ABI_VERSION))
+        return fns[symbol]
+
     def check(self, rc):
         if rc != 0:
             msg = self.lib.eb_last_error()
@@ -326,7 +356,7 @@ class CApi(object):
         sym = 'eb_' + name
         fn = (self.grad_fn(sym) if sym in GRAD_PROTOTYPES else self.cand_fn(sym) if sym in CAND_PROTOTYPES
               else self.cand_grad_fn(sym) if sym in CAND_GRAD_PROTOTYPES else self.sample_fn(sym) if sym in SAMPLE_PROTOTYPES
-              else getattr(self.lib, sym))
+              else self.ilqr_fn(sym) if sym in ILQR_PROTOTYPES else getattr(self.lib, sym))
 
         def call(*args):
             self.check(fn(*args))

@@ -24,6 +24,8 @@
 #include "eb_cand_grad.h"
 #include "../../include/envbuild_sample.h"
 #include "eb_sample.h"
+#include "../../include/envbuild_ilqr.h"
+#include "eb_ilqr.h"
 #include "eb_grad.h"
 #include "eb_kernels.h"
 
@@ -2047,6 +2049,81 @@ int eb_rollout_tape_sample(eb_handle h, int32_t n_env, int32_t n_samples, int32_
     A.horizon = horizon;
     A.training = training; A.path_id = training ? 0 : path_id;
     EB_HIP(eb::launch_rollout_tape_sample(h->cfg.task, A, (hipStream_t)stream));
+    return EB_OK;
+}
+
+}  // extern "C"
+
+// ---- include/envbuild_ilqr.h: one iLQR iteration on the model rollout in one launch (eb_rollout_tape_ilqr.hip) ----
+extern "C" {
+
+int eb_ilqr_abi_version(void) { return EB_ILQR_ABI_VERSION; }
+
+int eb_rollout_tape_ilqr_max(eb_handle h, int32_t horizon, int32_t* max_alpha, int32_t* max_horizon) {
+    (void)horizon;
+    if (!h || !max_alpha || !max_horizon) return fail(EB_EINVAL, "eb_rollout_tape_ilqr_max: bad argument");
+    *max_alpha = eb::IL_MAX_ALPHA;
+    *max_horizon = eb::IL_MAX_HORIZON;
+    return EB_OK;
+}
+
+int eb_rollout_tape_ilqr(eb_handle h, int32_t n_env, int32_t horizon, int32_t n_alpha, const float* obs0, const float* u_nom,
+                         const float* x_nom, const float* gains, const int32_t* ref_idx, int32_t path_id, const float* alphas,
+                         const float* mu, const float* w5, float* cost, int32_t* best_index, float* best_cost, float* u_out,
+                         float* x_out, float* gains_out, float* dv, float* cand_out, float* lq_out, void* stream) {
+    if (h && n_env == 0) return EB_OK;
+    int rc = check_paths(h, "eb_rollout_tape_ilqr: null handle");
+    if (rc) return rc;
+    rc = check_modes(h);
+    if (rc) return rc;
+    if (n_env < 0 || !obs0 || !u_nom) return fail(EB_EINVAL, "eb_rollout_tape_ilqr: bad argument");
+    if (horizon < 1 || horizon > eb::IL_MAX_HORIZON || n_alpha < 0 || n_alpha > eb::IL_MAX_ALPHA) {
+        char msg[256];
+        std::snprintf(msg, sizeof msg, "eb_rollout_tape_ilqr: horizon %d / n_alpha %d exceed the kernel's limits of 1..%d / 0..%d "
+                      "(eb_rollout_tape_ilqr_max)", (int)horizon, (int)n_alpha, eb::IL_MAX_HORIZON, eb::IL_MAX_ALPHA);
+        return fail(EB_EINVAL, msg);
+    }
+    if ((x_nom == nullptr) != (gains == nullptr)) return fail(EB_EINVAL, "eb_rollout_tape_ilqr: x_nom and gains come together or not at all");
+    if (n_alpha > 0 && !gains) return fail(EB_EINVAL, "eb_rollout_tape_ilqr: n_alpha must be 0 without gains");
+    if (n_alpha > 0 && !alphas) return fail(EB_EINVAL, "eb_rollout_tape_ilqr: alphas is required for n_alpha > 0");
+    for (int k = 0; k < n_alpha; ++k)
+        if (!(alphas[k] > 0.0f) || !std::isfinite(alphas[k])) return fail(EB_EINVAL, "eb_rollout_tape_ilqr: alphas must be finite and > 0");
+    if (!w5) return fail(EB_EINVAL, "eb_rollout_tape_ilqr: w5 is required (the weights of cost)");
+    if (!(w5[0] <= 0.0f) || !(w5[1] >= 0.0f) || !(w5[2] >= 0.0f) || !(w5[3] >= 0.0f) || !(w5[4] >= 0.0f))
+        return fail(EB_EINVAL, "eb_rollout_tape_ilqr: weights must satisfy w5[0] <= 0 and w5[1..4] >= 0 (a Gauss-Newton model needs a sum of squares)");
+    {
+        const void* ins[] = {obs0, u_nom, x_nom, gains, ref_idx, mu};
+        const void* outs[] = {cost, best_index, best_cost, u_out, x_out, gains_out, dv, cand_out, lq_out};
+        for (const void* o : outs)
+            for (const void* i : ins)
+                if (o && o == i) return fail(EB_EINVAL, "eb_rollout_tape_ilqr: an output pointer equals an input pointer (ping-pong the buffers)");
+    }
+    const bool training = h->cfg.mode == EB_MODE_TRAINING;
+    if (training) {
+        if (!ref_idx) return fail(EB_EINVAL, "training mode needs ref_idx (EnvironmentModel.reset(obses, ref_indexes))");
+    } else if (path_id < 0 || path_id >= h->pt.n_paths) {
+        return fail(EB_EINVAL, "bad path_id");
+    }
+    EB_HIP(hipSetDevice(h->cfg.device));
+    eb::TapeIlqrArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.obs0 = obs0; A.u_nom = u_nom; A.x_nom = x_nom; A.gains = gains; A.ref_idx = training ? ref_idx : nullptr; A.mu = mu;
+    for (int k = 0; k < n_alpha; ++k) A.alphas[k] = alphas[k];
+    for (int k = 0; k < 5; ++k) A.w5[k] = w5[k];
+    A.cost = cost; A.best_index = best_index; A.best_cost = best_cost; A.u_out = u_out; A.x_out = x_out; A.gains_out = gains_out;
+    A.dv = dv; A.cand_out = cand_out; A.lq_out = lq_out;
+    A.dt = h->d_pt;
+    A.xy10 = reinterpret_cast<const float*>(h->d_red_all);
+    A.phi10 = h->d_phi10_all;
+    A.rad_all = h->d_rad_all;
+    A.cells = h->d_cells;
+    A.gx0 = h->pt.gx0; A.gy0 = h->pt.gy0; A.gnx = h->pt.gnx; A.gny = h->pt.gny;
+    for (int k = 0; k < 3; ++k) { A.red_off[k] = h->red_off[k]; A.red_len[k] = h->pt.red_len[k]; }
+    A.n_paths = h->pt.n_paths;
+    A.n_env = n_env; A.n_alpha = n_alpha; A.obs_dim = obs_dim(h->cfg); A.n_veh = h->cfg.n_veh; A.nd = A.obs_dim - 4 * A.n_veh;
+    A.horizon = horizon;
+    A.training = training; A.path_id = training ? 0 : path_id;
+    EB_HIP(eb::launch_rollout_tape_ilqr(h->cfg.task, A, (hipStream_t)stream));
     return EB_OK;
 }
 

@@ -41,6 +41,14 @@ solver's.
 
     smpc = SamplingMPC(model, horizon=25, n_samples=256)
     u, J, info = smpc.solve(obses, ref_indexes=ref)    # info['J_history'] [iterations + 1, B], info['counter_next']
+
+Second order.  ILQRMPC is iLQR / Gauss-Newton DDP with an exact box QP per step: per iteration ONE eb_rollout_tape_ilqr launch
+(include/envbuild_ilqr.h) tries the previous feedback gains at several step lengths, keeps the best trajectory, linearises along it
+and sweeps backwards to the next gains.  A solve is iterations + 2 launches and reads nothing on the host.  polish works as
+SamplingMPC's.
+
+    impc = ILQRMPC(model, horizon=25)
+    u, J, info = impc.solve(obses, ref_indexes=ref)    # info['J_history'] [iterations + 1, B], info['best_index'], info['mu']
 """
 import ctypes as C
 
@@ -48,7 +56,8 @@ import torch
 
 from . import _capi
 
-__all__ = ['OpenLoopMPC', 'SamplingMPC', 'cost_from_out5', 'projected_gradient', 'sampling_loop', 'best_start', 'DEFAULT_WEIGHTS']
+__all__ = ['OpenLoopMPC', 'SamplingMPC', 'ILQRMPC', 'cost_from_out5', 'projected_gradient', 'sampling_loop', 'ilqr_loop', 'best_start',
+           'DEFAULT_WEIGHTS']
 
 DEFAULT_WEIGHTS = (-1.0, 10.0, 0.0, 0.0, 0.0)
 
@@ -481,6 +490,137 @@ class SamplingMPC(object):
             starts = torch.stack([torch.zeros_like(u), u])
             up, Jp, pinfo = self.polish.solve(obs, ref_indexes=ri, path_index=None if ri is not None else pid, u_init=starts, starts='all')
             info.update(u_sampled=u, J_sampled=J, polish=pinfo, launches=info['launches'] + pinfo['launches'])
+            u, J = up, Jp
+        return u, J, info
+
+    warm_start = staticmethod(OpenLoopMPC.warm_start)
+
+
+def ilqr_loop(step, u0, iterations, mu0=0.0):
+    """The iLQR iteration on a batch of independent problems, free of the device:
+        step(u_nom [H, B, 2], x_nom, gains, mu [B] or None, need_gains) -> dict(best_index [B], best_cost [B], u, x, gains)
+    is one iteration along u_nom: candidate 0 is u_nom itself, candidates j >= 1 follow the feedback law (x_nom, gains) at the step
+    lengths of the caller; u / x / gains are the best candidate's tape, its states and the NEXT gains (None / None / None on the
+    first call: candidate 0 only).  need_gains is False on the LAST call, whose gains nobody reads: the step may skip its backward
+    sweep and leave `gains` out.  step may hand out the same two sets of tensors in turn (ping-pong): what is kept here is cloned.
+    Per env the regularisation mu becomes max(10 mu, 1e-3), capped at 1e6, when candidate 0 won (no step length helped), else 0.2 mu,
+    flushed to 0 below 1e-6 — a `where`, nothing is read on the host.
+    -> (u [H, B, 2], J [B], info): J_history [iterations + 1, B] (it never increases: candidate 0 is always in the set), best_index
+    [iterations, B], mu [B] (after the last iteration)."""
+    n_it = int(iterations)
+    out = step(u0, None, None, None, n_it > 0)
+    J = out['best_cost']
+    mu = torch.full_like(J, float(mu0))
+    hist, picks = [J.clone()], []
+    for it in range(n_it):
+        out = step(out['u'], out['x'], out['gains'], mu, it + 1 < n_it)
+        stay = out['best_index'] == 0
+        down = 0.2 * mu
+        mu = torch.where(stay, (10.0 * mu).clamp(1e-3, 1e6), torch.where(down < 1e-6, torch.zeros_like(mu), down))
+        hist.append(out['best_cost'].clone())
+        picks.append(out['best_index'].clone())
+    info = dict(J_history=torch.stack(hist), mu=mu,
+                best_index=torch.stack(picks) if picks else torch.zeros((0,) + tuple(J.shape), dtype=torch.int32, device=J.device))
+    return out['u'].clone(), hist[-1], info
+
+
+class ILQRMPC(object):
+    """Second-order MPC (iLQR / Gauss-Newton DDP, box-constrained) over `horizon` steps of `model`: one eb_rollout_tape_ilqr launch per
+    iteration.  alphas: the step lengths every iteration tries (at most ilqr.tape_ilqr_max's); mu0: the start value of the per-env
+    regularisation of Q_uu; weights must satisfy w[0] <= 0 and w[1..4] >= 0 (a sum of squares).  polish: an OpenLoopMPC on the same
+    model, horizon and weights, or None.  fp32 state only."""
+
+    def __init__(self, model, horizon=25, weights=DEFAULT_WEIGHTS, iterations=15, alphas=(1, .5, .25, .125, .0625, .03125, .015625),
+                 mu0=0.0, polish=None):
+        from .dynamics_and_models import _dev
+        from . import ilqr as _ilqr
+        self._dev_fn, self._ilqr = _dev, _ilqr
+        if model.state_dtype != torch.float32:
+            raise _capi.EbError('ILQRMPC: fp32 state only')
+        model.api.ilqr_fn('eb_rollout_tape_ilqr')                    # EbError here when the library has no iLQR iteration
+        self.model, self.horizon = model, int(horizon)
+        self.weights = tuple(float(v) for v in weights)
+        if len(self.weights) != 5:
+            raise ValueError('weights: five floats, one per out5 row')
+        if self.weights[0] > 0 or min(self.weights[1:]) < 0:
+            raise ValueError('ILQRMPC: weights must satisfy w[0] <= 0 and w[1..4] >= 0')
+        self.iterations = int(iterations)
+        if self.iterations < 0:
+            raise ValueError('ILQRMPC: iterations must not be negative')
+        self.alphas = tuple(float(a) for a in alphas)
+        max_alpha, max_h = _ilqr.tape_ilqr_max(model, self.horizon)
+        if self.horizon < 1 or self.horizon > max_h:
+            raise ValueError('ILQRMPC: horizon %d is outside 1..%d (eb_rollout_tape_ilqr_max)' % (self.horizon, max_h))
+        if len(self.alphas) < 1 or len(self.alphas) > max_alpha or not all(0 < a < float('inf') for a in self.alphas):
+            raise ValueError('ILQRMPC: 1..%d finite positive step lengths (eb_rollout_tape_ilqr_max)' % max_alpha)
+        self.mu0 = float(mu0)
+        if not self.mu0 >= 0:
+            raise ValueError('ILQRMPC: mu0 must not be negative')
+        self.polish = polish
+        if polish is not None and (polish.model is not model or polish.horizon != self.horizon or polish.weights != self.weights):
+            raise ValueError('ILQRMPC: polish must be an OpenLoopMPC on the same model, horizon and weights')
+        self._value = OpenLoopMPC(model, horizon=self.horizon, weights=self.weights)      # the independent evaluation of the result
+        self._al = (C.c_float * len(self.alphas))(*self.alphas)
+        self._w5 = (C.c_float * 5)(*self.weights)
+        self._buffers = None
+        self.launches = 0
+
+    def _ping_pong(self, B, device):
+        """the two sets of output tensors of a solve, allocated once per (batch size, device)"""
+        key = (B, str(device))
+        if self._buffers is None or self._buffers[0] != key:
+            want = ('cost', 'best_index', 'best_cost', 'u', 'x', 'gains')
+            first = self._ilqr.alloc_outputs(self.horizon, B, 0, want, device)
+            sets = [self._ilqr.alloc_outputs(self.horizon, B, len(self.alphas), want, device) for _ in range(2)]
+            self._buffers = (key, first, sets)
+        return self._buffers[1], self._buffers[2]
+
+    def solve(self, obses, ref_indexes=None, path_index=None, u_init=None):
+        """-> (u [H, B, 2] raw actions in [-1, 1], J [B], info).  u_init: None = the zero tape, or a tape [H, B, 2] (warm_start).
+        Launch 0 has no gains (it scores the start and linearises along it); then `iterations` launches, each consuming the previous
+        one's u / x / gains through two sets of buffers allocated once (the last one asks for no gains: it is the value-only form); then ONE independent value-only eb_rollout_tape_vjp launch
+        whose cost_from_out5 is the returned J (the contract of OpenLoopMPC.solve).  info: J_history [iterations + 1, B] (the best cost
+        after launch 0 and after every iteration, as the kernel formed it: it never increases), best_index [iterations, B] (0: no step
+        length helped), mu [B], J_kernel [B] (= J_history[-1]; it agrees with J to the rounding of the two summation orders),
+        launches (iterations + 2).  With polish the zero tape and the iLQR tape go through
+        polish.solve(u_init=stack([zero, u_ilqr]), starts='all') — start 0 is the zero tape on purpose: its descent is the default
+        solver's — and u, J are the polished ones; info then also has u_ilqr, J_ilqr and `polish`, and launches counts both stages."""
+        m = self.model
+        obs = self._dev_fn(obses, m.device).detach().contiguous()
+        if obs.dim() != 2 or obs.shape[1] != m.obs_dim:
+            raise ValueError('obses must be [B, %d]; got %s' % (m.obs_dim, tuple(obs.shape)))
+        B = obs.shape[0]
+        ri, pid = _solve_path_args(m, self._dev_fn, ref_indexes, path_index, 'ILQRMPC.solve')
+        if u_init is None:
+            u0 = torch.zeros((self.horizon, B, 2), dtype=torch.float32, device=m.device)
+        else:
+            u0 = self._dev_fn(u_init, m.device).detach().contiguous()
+            if tuple(u0.shape) != (self.horizon, B, 2):
+                raise ValueError('u_init must be [%d, %d, 2]; got %s' % (self.horizon, B, tuple(u0.shape)))
+        first_out, sets = self._ping_pong(B, obs.device)
+        start = self.launches
+        turn = [0]
+
+        def step(u_nom, x_nom, gains, mu, need_gains):
+            dest = first_out if gains is None else sets[turn[0]]
+            if not need_gains:                                       # the last launch: no gains_out, so no backward sweep
+                dest = {k: v for k, v in dest.items() if k != 'gains'}
+            if gains is None:
+                out = self._ilqr.launch(m, obs, u_nom, None, None, (), None, ri, pid, self._w5, dest)
+            else:
+                out = self._ilqr.launch(m, obs, u_nom, x_nom, gains, self._al, mu.contiguous(), ri, pid, self._w5, dest)
+                turn[0] ^= 1
+            self.launches += 1
+            return out
+        u, J_kernel, info = ilqr_loop(step, u0, self.iterations, self.mu0)
+        u = u.contiguous()
+        J = self._value.value_and_grad(obs, u, ri, pid, need_grad=False)[0]
+        self.launches += 1
+        info.update(J_kernel=J_kernel, launches=self.launches - start)
+        if self.polish is not None:
+            starts = torch.stack([torch.zeros_like(u), u])
+            up, Jp, pinfo = self.polish.solve(obs, ref_indexes=ri, path_index=None if ri is not None else pid, u_init=starts, starts='all')
+            info.update(u_ilqr=u, J_ilqr=J, polish=pinfo, launches=info['launches'] + pinfo['launches'])
             u, J = up, Jp
         return u, J, info
 
