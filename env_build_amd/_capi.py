@@ -192,6 +192,18 @@ ILQR_PROTOTYPES = {
     'eb_rollout_tape_ilqr_max': (C.c_int, [_P, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
+# The optional families, each a header with a version of its own: family -> (header, what a library without it lacks, the word its
+# version message uses, version symbol, expected version, prototypes).  CApi.family_fn binds a family on first use.
+FAMILIES = {
+    'grad': ('envbuild_grad.h', 'reverse pass', 'gradient', 'eb_grad_abi_version', EB_GRAD_ABI_VERSION, GRAD_PROTOTYPES),
+    'cand': ('envbuild_cand.h', 'candidate-tape rollout', 'candidate', 'eb_cand_abi_version', EB_CAND_ABI_VERSION, CAND_PROTOTYPES),
+    'cand_grad': ('envbuild_cand_grad.h', 'candidate-tape gradient', 'candidate-gradient', 'eb_cand_grad_abi_version',
+                  EB_CAND_GRAD_ABI_VERSION, CAND_GRAD_PROTOTYPES),
+    'sample': ('envbuild_sample.h', 'sampled-tape rollout', 'sampled-tape', 'eb_sample_abi_version', EB_SAMPLE_ABI_VERSION,
+               SAMPLE_PROTOTYPES),
+    'ilqr': ('envbuild_ilqr.h', 'iLQR iteration', 'iLQR', 'eb_ilqr_abi_version', EB_ILQR_ABI_VERSION, ILQR_PROTOTYPES),
+}
+
 
 class EbError(RuntimeError):
     pass
@@ -212,101 +224,40 @@ class CApi(object):
                           % (path, self.lib.eb_abi_version(), EB_ABI_VERSION))
         self.backend = self.lib.eb_backend().decode()
 
-    def grad_fn(self, symbol):
-        """The raw ctypes function of one include/envbuild_grad.h entry, bound on first use; EbError when this library has no
-        reverse pass."""
-        fns = self.__dict__.setdefault('_grad_fns', {})
+    def family_fn(self, family, symbol):
+        """The raw ctypes function of one entry of an optional family (a key of FAMILIES), the family bound on first use; EbError when
+        this library does not export it or speaks another version of it."""
+        header, label, abi, version_symbol, version, prototypes = FAMILIES[family]
+        fns = self.__dict__.setdefault('_%s_fns' % family, {})
         if not fns:
-            missing = [n for n in GRAD_PROTOTYPES if not hasattr(self.lib, n)]
+            missing = [n for n in prototypes if not hasattr(self.lib, n)]
             if missing:
-                raise EbError('%s (backend %r) does not export %s: this library has no reverse pass (include/envbuild_grad.h is '
-                              'implemented by the HIP library only; rebuild an older one)' % (self.path, self.backend, ', '.join(missing)))
-            for n, (res, args) in GRAD_PROTOTYPES.items():
+                raise EbError('%s (backend %r) does not export %s: this library has no %s (include/%s is implemented by the HIP library '
+                              'only; rebuild an older one)' % (self.path, self.backend, ', '.join(missing), label, header))
+            for n, (res, args) in prototypes.items():
                 fn = getattr(self.lib, n)
                 fn.restype, fn.argtypes = res, args
                 fns[n] = fn
-            if fns['eb_grad_abi_version']() != EB_GRAD_ABI_VERSION:
-                v = fns['eb_grad_abi_version']()
+            v = fns[version_symbol]()
+            if v != version:
                 fns.clear()
-                raise EbError('%s: gradient ABI version %d, expected %d' % (self.path, v, EB_GRAD_ABI_VERSION))
+                raise EbError('%s: %s ABI version %d, expected %d' % (self.path, abi, v, version))
         return fns[symbol]
+
+    def grad_fn(self, symbol):
+        return self.family_fn('grad', symbol)
 
     def cand_fn(self, symbol):
-        """The raw ctypes function of one include/envbuild_cand.h entry, bound on first use; EbError when this library has no
-        candidate-tape rollout."""
-        fns = self.__dict__.setdefault('_cand_fns', {})
-        if not fns:
-            missing = [n for n in CAND_PROTOTYPES if not hasattr(self.lib, n)]
-            if missing:
-                raise EbError('%s (backend %r) does not export %s: this library has no candidate-tape rollout (include/envbuild_cand.h '
-                              'is implemented by the HIP library only; rebuild an older one)' % (self.path, self.backend, ', '.join(missing)))
-            for n, (res, args) in CAND_PROTOTYPES.items():
-                fn = getattr(self.lib, n)
-                fn.restype, fn.argtypes = res, args
-                fns[n] = fn
-            if fns['eb_cand_abi_version']() != EB_CAND_ABI_VERSION:
-                v = fns['eb_cand_abi_version']()
-                fns.clear()
-                raise EbError('%s: candidate ABI version %d, expected %d' % (self.path, v, EB_CAND_ABI_VERSION))
-        return fns[symbol]
+        return self.family_fn('cand', symbol)
 
     def cand_grad_fn(self, symbol):
-        """The raw ctypes function of one include/envbuild_cand_grad.h entry, bound on first use; EbError when this library has no
-        candidate-tape gradient."""
-        fns = self.__dict__.setdefault('_cand_grad_fns', {})
-        if not fns:
-            missing = [n for n in CAND_GRAD_PROTOTYPES if not hasattr(self.lib, n)]
-            if missing:
-                raise EbError('%s (backend %r) does not export %s: this library has no candidate-tape gradient '
-                              '(include/envbuild_cand_grad.h is implemented by the HIP library only; rebuild an older one)'
-                              % (self.path, self.backend, ', '.join(missing)))
-            for n, (res, args) in CAND_GRAD_PROTOTYPES.items():
-                fn = getattr(self.lib, n)
-                fn.restype, fn.argtypes = res, args
-                fns[n] = fn
-            if fns['eb_cand_grad_abi_version']() != EB_CAND_GRAD_ABI_VERSION:
-                v = fns['eb_cand_grad_abi_version']()
-                fns.clear()
-                raise EbError('%s: candidate-gradient ABI version %d, expected %d' % (self.path, v, EB_CAND_GRAD_ABI_VERSION))
-        return fns[symbol]
+        return self.family_fn('cand_grad', symbol)
 
     def sample_fn(self, symbol):
-        """The raw ctypes function of one include/envbuild_sample.h entry, bound on first use; EbError when this library has no
-        sampled-tape rollout."""
-        fns = self.__dict__.setdefault('_sample_fns', {})
-        if not fns:
-            missing = [n for n in SAMPLE_PROTOTYPES if not hasattr(self.lib, n)]
-            if missing:
-                raise EbError('%s (backend %r) does not export %s: this library has no sampled-tape rollout (include/envbuild_sample.h '
-                              'is implemented by the HIP library only; rebuild an older one)' % (self.path, self.backend, ', '.join(missing)))
-            for n, (res, args) in SAMPLE_PROTOTYPES.items():
-                fn = getattr(self.lib, n)
-                fn.restype, fn.argtypes = res, args
-                fns[n] = fn
-            if fns['eb_sample_abi_version']() != EB_SAMPLE_ABI_VERSION:
-                v = fns['eb_sample_abi_version']()
-                fns.clear()
-                raise EbError('%s: sampled-tape ABI version %d, expected %d' % (self.path, v, EB_SAMPLE_ABI_VERSION))
-        return fns[symbol]
+        return self.family_fn('sample', symbol)
 
     def ilqr_fn(self, symbol):
-        """The raw ctypes function of one include/envbuild_ilqr.h entry, bound on first use; EbError when this library has no
-        iLQR iteration."""
-        fns = self.__dict__.setdefault('_ilqr_fns', {})
-        if not fns:
-            missing = [n for n in ILQR_PROTOTYPES if not hasattr(self.lib, n)]
-            if missing:
-                raise EbError('%s (backend %r) does not export %s: this library has no iLQR iteration (include/envbuild_ilqr.h '
-                              'is implemented by the HIP library only; rebuild an older one)' % (self.path, self.backend, ', '.join(missing)))
-            for n, (res, args) in ILQR_PROTOTYPES.items():
-                fn = getattr(self.lib, n)
-                fn.restype, fn.argtypes = res, args
-                fns[n] = fn
-            if fns['eb_ilqr_abi_version']() != EB_ILQR_ABI_VERSION:
-                v = fns['eb_ilqr_abi_version']()
-                fns.clear()
-                raise EbError('%s: iLQR ABI version %d, expected %d' % (self.path, v, EB_ILQR_ABI_VERSION))
-        return fns[symbol]
+        return self.family_fn('ilqr', symbol)
 
     def check(self, rc):
         if rc != 0:
@@ -354,9 +305,8 @@ class CApi(object):
     def __getattr__(self, name):
         # eb_xxx(...) with return-code checking: api.rollout_step(h, ...)
         sym = 'eb_' + name
-        fn = (self.grad_fn(sym) if sym in GRAD_PROTOTYPES else self.cand_fn(sym) if sym in CAND_PROTOTYPES
-              else self.cand_grad_fn(sym) if sym in CAND_GRAD_PROTOTYPES else self.sample_fn(sym) if sym in SAMPLE_PROTOTYPES
-              else self.ilqr_fn(sym) if sym in ILQR_PROTOTYPES else getattr(self.lib, sym))
+        family = next((f for f, row in FAMILIES.items() if sym in row[5]), None)
+        fn = self.family_fn(family, sym) if family else getattr(self.lib, sym)
 
         def call(*args):
             self.check(fn(*args))

@@ -19,7 +19,7 @@ import ctypes as C
 
 import torch
 
-from . import _capi
+from ._tape_args import check_rows, five_weights, need_fp32
 from .dynamics_and_models import _dev, _stream
 
 __all__ = ['rollout_tape_candidates', 'tape_cand_max', 'rollout_tape_candidates_grad', 'tape_cand_grad_max']
@@ -30,6 +30,25 @@ def tape_cand_max(model, horizon):
     limit = C.c_int32(0)
     model.api.check(model.api.cand_fn('eb_rollout_tape_cand_max')(model.handle, int(horizon), C.byref(limit)))
     return limit.value
+
+
+def _chunk_loop(fn, limit, model, obs, tapes, ref_idx, path_ids, retrack, w5, outputs):
+    """fn (eb_rollout_tape_cand or eb_rollout_tape_cand_vjp) over the K candidates of tapes in chunks of `limit`; outputs: the entry's
+    output tensors [K, ...] or None, in its argument order -> launches"""
+    K, H, B = tapes.shape[0], tapes.shape[1], obs.shape[0]
+    per_cand = ref_idx is not None and ref_idx.dim() == 2
+    launches = 0
+    for k0 in range(0, K, limit):
+        k1 = min(K, k0 + limit)
+        ri = None if ref_idx is None else (ref_idx[k0:k1] if per_cand else ref_idx)
+        ids = None if path_ids is None else (C.c_int32 * (k1 - k0))(*path_ids[k0:k1])
+        rc = fn(model.handle, B, k1 - k0, H, obs.data_ptr(), tapes[k0:k1].data_ptr(), None if ri is None else ri.data_ptr(),
+                B if per_cand else 0, None if ids is None else C.cast(ids, C.c_void_p), 0, 1 if retrack else 0, w5,
+                *[None if o is None else o[k0:k1].data_ptr() for o in outputs], _stream(model.device))
+        if rc != 0:
+            model.api.check(rc)
+        launches += 1
+    return launches
 
 
 def launch_chunks(model, obs, tapes, ref_idx, path_ids, retrack, weights, want_out5):
@@ -43,28 +62,13 @@ def launch_chunks(model, obs, tapes, ref_idx, path_ids, retrack, weights, want_o
     if K == 0 or B == 0:
         return out5, cost, 0
     w5 = None if weights is None else (C.c_float * 5)(*[float(v) for v in weights])
-    limit = tape_cand_max(model, H)
-    per_cand = ref_idx is not None and ref_idx.dim() == 2
-    launches = 0
-    for k0 in range(0, K, limit):
-        k1 = min(K, k0 + limit)
-        ri = None if ref_idx is None else (ref_idx[k0:k1] if per_cand else ref_idx)
-        ids = None if path_ids is None else (C.c_int32 * (k1 - k0))(*path_ids[k0:k1])
-        rc = fn(model.handle, B, k1 - k0, H, obs.data_ptr(), tapes[k0:k1].data_ptr(), None if ri is None else ri.data_ptr(),
-                B if per_cand else 0, None if ids is None else C.cast(ids, C.c_void_p), 0, 1 if retrack else 0, w5,
-                None if out5 is None else out5[k0:k1].data_ptr(), None if cost is None else cost[k0:k1].data_ptr(),
-                _stream(model.device))
-        if rc != 0:
-            model.api.check(rc)
-        launches += 1
+    launches = _chunk_loop(fn, tape_cand_max(model, H), model, obs, tapes, ref_idx, path_ids, retrack, w5, (out5, cost))
     return out5, cost, launches
 
 
 def _prepare(model, obses, action_tapes, ref_indexes, path_indexes):
     """argument checks and path handling of both entries -> (obs [B, D], tapes [K, H, B, 2], ref_idx or None, path ids or None)"""
-    obs = _dev(obses, model.device).detach()
-    if obs.dim() != 2 or obs.shape[1] != model.obs_dim:
-        raise ValueError('obses must be [B, %d]; got %s' % (model.obs_dim, tuple(obs.shape)))
+    obs = check_rows(model, _dev(obses, model.device).detach())
     B = obs.shape[0]
     tapes = _dev(action_tapes, model.device).detach()
     if tapes.dim() != 4 or tapes.shape[2] != B or tapes.shape[3] != 2 or tapes.shape[1] < 1:
@@ -98,13 +102,11 @@ def rollout_tape_candidates(model, obses, action_tapes, ref_indexes=None, path_i
       weights       five floats: cost[k] = sum_t w . out5[k][t] in the order include/envbuild_cand.h fixes; None = no cost;
       want_out5     False: the cost only.
     `model` (an EnvironmentModel with fp32 state) supplies the task, the slot modes and the tables; its own state is not touched."""
-    if model.state_dtype != torch.float32:
-        raise _capi.EbError('cand.rollout_tape_candidates: fp32 state only (the fp16-state kernels have no candidate form)')
+    need_fp32(model, 'cand.rollout_tape_candidates: fp32 state only (the fp16-state kernels have no candidate form)')
     model.api.cand_fn('eb_rollout_tape_cand')              # EbError before any work when the library has no such entry
     if weights is None and not want_out5:
         raise ValueError('rollout_tape_candidates: nothing asked for (weights is None and want_out5 is False)')
-    if weights is not None and len(tuple(weights)) != 5:
-        raise ValueError('weights: five floats, one per out5 row')
+    five_weights(weights, optional=True)
     obs, tapes, ri, ids = _prepare(model, obses, action_tapes, ref_indexes, path_indexes)
     out5, cost, _ = launch_chunks(model, obs, tapes, ri, ids, retrack, weights, want_out5)
     return out5, cost
@@ -136,19 +138,7 @@ def launch_grad_chunks(model, obs, tapes, ref_idx, path_ids, retrack, weights, w
         raise ValueError('eb_rollout_tape_cand_vjp: a horizon of %d steps leaves room for no candidate on this model '
                          '(eb_rollout_tape_cand_vjp_max)' % H)
     w5 = (C.c_float * 5)(*[float(v) for v in weights])
-    per_cand = ref_idx is not None and ref_idx.dim() == 2
-    launches = 0
-    for k0 in range(0, K, limit):
-        k1 = min(K, k0 + limit)
-        ri = None if ref_idx is None else (ref_idx[k0:k1] if per_cand else ref_idx)
-        ids = None if path_ids is None else (C.c_int32 * (k1 - k0))(*path_ids[k0:k1])
-        rc = fn(model.handle, B, k1 - k0, H, obs.data_ptr(), tapes[k0:k1].data_ptr(), None if ri is None else ri.data_ptr(),
-                B if per_cand else 0, None if ids is None else C.cast(ids, C.c_void_p), 0, 1 if retrack else 0, w5,
-                None if out5 is None else out5[k0:k1].data_ptr(), cost[k0:k1].data_ptr(),
-                None if g_obs is None else g_obs[k0:k1].data_ptr(), g[k0:k1].data_ptr(), _stream(model.device))
-        if rc != 0:
-            model.api.check(rc)
-        launches += 1
+    launches = _chunk_loop(fn, limit, model, obs, tapes, ref_idx, path_ids, retrack, w5, (out5, cost, g_obs, g))
     return cost, g, out5, g_obs, launches
 
 
@@ -161,11 +151,9 @@ def rollout_tape_candidates_grad(model, obses, action_tapes, weights, ref_indexe
       ref_indexes, path_indexes, retrack   as rollout_tape_candidates;
       want_g_obs    the cotangent of every candidate's private copy of the row's first nd columns (after the retrack replacement).
     fp32 state only; no CPU path and no fall-back to K separate launches."""
-    if model.state_dtype != torch.float32:
-        raise _capi.EbError('cand.rollout_tape_candidates_grad: fp32 state only (the reverse pass has no fp16-state form)')
+    need_fp32(model, 'cand.rollout_tape_candidates_grad: fp32 state only (the reverse pass has no fp16-state form)')
     model.api.cand_grad_fn('eb_rollout_tape_cand_vjp')     # EbError before any work when the library has no such entry
-    if weights is None or len(tuple(weights)) != 5:
-        raise ValueError('weights: five floats, one per out5 row')
+    five_weights(() if weights is None else weights)
     obs, tapes, ri, ids = _prepare(model, obses, action_tapes, ref_indexes, path_indexes)
     cost, g, out5, g_obs, _ = launch_grad_chunks(model, obs, tapes, ri, ids, retrack, weights, want_out5, want_g_obs)
     return cost, g, out5, g_obs

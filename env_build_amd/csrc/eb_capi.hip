@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -498,15 +499,26 @@ static int check_modes(eb_handle h) {
     if (!h->modes_set) return fail(EB_ESTATE, "vehicle modes not set (eb_set_veh_modes)");
     return EB_OK;
 }
-static int check_rollout(eb_handle h, int n_env, const int32_t* ref_idx, int path_id, const char* who) {
-    int rc = check_paths(h, who);
-    if (rc) return rc;
-    rc = check_modes(h);
-    if (rc) return rc;
+// what every rollout and tape entry asks of its handle: paths, then vehicle modes
+static int check_tape(eb_handle h, const char* who) {
+    const int rc = check_paths(h, who);
+    return rc ? rc : check_modes(h);
+}
+// the single-path rule: training reads ref_idx per env, selecting one path_id in range.  On success *ref_idx / *path_id hold the
+// pair a kernel that takes only the mode's own half is given (NULL in selecting mode, 0 in training mode).
+static int check_path_arg(eb_handle h, const int32_t** ref_idx, int32_t* path_id) {
     if (h->cfg.mode == EB_MODE_TRAINING) {
-        if (!ref_idx) return fail(EB_EINVAL, "training mode needs ref_idx (EnvironmentModel.reset(obses, ref_indexes))");
-    } else if (path_id < 0 || path_id >= h->pt.n_paths) return fail(EB_EINVAL, "bad path_id");
+        if (!*ref_idx) return fail(EB_EINVAL, "training mode needs ref_idx (EnvironmentModel.reset(obses, ref_indexes))");
+        *path_id = 0;
+    } else {
+        if (*path_id < 0 || *path_id >= h->pt.n_paths) return fail(EB_EINVAL, "bad path_id");
+        *ref_idx = nullptr;
+    }
     return EB_OK;
+}
+static int check_rollout(eb_handle h, int n_env, const int32_t* ref_idx, int path_id, const char* who) {
+    const int rc = check_tape(h, who);
+    return rc ? rc : check_path_arg(h, &ref_idx, &path_id);
 }
 
 int eb_f_xu(eb_handle h, int32_t n, const float* states, const float* actions, float tau, float* next_states,
@@ -1762,6 +1774,89 @@ static int step_vjp(eb_handle h, int32_t n_env, const float* obs_in, const float
     return EB_OK;
 }
 
+// ---- what the one-launch tape entries (eb_rollout_tape_vjp / _cand / _cand_vjp / _sample / _ilqr) share on the host ----
+// the handle's closest-point tables and the launch's shape, which TapeVjpArgs, TapeCandArgs, TapeSampleArgs and TapeIlqrArgs name alike
+template <class Args>
+static void fill_tape_scene(eb_handle h, int32_t n_env, int32_t horizon, Args& A) {
+    A.dt = h->d_pt;
+    A.xy10 = reinterpret_cast<const float*>(h->d_red_all);
+    A.phi10 = h->d_phi10_all;
+    A.rad_all = h->d_rad_all;
+    A.cells = h->d_cells;
+    A.gx0 = h->pt.gx0; A.gy0 = h->pt.gy0; A.gnx = h->pt.gnx; A.gny = h->pt.gny;
+    for (int k = 0; k < 3; ++k) { A.red_off[k] = h->red_off[k]; A.red_len[k] = h->pt.red_len[k]; }
+    A.n_paths = h->pt.n_paths;
+    A.n_env = n_env; A.obs_dim = obs_dim(h->cfg); A.n_veh = h->cfg.n_veh; A.nd = A.obs_dim - 4 * A.n_veh;
+    A.horizon = horizon;
+    A.training = h->cfg.mode == EB_MODE_TRAINING;
+}
+
+// EB_EINVAL with a formatted message: the refusals that name a kernel's limit, and those of checks two entries share
+__attribute__((format(printf, 1, 2))) static int fail_limit(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    std::vsnprintf(g_err, sizeof g_err, fmt, ap);
+    va_end(ap);
+    return EB_EINVAL;
+}
+
+// the per-candidate path rule: training reads ref_idx[k * ref_ld + env], selecting packs candidate k's path into bits 2k, 2k + 1
+static int cand_path_bits(eb_handle h, const char* who, int32_t n_env, int32_t n_cand, const int32_t* ref_idx, int32_t ref_ld,
+                          const int32_t* path_ids, int32_t path_id, unsigned* path_bits) {
+    *path_bits = 0u;
+    if (h->cfg.mode == EB_MODE_TRAINING) {
+        if (!ref_idx) return fail(EB_EINVAL, "training mode needs ref_idx (EnvironmentModel.reset(obses, ref_indexes))");
+        if (ref_ld < 0 || (ref_ld > 0 && ref_ld < n_env)) return fail_limit("%s: ref_ld must be 0 or at least n_env", who);
+    } else {
+        for (int k = 0; k < n_cand; ++k) {
+            const int p = path_ids ? path_ids[k] : path_id;
+            if (p < 0 || p >= h->pt.n_paths) return fail(EB_EINVAL, "bad path_id");
+            *path_bits |= (unsigned)p << (2 * k);                               // n_paths <= 3, n_cand <= 8
+        }
+    }
+    return EB_OK;
+}
+
+// eb_rollout_tape_cand and eb_rollout_tape_cand_vjp (`grad`) up to their launch: the checks in the order they fire, then the forward's
+// launch arguments.  The two differ in which outputs they insist on and in their candidate limit.
+static int cand_setup(eb_handle h, bool grad, int32_t n_env, int32_t n_cand, int32_t horizon, const float* obs0, const float* action_tapes,
+                      const int32_t* ref_idx, int32_t ref_ld, const int32_t* path_ids, int32_t path_id, int32_t retrack, const float* w5,
+                      float* out5_steps, float* cost, const float* g_action_tapes, eb::TapeCandArgs* out) {
+    const char* who = grad ? "eb_rollout_tape_cand_vjp" : "eb_rollout_tape_cand";
+    int rc = check_tape(h, grad ? "eb_rollout_tape_cand_vjp: null handle" : "eb_rollout_tape_cand: null handle");
+    if (rc) return rc;
+    if (n_env < 0 || n_cand < 0 || horizon < 1 || horizon > eb::TC_MAX_HORIZON || !obs0 || !action_tapes)
+        return fail_limit("%s: bad argument", who);
+    if (grad) {
+        if (!g_action_tapes)
+            return fail(EB_EINVAL, "eb_rollout_tape_cand_vjp: g_action_tapes is required; the value-only form is eb_rollout_tape_cand "
+                                   "(include/envbuild_cand.h)");
+        if (!w5) return fail(EB_EINVAL, "eb_rollout_tape_cand_vjp: w5 is required (the weights of cost and the cotangent of out5)");
+    } else {
+        if (!out5_steps && !cost) return fail(EB_EINVAL, "eb_rollout_tape_cand: neither out5_steps nor cost is asked for");
+        if (cost && !w5) return fail(EB_EINVAL, "eb_rollout_tape_cand: cost needs w5");
+    }
+    const int limit = grad ? eb::rollout_tape_cand_vjp_max(h->cfg.n_veh, horizon) : eb::rollout_tape_cand_max(h->cfg.n_veh);
+    if (n_cand > limit)
+        return grad ? fail_limit("eb_rollout_tape_cand_vjp: %d candidates exceed the kernel's limit of %d for %d vehicle slots and %d steps "
+                                 "(eb_rollout_tape_cand_vjp_max): evaluate the set in chunks", (int)n_cand, limit, (int)h->cfg.n_veh, (int)horizon)
+                    : fail_limit("eb_rollout_tape_cand: %d candidates exceed the kernel's limit of %d for %d vehicle slots "
+                                 "(eb_rollout_tape_cand_max): evaluate the set in chunks", (int)n_cand, limit, (int)h->cfg.n_veh);
+    unsigned path_bits;
+    rc = cand_path_bits(h, who, n_env, n_cand, ref_idx, ref_ld, path_ids, path_id, &path_bits);
+    if (rc) return rc;
+    EB_HIP(hipSetDevice(h->cfg.device));
+    eb::TapeCandArgs& A = *out;
+    std::memset(&A, 0, sizeof A);
+    fill_tape_scene(h, n_env, horizon, A);
+    A.obs0 = obs0; A.tapes = action_tapes; A.ref_idx = A.training ? ref_idx : nullptr;
+    for (int k = 0; k < 5; ++k) A.w5[k] = w5 ? w5[k] : 0.0f;
+    A.out5_steps = out5_steps; A.cost = cost;
+    A.n_cand = n_cand; A.ref_ld = ref_ld; A.retrack = retrack != 0;
+    A.path_bits = path_bits;
+    return EB_OK;
+}
+
 extern "C" {
 
 int eb_grad_abi_version(void) { return EB_GRAD_ABI_VERSION; }
@@ -1821,15 +1916,12 @@ int eb_rollout_tape_vjp(eb_handle h, int32_t n_env, int32_t horizon, const float
     if (h && n_env == 0) return EB_OK;
     int rc = check_rollout(h, n_env, ref_idx, path_id, "eb_rollout_tape_vjp: null handle");
     if (rc) return rc;
-    const int D = obs_dim(h->cfg), nd = D - 4 * h->cfg.n_veh;
+    const int nd = obs_dim(h->cfg) - 4 * h->cfg.n_veh;
     if (n_env < 0 || horizon < 1 || !obs0 || !action_tape) return fail(EB_EINVAL, "eb_rollout_tape_vjp: bad argument");
     const int limit = eb::rollout_tape_vjp_max_horizon(h->cfg.n_veh);
-    if (horizon > limit) {
-        char msg[256];
-        std::snprintf(msg, sizeof msg, "eb_rollout_tape_vjp: horizon %d exceeds the kernel's limit of %d steps for %d vehicle slots "
-                                       "(eb_rollout_tape_vjp_max_horizon)", (int)horizon, limit, (int)h->cfg.n_veh);
-        return fail(EB_EINVAL, msg);
-    }
+    if (horizon > limit)
+        return fail_limit("eb_rollout_tape_vjp: horizon %d exceeds the kernel's limit of %d steps for %d vehicle slots "
+                          "(eb_rollout_tape_vjp_max_horizon)", (int)horizon, limit, (int)h->cfg.n_veh);
     if (g_obs_final && ld_final < nd) return fail(EB_EINVAL, "eb_rollout_tape_vjp: ld_final must be at least nd = 6 + 3 * (n_future + 1)");
     if (obs_out && obs_out == obs0) return fail(EB_EINVAL, "eb_rollout_tape_vjp: obs_out must not alias obs0");
     if (g_obs0 && g_obs0 == g_obs_final) return fail(EB_EINVAL, "eb_rollout_tape_vjp: g_obs0 must not alias g_obs_final");
@@ -1840,47 +1932,14 @@ int eb_rollout_tape_vjp(eb_handle h, int32_t n_env, int32_t horizon, const float
     A.obs0 = obs0; A.tape = action_tape; A.ref_idx = ref_idx; A.g_obs_final = g_obs_final; A.g_out5_steps = g_out5_steps;
     for (int k = 0; k < 5; ++k) A.w5[k] = w5 ? w5[k] : 0.0f;
     A.out5_steps = out5_steps; A.obs_out = obs_out; A.g_obs0 = g_obs0; A.g_action_tape = g_action_tape;
-    A.dt = h->d_pt;
-    A.xy10 = reinterpret_cast<const float*>(h->d_red_all);
-    A.phi10 = h->d_phi10_all;
-    A.rad_all = h->d_rad_all;
-    A.cells = h->d_cells;
-    A.gx0 = h->pt.gx0; A.gy0 = h->pt.gy0; A.gnx = h->pt.gnx; A.gny = h->pt.gny;
-    for (int k = 0; k < 3; ++k) { A.red_off[k] = h->red_off[k]; A.red_len[k] = h->pt.red_len[k]; }
-    A.n_paths = h->pt.n_paths;
-    A.n_env = n_env; A.obs_dim = D; A.nd = nd; A.n_veh = h->cfg.n_veh; A.n_future = h->cfg.n_future;
-    A.horizon = horizon; A.ld_final = ld_final;
-    A.path_id = path_id; A.training = h->cfg.mode == EB_MODE_TRAINING;
+    fill_tape_scene(h, n_env, horizon, A);
+    A.n_future = h->cfg.n_future; A.ld_final = ld_final;
+    A.path_id = path_id;
     EB_HIP(eb::launch_rollout_tape_vjp(h->cfg.task, A, h->n_cu, (hipStream_t)stream));
     return EB_OK;
 }
 
 }  // extern "C"
-
-// the launch arguments both candidate entries share, after their checks
-static eb::TapeCandArgs cand_args(eb_handle h, int32_t n_env, int32_t n_cand, int32_t horizon, const float* obs0, const float* action_tapes,
-                                  const int32_t* ref_idx, int32_t ref_ld, int32_t retrack, unsigned path_bits, const float* w5,
-                                  float* out5_steps, float* cost) {
-    const bool training = h->cfg.mode == EB_MODE_TRAINING;
-    eb::TapeCandArgs A;
-    std::memset(&A, 0, sizeof A);
-    A.obs0 = obs0; A.tapes = action_tapes; A.ref_idx = training ? ref_idx : nullptr;
-    for (int k = 0; k < 5; ++k) A.w5[k] = w5 ? w5[k] : 0.0f;
-    A.out5_steps = out5_steps; A.cost = cost;
-    A.dt = h->d_pt;
-    A.xy10 = reinterpret_cast<const float*>(h->d_red_all);
-    A.phi10 = h->d_phi10_all;
-    A.rad_all = h->d_rad_all;
-    A.cells = h->d_cells;
-    A.gx0 = h->pt.gx0; A.gy0 = h->pt.gy0; A.gnx = h->pt.gnx; A.gny = h->pt.gny;
-    for (int k = 0; k < 3; ++k) { A.red_off[k] = h->red_off[k]; A.red_len[k] = h->pt.red_len[k]; }
-    A.n_paths = h->pt.n_paths;
-    A.n_env = n_env; A.n_cand = n_cand; A.obs_dim = obs_dim(h->cfg); A.n_veh = h->cfg.n_veh; A.nd = A.obs_dim - 4 * A.n_veh;
-    A.horizon = horizon;
-    A.ref_ld = ref_ld; A.training = training; A.retrack = retrack != 0;
-    A.path_bits = path_bits;
-    return A;
-}
 
 // ---- include/envbuild_cand.h: K candidate tapes per env from one shared scene (eb_rollout_tape_cand.hip) ----
 extern "C" {
@@ -1897,35 +1956,10 @@ int eb_rollout_tape_cand(eb_handle h, int32_t n_env, int32_t n_cand, int32_t hor
                          const int32_t* ref_idx, int32_t ref_ld, const int32_t* path_ids, int32_t path_id, int32_t retrack,
                          const float* w5, float* out5_steps, float* cost, void* stream) {
     if (h && (n_env == 0 || n_cand == 0)) return EB_OK;
-    int rc = check_paths(h, "eb_rollout_tape_cand: null handle");
+    eb::TapeCandArgs A;
+    const int rc = cand_setup(h, false, n_env, n_cand, horizon, obs0, action_tapes, ref_idx, ref_ld, path_ids, path_id, retrack, w5, out5_steps,
+                              cost, nullptr, &A);
     if (rc) return rc;
-    rc = check_modes(h);
-    if (rc) return rc;
-    if (n_env < 0 || n_cand < 0 || horizon < 1 || horizon > eb::TC_MAX_HORIZON || !obs0 || !action_tapes)
-        return fail(EB_EINVAL, "eb_rollout_tape_cand: bad argument");
-    if (!out5_steps && !cost) return fail(EB_EINVAL, "eb_rollout_tape_cand: neither out5_steps nor cost is asked for");
-    if (cost && !w5) return fail(EB_EINVAL, "eb_rollout_tape_cand: cost needs w5");
-    const int limit = eb::rollout_tape_cand_max(h->cfg.n_veh);
-    if (n_cand > limit) {
-        char msg[256];
-        std::snprintf(msg, sizeof msg, "eb_rollout_tape_cand: %d candidates exceed the kernel's limit of %d for %d vehicle slots "
-                                       "(eb_rollout_tape_cand_max): evaluate the set in chunks", (int)n_cand, limit, (int)h->cfg.n_veh);
-        return fail(EB_EINVAL, msg);
-    }
-    const bool training = h->cfg.mode == EB_MODE_TRAINING;
-    unsigned path_bits = 0u;
-    if (training) {
-        if (!ref_idx) return fail(EB_EINVAL, "training mode needs ref_idx (EnvironmentModel.reset(obses, ref_indexes))");
-        if (ref_ld < 0 || (ref_ld > 0 && ref_ld < n_env)) return fail(EB_EINVAL, "eb_rollout_tape_cand: ref_ld must be 0 or at least n_env");
-    } else {
-        for (int k = 0; k < n_cand; ++k) {
-            const int p = path_ids ? path_ids[k] : path_id;
-            if (p < 0 || p >= h->pt.n_paths) return fail(EB_EINVAL, "bad path_id");
-            path_bits |= (unsigned)p << (2 * k);                                // n_paths <= 3, n_cand <= 8
-        }
-    }
-    EB_HIP(hipSetDevice(h->cfg.device));
-    const eb::TapeCandArgs A = cand_args(h, n_env, n_cand, horizon, obs0, action_tapes, ref_idx, ref_ld, retrack, path_bits, w5, out5_steps, cost);
     EB_HIP(eb::launch_rollout_tape_cand(h->cfg.task, A, h->n_cu, (hipStream_t)stream));
     return EB_OK;
 }
@@ -1947,38 +1981,10 @@ int eb_rollout_tape_cand_vjp(eb_handle h, int32_t n_env, int32_t n_cand, int32_t
                              const int32_t* ref_idx, int32_t ref_ld, const int32_t* path_ids, int32_t path_id, int32_t retrack,
                              const float* w5, float* out5_steps, float* cost, float* g_obs0, float* g_action_tapes, void* stream) {
     if (h && (n_env == 0 || n_cand == 0)) return EB_OK;
-    int rc = check_paths(h, "eb_rollout_tape_cand_vjp: null handle");
-    if (rc) return rc;
-    rc = check_modes(h);
-    if (rc) return rc;
-    if (n_env < 0 || n_cand < 0 || horizon < 1 || horizon > eb::TC_MAX_HORIZON || !obs0 || !action_tapes)
-        return fail(EB_EINVAL, "eb_rollout_tape_cand_vjp: bad argument");
-    if (!g_action_tapes)
-        return fail(EB_EINVAL, "eb_rollout_tape_cand_vjp: g_action_tapes is required; the value-only form is eb_rollout_tape_cand "
-                               "(include/envbuild_cand.h)");
-    if (!w5) return fail(EB_EINVAL, "eb_rollout_tape_cand_vjp: w5 is required (the weights of cost and the cotangent of out5)");
-    const int limit = eb::rollout_tape_cand_vjp_max(h->cfg.n_veh, horizon);
-    if (n_cand > limit) {
-        char msg[256];
-        std::snprintf(msg, sizeof msg, "eb_rollout_tape_cand_vjp: %d candidates exceed the kernel's limit of %d for %d vehicle slots and "
-                                       "%d steps (eb_rollout_tape_cand_vjp_max): evaluate the set in chunks",
-                      (int)n_cand, limit, (int)h->cfg.n_veh, (int)horizon);
-        return fail(EB_EINVAL, msg);
-    }
-    unsigned path_bits = 0u;
-    if (h->cfg.mode == EB_MODE_TRAINING) {
-        if (!ref_idx) return fail(EB_EINVAL, "training mode needs ref_idx (EnvironmentModel.reset(obses, ref_indexes))");
-        if (ref_ld < 0 || (ref_ld > 0 && ref_ld < n_env)) return fail(EB_EINVAL, "eb_rollout_tape_cand_vjp: ref_ld must be 0 or at least n_env");
-    } else {
-        for (int k = 0; k < n_cand; ++k) {
-            const int p = path_ids ? path_ids[k] : path_id;
-            if (p < 0 || p >= h->pt.n_paths) return fail(EB_EINVAL, "bad path_id");
-            path_bits |= (unsigned)p << (2 * k);                                // n_paths <= 3, n_cand <= 8
-        }
-    }
-    EB_HIP(hipSetDevice(h->cfg.device));
     eb::TapeCandVjpArgs A;
-    A.F = cand_args(h, n_env, n_cand, horizon, obs0, action_tapes, ref_idx, ref_ld, retrack, path_bits, w5, out5_steps, cost);
+    const int rc = cand_setup(h, true, n_env, n_cand, horizon, obs0, action_tapes, ref_idx, ref_ld, path_ids, path_id, retrack, w5, out5_steps,
+                              cost, g_action_tapes, &A.F);
+    if (rc) return rc;
     A.g_obs0 = g_obs0; A.g_tapes = g_action_tapes;
     EB_HIP(eb::launch_rollout_tape_cand_vjp(h->cfg.task, A, h->n_cu, (hipStream_t)stream));
     return EB_OK;
@@ -2002,9 +2008,7 @@ int eb_rollout_tape_sample(eb_handle h, int32_t n_env, int32_t n_samples, int32_
                            const float* sigma2, float beta, float inv_lambda, const float* w5, float* cost, float* best_tape,
                            float* best_cost, int32_t* best_index, float* mean_tape, float* samples_out, void* stream) {
     if (h && (n_env == 0 || n_samples == 0)) return EB_OK;
-    int rc = check_paths(h, "eb_rollout_tape_sample: null handle");
-    if (rc) return rc;
-    rc = check_modes(h);
+    int rc = check_tape(h, "eb_rollout_tape_sample: null handle");
     if (rc) return rc;
     if (n_env < 0 || n_samples < 0 || !obs0 || !nominal) return fail(EB_EINVAL, "eb_rollout_tape_sample: bad argument");
     if (horizon < 1 || horizon > eb::TS_MAX_HORIZON) return fail(EB_EINVAL, "eb_rollout_tape_sample: horizon must be in 1..128");
@@ -2015,39 +2019,23 @@ int eb_rollout_tape_sample(eb_handle h, int32_t n_env, int32_t n_samples, int32_
         return fail(EB_EINVAL, "eb_rollout_tape_sample: sigma2 must be two floats >= 0");
     if (!(beta >= 0.0f && beta < 1.0f)) return fail(EB_EINVAL, "eb_rollout_tape_sample: beta must be in [0, 1)");
     if (!(inv_lambda >= 0.0f) || !std::isfinite(inv_lambda)) return fail(EB_EINVAL, "eb_rollout_tape_sample: inv_lambda must be finite and >= 0");
-    if (n_samples > eb::TS_MAX_SAMPLES) {
-        char msg[256];
-        std::snprintf(msg, sizeof msg, "eb_rollout_tape_sample: %d samples exceed the kernel's limit of %d (eb_rollout_tape_sample_max)",
-                      (int)n_samples, eb::TS_MAX_SAMPLES);
-        return fail(EB_EINVAL, msg);
-    }
-    const bool training = h->cfg.mode == EB_MODE_TRAINING;
-    if (training) {
-        if (!ref_idx) return fail(EB_EINVAL, "training mode needs ref_idx (EnvironmentModel.reset(obses, ref_indexes))");
-    } else if (path_id < 0 || path_id >= h->pt.n_paths) {
-        return fail(EB_EINVAL, "bad path_id");
-    }
+    if (n_samples > eb::TS_MAX_SAMPLES)
+        return fail_limit("eb_rollout_tape_sample: %d samples exceed the kernel's limit of %d (eb_rollout_tape_sample_max)",
+                          (int)n_samples, eb::TS_MAX_SAMPLES);
+    rc = check_path_arg(h, &ref_idx, &path_id);
+    if (rc) return rc;
     EB_HIP(hipSetDevice(h->cfg.device));
     eb::TapeSampleArgs A;
     std::memset(&A, 0, sizeof A);
-    A.obs0 = obs0; A.nominal = nominal; A.ref_idx = training ? ref_idx : nullptr; A.env_ids = env_ids;
+    A.obs0 = obs0; A.nominal = nominal; A.ref_idx = ref_idx; A.env_ids = env_ids;
     A.seed = seed; A.counter = counter;
     A.sigma0 = sigma2[0]; A.sigma1 = sigma2[1]; A.beta = beta; A.inv_lambda = inv_lambda;
     A.gain = (float)std::sqrt(1.0 - (double)beta * (double)beta);
     for (int k = 0; k < 5; ++k) A.w5[k] = w5[k];
     A.cost = cost; A.best_tape = best_tape; A.best_cost = best_cost; A.best_index = best_index; A.mean_tape = mean_tape;
     A.samples_out = samples_out;
-    A.dt = h->d_pt;
-    A.xy10 = reinterpret_cast<const float*>(h->d_red_all);
-    A.phi10 = h->d_phi10_all;
-    A.rad_all = h->d_rad_all;
-    A.cells = h->d_cells;
-    A.gx0 = h->pt.gx0; A.gy0 = h->pt.gy0; A.gnx = h->pt.gnx; A.gny = h->pt.gny;
-    for (int k = 0; k < 3; ++k) { A.red_off[k] = h->red_off[k]; A.red_len[k] = h->pt.red_len[k]; }
-    A.n_paths = h->pt.n_paths;
-    A.n_env = n_env; A.n_samples = n_samples; A.obs_dim = obs_dim(h->cfg); A.n_veh = h->cfg.n_veh; A.nd = A.obs_dim - 4 * A.n_veh;
-    A.horizon = horizon;
-    A.training = training; A.path_id = training ? 0 : path_id;
+    fill_tape_scene(h, n_env, horizon, A);
+    A.n_samples = n_samples; A.path_id = path_id;
     EB_HIP(eb::launch_rollout_tape_sample(h->cfg.task, A, (hipStream_t)stream));
     return EB_OK;
 }
@@ -2072,17 +2060,12 @@ int eb_rollout_tape_ilqr(eb_handle h, int32_t n_env, int32_t horizon, int32_t n_
                          const float* mu, const float* w5, float* cost, int32_t* best_index, float* best_cost, float* u_out,
                          float* x_out, float* gains_out, float* dv, float* cand_out, float* lq_out, void* stream) {
     if (h && n_env == 0) return EB_OK;
-    int rc = check_paths(h, "eb_rollout_tape_ilqr: null handle");
-    if (rc) return rc;
-    rc = check_modes(h);
+    int rc = check_tape(h, "eb_rollout_tape_ilqr: null handle");
     if (rc) return rc;
     if (n_env < 0 || !obs0 || !u_nom) return fail(EB_EINVAL, "eb_rollout_tape_ilqr: bad argument");
-    if (horizon < 1 || horizon > eb::IL_MAX_HORIZON || n_alpha < 0 || n_alpha > eb::IL_MAX_ALPHA) {
-        char msg[256];
-        std::snprintf(msg, sizeof msg, "eb_rollout_tape_ilqr: horizon %d / n_alpha %d exceed the kernel's limits of 1..%d / 0..%d "
-                      "(eb_rollout_tape_ilqr_max)", (int)horizon, (int)n_alpha, eb::IL_MAX_HORIZON, eb::IL_MAX_ALPHA);
-        return fail(EB_EINVAL, msg);
-    }
+    if (horizon < 1 || horizon > eb::IL_MAX_HORIZON || n_alpha < 0 || n_alpha > eb::IL_MAX_ALPHA)
+        return fail_limit("eb_rollout_tape_ilqr: horizon %d / n_alpha %d exceed the kernel's limits of 1..%d / 0..%d "
+                          "(eb_rollout_tape_ilqr_max)", (int)horizon, (int)n_alpha, eb::IL_MAX_HORIZON, eb::IL_MAX_ALPHA);
     if ((x_nom == nullptr) != (gains == nullptr)) return fail(EB_EINVAL, "eb_rollout_tape_ilqr: x_nom and gains come together or not at all");
     if (n_alpha > 0 && !gains) return fail(EB_EINVAL, "eb_rollout_tape_ilqr: n_alpha must be 0 without gains");
     if (n_alpha > 0 && !alphas) return fail(EB_EINVAL, "eb_rollout_tape_ilqr: alphas is required for n_alpha > 0");
@@ -2098,31 +2081,18 @@ int eb_rollout_tape_ilqr(eb_handle h, int32_t n_env, int32_t horizon, int32_t n_
             for (const void* i : ins)
                 if (o && o == i) return fail(EB_EINVAL, "eb_rollout_tape_ilqr: an output pointer equals an input pointer (ping-pong the buffers)");
     }
-    const bool training = h->cfg.mode == EB_MODE_TRAINING;
-    if (training) {
-        if (!ref_idx) return fail(EB_EINVAL, "training mode needs ref_idx (EnvironmentModel.reset(obses, ref_indexes))");
-    } else if (path_id < 0 || path_id >= h->pt.n_paths) {
-        return fail(EB_EINVAL, "bad path_id");
-    }
+    rc = check_path_arg(h, &ref_idx, &path_id);
+    if (rc) return rc;
     EB_HIP(hipSetDevice(h->cfg.device));
     eb::TapeIlqrArgs A;
     std::memset(&A, 0, sizeof A);
-    A.obs0 = obs0; A.u_nom = u_nom; A.x_nom = x_nom; A.gains = gains; A.ref_idx = training ? ref_idx : nullptr; A.mu = mu;
+    A.obs0 = obs0; A.u_nom = u_nom; A.x_nom = x_nom; A.gains = gains; A.ref_idx = ref_idx; A.mu = mu;
     for (int k = 0; k < n_alpha; ++k) A.alphas[k] = alphas[k];
     for (int k = 0; k < 5; ++k) A.w5[k] = w5[k];
     A.cost = cost; A.best_index = best_index; A.best_cost = best_cost; A.u_out = u_out; A.x_out = x_out; A.gains_out = gains_out;
     A.dv = dv; A.cand_out = cand_out; A.lq_out = lq_out;
-    A.dt = h->d_pt;
-    A.xy10 = reinterpret_cast<const float*>(h->d_red_all);
-    A.phi10 = h->d_phi10_all;
-    A.rad_all = h->d_rad_all;
-    A.cells = h->d_cells;
-    A.gx0 = h->pt.gx0; A.gy0 = h->pt.gy0; A.gnx = h->pt.gnx; A.gny = h->pt.gny;
-    for (int k = 0; k < 3; ++k) { A.red_off[k] = h->red_off[k]; A.red_len[k] = h->pt.red_len[k]; }
-    A.n_paths = h->pt.n_paths;
-    A.n_env = n_env; A.n_alpha = n_alpha; A.obs_dim = obs_dim(h->cfg); A.n_veh = h->cfg.n_veh; A.nd = A.obs_dim - 4 * A.n_veh;
-    A.horizon = horizon;
-    A.training = training; A.path_id = training ? 0 : path_id;
+    fill_tape_scene(h, n_env, horizon, A);
+    A.n_alpha = n_alpha; A.path_id = path_id;
     EB_HIP(eb::launch_rollout_tape_ilqr(h->cfg.task, A, (hipStream_t)stream));
     return EB_OK;
 }

@@ -20,13 +20,14 @@
 //              lanes of the wave instead of the E <= 32 of eb_rollout_tape_vjp.hip, at the same instruction time.
 //
 // Forward arithmetic and order are those of eb_rollout_tape_cand.hip (out5, cost) and of the gradient form of
-// eb_rollout_tape_vjp.hip (partials, tape), restated here as those files restate eb_rollout.hip's; the reverse is the shared device
-// function fed the same values.  tests/test_gpu_cand_grad.py holds every output to those entries bit for bit.  The queue's order
+// eb_rollout_tape_vjp.hip (partials, tape), restated here as those files restate eb_rollout.hip's (the closest-point lookup is the
+// family's one copy, tape_closest in eb_tape_device.h); the reverse is the shared device function fed the same values.  tests/test_gpu_cand_grad.py holds every output to those entries bit for bit.  The queue's order
 // varies from run to run; the sums do not.  A (row, candidate)'s bits depend on nothing but the row and that candidate's tape and
 // path.  No atomics to global memory, no scratch; fp32 state only.
 #include <hip/hip_runtime.h>
 
 #include "eb_cand_grad.h"
+#include "eb_tape_device.h"
 #include "eb_tape_grad_device.h"
 
 namespace eb {
@@ -37,7 +38,6 @@ constexpr int CG_ENV_LANES = 64;                        // the env role is wave 
 constexpr int CG_TAPE_FLOATS = 12;                      // floats per (env, candidate, step) in the LDS tape
 constexpr size_t CG_LDS_BUDGET = 64 * 1024;             // dynamic LDS per block: two blocks per CU at least
 constexpr int CG_RPT_MAX = 4;                           // records a lane keeps in registers: a tile holds at most 1024
-typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));
 
 struct CgSmem {
     float4 ego[CG_ENV_LANES];             // x, y, sin phi, cos phi of the pre-step pose of (env, candidate)
@@ -50,22 +50,6 @@ struct CgSmem {
 inline size_t cg_tape_bytes(int E, int K, int horizon) { return (size_t)CG_TAPE_FLOATS * horizon * E * K * sizeof(float); }
 inline size_t cg_lds_bytes(int E, int K, int n_veh, int horizon) {
     return cg_tape_bytes(E, K, horizon) + (size_t)E * K * n_veh * (sizeof(float4) + sizeof(float) + sizeof(unsigned short));
-}
-
-// closest point of (px, py) on path p: eb_rollout.hip:closest_cell_index<0, false>, restated (DAM:702-715)
-__device__ __forceinline__ int cg_closest(const TapeCandArgs& A, int p, int roff, float px, float py, float& rx, float& ry, float& rphi) {
-    const float* xy = A.xy10 + 2 * roff;
-    const float* ph = A.phi10 + roff;
-    const float fx = (px - A.gx0) * CELL_INV, fy = (py - A.gy0) * CELL_INV;
-    unsigned c = 0xffffffffu;
-    if (fx >= 0.0f && fx < (float)A.gnx && fy >= 0.0f && fy < (float)A.gny) c = A.cells[(p * A.gny + (int)fy) * A.gnx + (int)fx];
-    if (c == 0xffffffffu) {                                                    // off the corridor's grid: the pruned full search
-        const int n = p == 0 ? A.red_len[0] : p == 1 ? A.red_len[1] : A.red_len[2];
-        const int bi = closest_reduced_index(reinterpret_cast<const float2*>(xy), A.rad_all + 32 * p, n, px, py, 0, 1 << 30);
-        rx = xy[2 * bi]; ry = xy[2 * bi + 1]; rphi = ph[bi];
-        return bi;
-    }
-    return closest_in_range<0>(xy, ph, (int)(c & 0xffffu), (int)(c >> 16), px, py, rx, ry, rphi);
 }
 
 template <int TASK, int RPT>
@@ -128,7 +112,7 @@ __global__ __launch_bounds__(CG_THREADS, 3) void rollout_tape_cand_vjp_kernel(co
             float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;       // builds one obs per path, hier_decision.py:113-117)
             if (p >= 0) {
                 float rx = 0.0f, ry = 0.0f, rphi = 0.0f;
-                cg_closest(A, p, roff, st[3], st[4], rx, ry, rphi);
+                tape_closest(A, p, roff, st[3], st[4], rx, ry, rphi);
                 t0 = two2one<TASK>(st[3], st[4], rx, ry);                       // DAM:758
                 t1 = deal_with_phi_diff(st[5] - rphi);                          // DAM:759
                 t2 = st[0] - EXP_V;                                             // DAM:760
@@ -223,7 +207,7 @@ __global__ __launch_bounds__(CG_THREADS, 3) void rollout_tape_cand_vjp_kernel(co
             float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;
             if (p >= 0) {                                                       // DAM:334-353
                 float rx = 0.0f, ry = 0.0f, rphi = 0.0f;
-                cg_closest(A, p, roff, nx[3], nx[4], rx, ry, rphi);
+                tape_closest(A, p, roff, nx[3], nx[4], rx, ry, rphi);
                 t0 = two2one<TASK>(nx[3], nx[4], rx, ry);                       // DAM:758
                 t1 = deal_with_phi_diff(nx[5] - rphi);                          // DAM:759
                 t2 = nx[0] - EXP_V;                                             // DAM:760

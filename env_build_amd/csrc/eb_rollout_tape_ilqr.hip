@@ -16,34 +16,19 @@
 //   sweep        thread 0 of the env alone, last step first: ilqr::step_model (ten grad::env_vjp evaluations and the Gauss-Newton
 //                terms) and ilqr::riccati_step out of LDS; the symmetric 6 x 6 value matrix lives in registers, in double.
 // One thread per env in pass 2 and in the sweep: the launch is latency-bound there, and DESIGN.md §14 says what that costs.
+// The closest-point lookup is tape_closest of eb_tape_device.h, shared with the other tape kernels.
 // No atomics, no scratch; fp32 state only.
 #include <hip/hip_runtime.h>
 
 #include "eb_ilqr.h"
 #include "eb_env_device.h"
+#include "eb_tape_device.h"
 #include "eb_ilqr_device.h"
 
 namespace eb {
 namespace {
 
 constexpr int IL_THREADS = 256;
-typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));   // 8-byte access, 4-byte aligned: the caller's tape pointer
-
-// closest point of (px, py) on path p: eb_rollout.hip:closest_cell_index<0, false>, restated (DAM:702-715)
-__device__ __forceinline__ void il_closest(const TapeIlqrArgs& A, int p, int roff, float px, float py, float& rx, float& ry, float& rphi) {
-    const float* xy = A.xy10 + 2 * roff;
-    const float* ph = A.phi10 + roff;
-    const float fx = (px - A.gx0) * CELL_INV, fy = (py - A.gy0) * CELL_INV;
-    unsigned c = 0xffffffffu;
-    if (fx >= 0.0f && fx < (float)A.gnx && fy >= 0.0f && fy < (float)A.gny) c = A.cells[(p * A.gny + (int)fy) * A.gnx + (int)fx];
-    if (c == 0xffffffffu) {                                                    // off the corridor's grid: the pruned full search
-        const int n = p == 0 ? A.red_len[0] : p == 1 ? A.red_len[1] : A.red_len[2];
-        const int bi = closest_reduced_index(reinterpret_cast<const float2*>(xy), A.rad_all + 32 * p, n, px, py, 0, 1 << 30);
-        rx = xy[2 * bi]; ry = xy[2 * bi + 1]; rphi = ph[bi];
-        return;
-    }
-    closest_in_range<0>(xy, ph, (int)(c & 0xffffu), (int)(c >> 16), px, py, rx, ry, rphi);
-}
 
 struct IlLane {
     int tid, el, ge, p, roff;
@@ -134,7 +119,7 @@ __device__ __forceinline__ float il_rollout(const TapeIlqrArgs& A, const IlLane&
             float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;
             if (L.p >= 0) {                                                 // DAM:334-353
                 float rx = 0.0f, ry = 0.0f, rphi = 0.0f;
-                il_closest(A, L.p, L.roff, nx[3], nx[4], rx, ry, rphi);
+                tape_closest(A, L.p, L.roff, nx[3], nx[4], rx, ry, rphi);
                 t0 = two2one<TASK>(nx[3], nx[4], rx, ry);                   // DAM:758
                 t1 = deal_with_phi_diff(nx[5] - rphi);                      // DAM:759
                 t2 = nx[0] - EXP_V;                                         // DAM:760

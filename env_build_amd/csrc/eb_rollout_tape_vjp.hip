@@ -20,12 +20,13 @@
 //              transpose, clip, tracking, walls, rewards and action transform of eb_grad_device.h, last step first.
 //
 // Forward arithmetic and order are those of eb_rollout.hip's tape kernel (the pieces that live in that translation unit and not in a
-// header — closest_cell_index<0, false>, the head row, the queue's penalty sums — are restated here; tests/test_gpu_tape_grad.py
-// holds them to the original bit for bit).  Reverse arithmetic is that of eb_rollout_vjp.hip.  The queue's order varies from run to
+// header — the head row, the queue's penalty sums — are restated here; closest_cell_index<0, false> is restated once for the whole
+// tape family, as tape_closest in eb_tape_device.h; tests/test_gpu_tape_grad.py holds them to the original bit for bit).  Reverse arithmetic is that of eb_rollout_vjp.hip.  The queue's order varies from run to
 // run; the sums do not.  A row's bits depend on nothing but the row.  No atomics to global memory, no scratch; fp32 state only.
 #include <hip/hip_runtime.h>
 
 #include "eb_grad.h"
+#include "eb_tape_device.h"
 #include "eb_tape_grad_device.h"
 
 namespace eb {
@@ -36,7 +37,6 @@ constexpr int TV_TAPE_FLOATS = 12;                      // floats per env-step i
 constexpr size_t TV_LDS_BUDGET = 64 * 1024;             // dynamic LDS per block: two blocks per CU at least
 constexpr int TV_MAX_HORIZON = 128;
 constexpr int TV_RPT_MAX = 4;                           // records a lane keeps in registers: a tile holds at most 1024
-typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));
 
 struct TvSmem {
     float4 ego[32];                       // x, y, sin phi, cos phi of the pre-step pose
@@ -50,22 +50,6 @@ struct TvSmem {
 inline size_t tv_queue_bytes(int E, int n_veh) { return (size_t)E * n_veh * (sizeof(float4) + sizeof(float) + sizeof(unsigned short)); }
 inline size_t tv_lds_bytes(int E, int n_veh, int horizon, bool grad) {
     return tv_queue_bytes(E, n_veh) + (grad ? (size_t)TV_TAPE_FLOATS * horizon * E * sizeof(float) : 0);
-}
-
-// closest point of (px, py) on path p: eb_rollout.hip:closest_cell_index<0, false>, restated (DAM:702-715)
-__device__ __forceinline__ int tv_closest(const TapeVjpArgs& A, int p, int roff, float px, float py, float& rx, float& ry, float& rphi) {
-    const float* xy = A.xy10 + 2 * roff;
-    const float* ph = A.phi10 + roff;
-    const float fx = (px - A.gx0) * CELL_INV, fy = (py - A.gy0) * CELL_INV;
-    unsigned c = 0xffffffffu;
-    if (fx >= 0.0f && fx < (float)A.gnx && fy >= 0.0f && fy < (float)A.gny) c = A.cells[(p * A.gny + (int)fy) * A.gnx + (int)fx];
-    if (c == 0xffffffffu) {                                                    // off the corridor's grid: the pruned full search
-        const int n = p == 0 ? A.red_len[0] : p == 1 ? A.red_len[1] : A.red_len[2];
-        const int bi = closest_reduced_index(reinterpret_cast<const float2*>(xy), A.rad_all + 32 * p, n, px, py, 0, 1 << 30);
-        rx = xy[2 * bi]; ry = xy[2 * bi + 1]; rphi = ph[bi];
-        return bi;
-    }
-    return closest_in_range<0>(xy, ph, (int)(c & 0xffffu), (int)(c >> 16), px, py, rx, ry, rphi);
 }
 
 template <int TASK, int RPT, bool GRAD>
@@ -212,7 +196,7 @@ __global__ __launch_bounds__(TV_THREADS, 3) void rollout_tape_vjp_kernel(const T
             bi = 0;
             if (p >= 0) {                                                       // DAM:334-353
                 float rx = 0.0f, ry = 0.0f, rphi = 0.0f;
-                bi = tv_closest(A, p, roff, nx[3], nx[4], rx, ry, rphi);
+                bi = tape_closest(A, p, roff, nx[3], nx[4], rx, ry, rphi);
                 t0 = two2one<TASK>(nx[3], nx[4], rx, ry);                       // DAM:758
                 t1 = deal_with_phi_diff(nx[5] - rphi);                          // DAM:759
                 t2 = nx[0] - EXP_V;                                             // DAM:760

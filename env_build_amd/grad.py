@@ -22,6 +22,7 @@ eb_rollout_tape launch, backward one eb_rollout_tape_vjp launch (csrc/eb_rollout
 import torch
 
 from . import _capi
+from ._tape_args import check_rows, need_fp32
 from .dynamics_and_models import EnvironmentModel, DevArray, _dev, _stream, _unwrap
 
 __all__ = ['DifferentiableEnvironmentModel', 'rollout_step', 'rollout_tape', 'tape_vjp_max_horizon']
@@ -188,11 +189,8 @@ def rollout_tape(model, obses, action_tape):
     supplies the task, the slot modes and the path choice; its own state is not touched.  A tape longer than
     tape_vjp_max_horizon(model) falls back to H step launches that keep every pre-step obs plus eb_rollout_chain_vjp — the same
     bits, 2 H launches."""
-    if model.state_dtype != torch.float32:
-        raise _capi.EbError('grad.rollout_tape: fp32 state only (the fp16-state kernels have no reverse pass)')
-    obs = _graph_tensor(obses, model.device, 'obses')
-    if obs.dim() != 2 or obs.shape[1] != model.obs_dim:
-        raise ValueError('obses must be [B, %d]; got %s' % (model.obs_dim, tuple(obs.shape)))
+    need_fp32(model, 'grad.rollout_tape: fp32 state only (the fp16-state kernels have no reverse pass)')
+    obs = check_rows(model, _graph_tensor(obses, model.device, 'obses'))
     tape = _graph_tensor(action_tape, model.device, 'action_tape')
     if tape.dim() != 3 or tape.shape[1] != obs.shape[0] or tape.shape[2] != 2 or tape.shape[0] < 1:
         raise ValueError('action_tape must be [H, %d, 2]; got %s' % (obs.shape[0], tuple(tape.shape)))

@@ -21,7 +21,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _capi
+from ._tape_args import check_rows, five_weights, need_fp32, path_args
 from .dynamics_and_models import _dev, _stream
 from .mpc import DEFAULT_WEIGHTS
 
@@ -271,18 +271,14 @@ def rollout_tape_ilqr(model, obses, u_nom, x_nom=None, gains=None, alphas=(), mu
     x_nom [H, 6, B] and gains [H, 14, B] come together (a previous launch's x and gains) or not at all; without them alphas must be
     empty.  mu [B] >= 0 or None: the regularisation added to Q_uu's diagonal.  ref_indexes [B] (mode='training', None = the model's
     own) or path_index (mode='selecting', None = the model's current path).  `model`'s own state is not touched."""
-    if model.state_dtype != torch.float32:
-        raise _capi.EbError('ilqr.rollout_tape_ilqr: fp32 state only')
+    need_fp32(model, 'ilqr.rollout_tape_ilqr: fp32 state only')
     model.api.ilqr_fn('eb_rollout_tape_ilqr')              # EbError before any work when the library has no such entry
     want = tuple(want)
     for k in want:
         if k not in OUTPUTS:
             raise ValueError('want: a subset of %r; got %r' % (OUTPUTS, k))
-    if weights is not None and len(tuple(weights)) != 5:
-        raise ValueError('weights: five floats, one per out5 row')
-    obs = _dev(obses, model.device).detach().contiguous()
-    if obs.dim() != 2 or obs.shape[1] != model.obs_dim:
-        raise ValueError('obses must be [B, %d]; got %s' % (model.obs_dim, tuple(obs.shape)))
+    five_weights(weights, optional=True)
+    obs = check_rows(model, _dev(obses, model.device).detach().contiguous())
     B = obs.shape[0]
     u = _dev(u_nom, model.device).detach().contiguous()
     if u.dim() != 3 or u.shape[1] != B or u.shape[2] != 2 or u.shape[0] < 1:
@@ -302,12 +298,6 @@ def rollout_tape_ilqr(model, obses, u_nom, x_nom=None, gains=None, alphas=(), mu
         m = _dev(mu, model.device).detach().contiguous()
         if tuple(m.shape) != (B,):
             raise ValueError('mu must be [%d]; got %s' % (B, tuple(m.shape)))
-    ri, pid = None, 0
-    if model.mode == 'training':
-        ri = model._path_args()[0] if ref_indexes is None else _dev(ref_indexes, model.device, torch.int32)
-        if ri is not None and tuple(ri.shape) != (B,):
-            raise ValueError('ref_indexes must be [%d]; got %s' % (B, tuple(ri.shape)))
-    else:
-        pid = int(model._path_args()[1] if path_index is None else path_index)
+    ri, pid = path_args(model, B, ref_indexes, path_index)
     alphas = tuple(float(a) for a in alphas)
     return launch(model, obs, u, xn, gn, alphas, m, ri, pid, weights, alloc_outputs(H, B, len(alphas), want, obs.device))

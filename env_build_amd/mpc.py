@@ -54,7 +54,7 @@ import ctypes as C
 
 import torch
 
-from . import _capi
+from ._tape_args import check_rows, five_weights, need_fp32, tapes_or_zeros
 
 __all__ = ['OpenLoopMPC', 'SamplingMPC', 'ILQRMPC', 'cost_from_out5', 'projected_gradient', 'sampling_loop', 'ilqr_loop', 'best_start',
            'DEFAULT_WEIGHTS']
@@ -187,12 +187,9 @@ class OpenLoopMPC(object):
     def __init__(self, model, horizon=25, weights=DEFAULT_WEIGHTS, iterations=60, ls_trials=3, c1=1e-4, fused_line_search=False):
         from .dynamics_and_models import _dev, _stream
         self._dev_fn, self._stream_fn = _dev, _stream
-        if model.state_dtype != torch.float32:
-            raise _capi.EbError('OpenLoopMPC: the reverse pass is fp32-state only')
+        need_fp32(model, 'OpenLoopMPC: the reverse pass is fp32-state only')
         self.model, self.horizon = model, int(horizon)
-        self.weights = tuple(float(v) for v in weights)
-        if len(self.weights) != 5:
-            raise ValueError('weights: five floats, one per out5 row')
+        self.weights = five_weights(weights)
         self.iterations, self.ls_trials, self.c1 = int(iterations), int(ls_trials), float(c1)
         self._fn = model.api.grad_fn('eb_rollout_tape_vjp')          # EbError here when the library has no reverse pass
         limit = C.c_int32(0)
@@ -282,6 +279,16 @@ class OpenLoopMPC(object):
         u = U.gather(0, idx.view(1, 1, -1, 1).expand(1, U.shape[1], U.shape[2], 2))[0]
         return u.contiguous(), J.gather(0, idx.view(1, -1))[0], idx
 
+    def _per_path(self, obses, tapes, what):
+        """one candidate per path of the task -> (obs [B, D], tapes [P, H, B, 2] (None = zeros), ref_idx [P, B] or None, path ids or None)"""
+        m = self.model
+        obs = check_rows(m, self._dev_fn(obses, m.device).detach())
+        P, B = len(m.ref_path.path_list), obs.shape[0]
+        U = tapes_or_zeros(m, tapes, (P, self.horizon, B, 2), what)
+        if m.mode == 'training':
+            return obs, U, torch.arange(P, dtype=torch.int32, device=m.device).view(P, 1).expand(P, B).contiguous(), None
+        return obs, U, None, list(range(P))
+
     def solve_paths(self, obses, u_init=None, iterations=None, check_every=0, tol=1e-3):
         """One start per path of the task, candidate p on path p from the row's tracking error on THAT path (retrack; the reference
         builds one obs per path, hier_decision.py:113-117), all optimised together; the best path per env is returned — "optimise a
@@ -289,20 +296,7 @@ class OpenLoopMPC(object):
         u_init: None = the zero tapes, or [P, H, B, 2].  info as projected_gradient's with a start dimension, plus path_index [B] (the
         first minimum; a NaN never wins), J_paths [P, B], u_paths [P, H, B, 2], launches (launch_count(P, iterations)).  The
         hysteresis of hier_decision.py:121 stays with the caller."""
-        m = self.model
-        obs = self._dev_fn(obses, m.device).detach()
-        if obs.dim() != 2 or obs.shape[1] != m.obs_dim:
-            raise ValueError('obses must be [B, %d]; got %s' % (m.obs_dim, tuple(obs.shape)))
-        P, B = len(m.ref_path.path_list), obs.shape[0]
-        if u_init is None:
-            U0 = torch.zeros((P, self.horizon, B, 2), dtype=torch.float32, device=m.device)
-        else:
-            U0 = self._dev_fn(u_init, m.device).detach()
-            if tuple(U0.shape) != (P, self.horizon, B, 2):
-                raise ValueError('u_init must be [%d, %d, %d, 2]; got %s' % (P, self.horizon, B, tuple(U0.shape)))
-        ri, ids = None, list(range(P))
-        if m.mode == 'training':
-            ri, ids = torch.arange(P, dtype=torch.int32, device=m.device).view(P, 1).expand(P, B).contiguous(), None
+        obs, U0, ri, ids = self._per_path(obses, u_init, 'u_init')
         U, J, info = self._solve_all(obs, U0, ri, ids, True, iterations, check_every, tol)
         u, J_best, idx = self._pick(U, J)
         info.update(path_index=idx, J_paths=J, u_paths=U.contiguous())
@@ -315,21 +309,8 @@ class OpenLoopMPC(object):
         [P, H, B, 2] or None = the zero tapes.  J is eb_rollout_tape_cand's `cost` with this solver's weights.  One launch; the
         hysteresis of hier_decision.py:121 stays with the caller."""
         from .cand import launch_chunks
-        m = self.model
-        obs = self._dev_fn(obses, m.device).detach()
-        if obs.dim() != 2 or obs.shape[1] != m.obs_dim:
-            raise ValueError('obses must be [B, %d]; got %s' % (m.obs_dim, tuple(obs.shape)))
-        P, B = len(m.ref_path.path_list), obs.shape[0]
-        if tapes is None:
-            U = torch.zeros((P, self.horizon, B, 2), dtype=torch.float32, device=m.device)
-        else:
-            U = self._dev_fn(tapes, m.device).detach()
-            if tuple(U.shape) != (P, self.horizon, B, 2):
-                raise ValueError('tapes must be [%d, %d, %d, 2]; got %s' % (P, self.horizon, B, tuple(U.shape)))
-        ri, ids = None, list(range(P))
-        if m.mode == 'training':
-            ri, ids = torch.arange(P, dtype=torch.int32, device=m.device).view(P, 1).expand(P, B).contiguous(), None
-        _out5, J, launches = launch_chunks(m, obs, U, ri, ids, True, self.weights, False)
+        obs, U, ri, ids = self._per_path(obses, tapes, 'tapes')
+        _out5, J, launches = launch_chunks(self.model, obs, U, ri, ids, True, self.weights, False)
         self.launches += launches
         return J, first_minimum(J)
 
@@ -347,9 +328,7 @@ class OpenLoopMPC(object):
         if starts not in ('best', 'all'):
             raise ValueError("starts must be 'best' or 'all'; got %r" % (starts,))
         m = self.model
-        obs = self._dev_fn(obses, m.device).detach()
-        if obs.dim() != 2 or obs.shape[1] != m.obs_dim:
-            raise ValueError('obses must be [B, %d]; got %s' % (m.obs_dim, tuple(obs.shape)))
+        obs = check_rows(m, self._dev_fn(obses, m.device).detach())
         B = obs.shape[0]
         ri, pid = self._paths(ref_indexes, path_index)
         if u_init is None:
@@ -387,6 +366,22 @@ class OpenLoopMPC(object):
         """The tape shifted by one step, its last action repeated: the next control step's u_init (the line mpc/main.py:571 left
         commented out)."""
         return torch.cat([u[1:], u[-1:]], 0).contiguous()
+
+
+def _finish(mpc, obs, u, J_kernel, info, ri, pid, first, prefix):
+    """The tail of SamplingMPC.solve and ILQRMPC.solve: ONE independent value-only evaluation of the stage's tape u gives the returned
+    J; with mpc.polish the zero tape and u then go through polish.solve(starts='all') and info keeps the stage's own result as
+    u_<prefix> / J_<prefix>.  first: mpc.launches when the solve began.  -> (u, J, info)"""
+    u = u.contiguous()
+    J = mpc._value.value_and_grad(obs, u, ri, pid, need_grad=False)[0]
+    mpc.launches += 1
+    info.update(J_kernel=J_kernel, launches=mpc.launches - first)
+    if mpc.polish is not None:
+        starts = torch.stack([torch.zeros_like(u), u])
+        up, Jp, pinfo = mpc.polish.solve(obs, ref_indexes=ri, path_index=None if ri is not None else pid, u_init=starts, starts='all')
+        info.update({'u_' + prefix: u, 'J_' + prefix: J}, polish=pinfo, launches=info['launches'] + pinfo['launches'])
+        u, J = up, Jp
+    return u, J, info
 
 
 def sampling_loop(step, u0, iterations, sigma, sigma_decay=1.0, counter=0):
@@ -429,13 +424,10 @@ class SamplingMPC(object):
         from .dynamics_and_models import _dev
         from . import sample as _sample
         self._dev_fn, self._sample = _dev, _sample
-        if model.state_dtype != torch.float32:
-            raise _capi.EbError('SamplingMPC: fp32 state only')
+        need_fp32(model, 'SamplingMPC: fp32 state only')
         model.api.sample_fn('eb_rollout_tape_sample')                # EbError here when the library has no sampled-tape rollout
         self.model, self.horizon = model, int(horizon)
-        self.weights = tuple(float(v) for v in weights)
-        if len(self.weights) != 5:
-            raise ValueError('weights: five floats, one per out5 row')
+        self.weights = five_weights(weights)
         self.n_samples, self.iterations = int(n_samples), int(iterations)
         limit = _sample.tape_sample_max(model, self.horizon)         # ValueError for a horizon outside 1..128
         if self.n_samples < 1 or self.n_samples > limit:
@@ -462,17 +454,10 @@ class SamplingMPC(object):
         descent is the default solver's — and u, J are the polished ones; info then also has u_sampled, J_sampled and `polish`
         (polish.solve's info), and launches counts both stages."""
         m = self.model
-        obs = self._dev_fn(obses, m.device).detach()
-        if obs.dim() != 2 or obs.shape[1] != m.obs_dim:
-            raise ValueError('obses must be [B, %d]; got %s' % (m.obs_dim, tuple(obs.shape)))
+        obs = check_rows(m, self._dev_fn(obses, m.device).detach())
         B = obs.shape[0]
         ri, pid = _solve_path_args(m, self._dev_fn, ref_indexes, path_index, 'SamplingMPC.solve')
-        if u_init is None:
-            u0 = torch.zeros((self.horizon, B, 2), dtype=torch.float32, device=m.device)
-        else:
-            u0 = self._dev_fn(u_init, m.device).detach()
-            if tuple(u0.shape) != (self.horizon, B, 2):
-                raise ValueError('u_init must be [%d, %d, 2]; got %s' % (self.horizon, B, tuple(u0.shape)))
+        u0 = tapes_or_zeros(m, u_init, (self.horizon, B, 2), 'u_init')
         inv = 0.0 if self.lam == float('inf') else 1.0 / self.lam
         first = self.launches
 
@@ -482,16 +467,7 @@ class SamplingMPC(object):
             self.launches += 1
             return out['cost'][0], out['best_tape'], out['best_cost'], out['mean_tape']
         u, J_kernel, info = sampling_loop(step, u0, self.iterations, self.sigma, self.sigma_decay, counter)
-        u = u.contiguous()
-        J = self._value.value_and_grad(obs, u, ri, pid, need_grad=False)[0]
-        self.launches += 1
-        info.update(J_kernel=J_kernel, launches=self.launches - first)
-        if self.polish is not None:
-            starts = torch.stack([torch.zeros_like(u), u])
-            up, Jp, pinfo = self.polish.solve(obs, ref_indexes=ri, path_index=None if ri is not None else pid, u_init=starts, starts='all')
-            info.update(u_sampled=u, J_sampled=J, polish=pinfo, launches=info['launches'] + pinfo['launches'])
-            u, J = up, Jp
-        return u, J, info
+        return _finish(self, obs, u, J_kernel, info, ri, pid, first, 'sampled')
 
     warm_start = staticmethod(OpenLoopMPC.warm_start)
 
@@ -535,13 +511,10 @@ class ILQRMPC(object):
         from .dynamics_and_models import _dev
         from . import ilqr as _ilqr
         self._dev_fn, self._ilqr = _dev, _ilqr
-        if model.state_dtype != torch.float32:
-            raise _capi.EbError('ILQRMPC: fp32 state only')
+        need_fp32(model, 'ILQRMPC: fp32 state only')
         model.api.ilqr_fn('eb_rollout_tape_ilqr')                    # EbError here when the library has no iLQR iteration
         self.model, self.horizon = model, int(horizon)
-        self.weights = tuple(float(v) for v in weights)
-        if len(self.weights) != 5:
-            raise ValueError('weights: five floats, one per out5 row')
+        self.weights = five_weights(weights)
         if self.weights[0] > 0 or min(self.weights[1:]) < 0:
             raise ValueError('ILQRMPC: weights must satisfy w[0] <= 0 and w[1..4] >= 0')
         self.iterations = int(iterations)
@@ -586,17 +559,10 @@ class ILQRMPC(object):
         polish.solve(u_init=stack([zero, u_ilqr]), starts='all') — start 0 is the zero tape on purpose: its descent is the default
         solver's — and u, J are the polished ones; info then also has u_ilqr, J_ilqr and `polish`, and launches counts both stages."""
         m = self.model
-        obs = self._dev_fn(obses, m.device).detach().contiguous()
-        if obs.dim() != 2 or obs.shape[1] != m.obs_dim:
-            raise ValueError('obses must be [B, %d]; got %s' % (m.obs_dim, tuple(obs.shape)))
+        obs = check_rows(m, self._dev_fn(obses, m.device).detach().contiguous())
         B = obs.shape[0]
         ri, pid = _solve_path_args(m, self._dev_fn, ref_indexes, path_index, 'ILQRMPC.solve')
-        if u_init is None:
-            u0 = torch.zeros((self.horizon, B, 2), dtype=torch.float32, device=m.device)
-        else:
-            u0 = self._dev_fn(u_init, m.device).detach().contiguous()
-            if tuple(u0.shape) != (self.horizon, B, 2):
-                raise ValueError('u_init must be [%d, %d, 2]; got %s' % (self.horizon, B, tuple(u0.shape)))
+        u0 = tapes_or_zeros(m, u_init, (self.horizon, B, 2), 'u_init').contiguous()
         first_out, sets = self._ping_pong(B, obs.device)
         start = self.launches
         turn = [0]
@@ -613,15 +579,6 @@ class ILQRMPC(object):
             self.launches += 1
             return out
         u, J_kernel, info = ilqr_loop(step, u0, self.iterations, self.mu0)
-        u = u.contiguous()
-        J = self._value.value_and_grad(obs, u, ri, pid, need_grad=False)[0]
-        self.launches += 1
-        info.update(J_kernel=J_kernel, launches=self.launches - start)
-        if self.polish is not None:
-            starts = torch.stack([torch.zeros_like(u), u])
-            up, Jp, pinfo = self.polish.solve(obs, ref_indexes=ri, path_index=None if ri is not None else pid, u_init=starts, starts='all')
-            info.update(u_ilqr=u, J_ilqr=J, polish=pinfo, launches=info['launches'] + pinfo['launches'])
-            u, J = up, Jp
-        return u, J, info
+        return _finish(self, obs, u, J_kernel, info, ri, pid, start, 'ilqr')
 
     warm_start = staticmethod(OpenLoopMPC.warm_start)

@@ -19,7 +19,7 @@ import math
 import numpy as np
 import torch
 
-from . import _capi
+from ._tape_args import check_rows, five_weights, need_fp32, path_args
 from .dynamics_and_models import _dev, _stream
 from .mpc import DEFAULT_WEIGHTS, first_minimum
 
@@ -152,33 +152,23 @@ def rollout_tape_samples(model, obses, nominal, n_samples, seed, counter, sigma,
     sigma: two floats >= 0, the noise scale per action component; beta in [0, 1): AR(1) smoothing over the steps; (seed, counter) and
     env_ids [B] (None: the row index) key the noise; ref_indexes [B] (mode='training', None = the model's own) or path_index
     (mode='selecting', None = the model's current path).  `model`'s own state is not touched."""
-    if model.state_dtype != torch.float32:
-        raise _capi.EbError('sample.rollout_tape_samples: fp32 state only')
+    need_fp32(model, 'sample.rollout_tape_samples: fp32 state only')
     model.api.sample_fn('eb_rollout_tape_sample')          # EbError before any work when the library has no such entry
     want = tuple(want)
     for k in want:
         if k not in ('cost', 'best', 'mean'):
             raise ValueError("want: a subset of ('cost', 'best', 'mean'); got %r" % (k,))
-    if weights is not None and len(tuple(weights)) != 5:
-        raise ValueError('weights: five floats, one per out5 row')
+    five_weights(weights, optional=True)
     if len(tuple(sigma)) != 2:
         raise ValueError('sigma: two floats, one per action component')
     if not lam > 0:
         raise ValueError('lam must be positive (inf: the plain average)')
-    obs = _dev(obses, model.device).detach().contiguous()
-    if obs.dim() != 2 or obs.shape[1] != model.obs_dim:
-        raise ValueError('obses must be [B, %d]; got %s' % (model.obs_dim, tuple(obs.shape)))
+    obs = check_rows(model, _dev(obses, model.device).detach().contiguous())
     B = obs.shape[0]
     nom = _dev(nominal, model.device).detach().contiguous()
     if nom.dim() != 3 or nom.shape[1] != B or nom.shape[2] != 2 or nom.shape[0] < 1:
         raise ValueError('nominal must be [H, %d, 2]; got %s' % (B, tuple(nom.shape)))
-    ri, pid = None, 0
-    if model.mode == 'training':
-        ri = model._path_args()[0] if ref_indexes is None else _dev(ref_indexes, model.device, torch.int32)
-        if ri is not None and tuple(ri.shape) != (B,):
-            raise ValueError('ref_indexes must be [%d]; got %s' % (B, tuple(ri.shape)))
-    else:
-        pid = int(model._path_args()[1] if path_index is None else path_index)
+    ri, pid = path_args(model, B, ref_indexes, path_index)
     ids = None
     if env_ids is not None:
         ids = _dev(env_ids, model.device, torch.int32).contiguous()

@@ -70,6 +70,25 @@ def test_product_never_imports_the_oracle():
                 assert not re.search(r'^\s*(from|import)\s+oracle\b', text, flags=re.M), f
 
 
+def test_every_optional_family_is_refused_by_name_on_a_library_without_it():
+    """_capi.FAMILIES drives the binder and __getattr__: on the oracle library, which exports none of the optional families, every
+    symbol of every row is refused with that row's own label, and the row's one-line method agrees."""
+    api = oracle_lib()
+    rows = _capi.FAMILIES
+    assert [row[5] for row in rows.values()] == [_capi.GRAD_PROTOTYPES, _capi.CAND_PROTOTYPES, _capi.CAND_GRAD_PROTOTYPES,
+                                                 _capi.SAMPLE_PROTOTYPES, _capi.ILQR_PROTOTYPES]
+    for family, (header, label, _abi, version_symbol, version, prototypes) in rows.items():
+        assert os.path.isfile(os.path.join(ROOT, 'include', header)) and version_symbol in prototypes
+        assert version == getattr(_capi, 'EB_%s_ABI_VERSION' % family.upper())
+        for symbol in prototypes:
+            with pytest.raises(_capi.EbError) as e:
+                getattr(api, symbol[len('eb_'):])
+            assert label in str(e.value) and header in str(e.value), symbol
+            with pytest.raises(_capi.EbError) as e:
+                getattr(api, family + '_fn')(symbol)
+            assert label in str(e.value)
+
+
 def test_oracle_exports_and_error_paths():
     api = oracle_lib()
     for name in header_symbols():
