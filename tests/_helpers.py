@@ -6,7 +6,7 @@ import subprocess
 
 import numpy as np
 
-from env_build_amd import _capi
+from env_build_amd import _capi, build as eb_build
 from env_build_amd.endtoend_env_utils import VEHICLE_MODE_LIST, tiled_mode_list
 from env_build_amd.ref_path_tables import build_ref_paths
 
@@ -45,6 +45,15 @@ def oracle_lib():
         _oracle = _capi.CApi(ORACLE_SO)
         assert _oracle.backend == 'oracle'
     return _oracle
+
+
+def build_host_harness(tmp_path_factory, source, tag):
+    """tests/<source> (a kernel's __host__ __device__ text behind extern "C" drivers) compiled for the host -> the loaded lib<tag>.so"""
+    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+    out = str(tmp_path_factory.mktemp(tag) / ('lib%s.so' % tag))
+    subprocess.check_call([hipcc, '--offload-arch=gfx950', '-O2', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared',
+                           '-I', eb_build.CSRC, os.path.join(ROOT, 'tests', source), '-o', out])
+    return C.CDLL(out)
 
 
 def golden(name):

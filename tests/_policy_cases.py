@@ -1,0 +1,58 @@
+"""What the CPU and the GPU policy tests share: seeded layers and their plain torch fp32 forward (utils/model.py:18-43 +
+utils/policy.py:85-92 restated), the G13 / G14 fixture names, G13's weight lists and G14's shield check.  A helper module: pytest does
+not collect it, and torch is imported where it is used."""
+import glob
+import os
+
+import numpy as np
+
+from env_build_amd.policy import orthogonal
+from tests._helpers import GOLDEN, close
+
+# G13: the reference's own MLPNet / Policy4Toyota / Preprocessor / LoadPolicy.run_batch over the tf.keras stand-in
+G13 = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(GOLDEN, 'g13_policy_*.npz')))
+# G14: HierarchicalDecision.is_safe / safe_shield (hier_decision.py:89-107) from the reference's own method bodies
+G14 = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(GOLDEN, 'g14_shield_*.npz')))
+
+
+def make_layers(rng, obs_dim, n_hidden, n_units, out_dim, bias_scale=0.1):
+    dims = [obs_dim] + [n_units] * n_hidden + [out_dim]
+    layers = []
+    for L in range(n_hidden + 1):
+        gain = np.sqrt(2.) if L < n_hidden else 1.
+        layers.append((orthogonal(rng, dims[L], dims[L + 1], gain),
+                       (bias_scale * rng.standard_normal(dims[L + 1])).astype(np.float32)))
+    return layers
+
+
+def torch_mlp(layers, obs, hidden_act, out_act, scale=None):
+    import torch
+    acts = {'linear': lambda x: x, 'relu': torch.relu, 'elu': torch.nn.functional.elu, 'tanh': torch.tanh}
+    x = torch.from_numpy(obs)
+    if scale is not None:
+        x = x * torch.from_numpy(scale)
+    for L, (k, b) in enumerate(layers):
+        x = x @ torch.from_numpy(k) + torch.from_numpy(b)
+        x = acts[out_act if L == len(layers) - 1 else hidden_act](x)
+    return x.numpy()
+
+
+def g13_layers(g, model):
+    n = 2 * (int(g['hidden']) + 1)
+    ws = [g['%s_w%d' % (model, i)] for i in range(n)]
+    return [(ws[2 * i], ws[2 * i + 1]) for i in range(n // 2)]        # Keras order: kernel, bias per layer
+
+
+def g14_check(model, g, mlp):
+    """eb_shield_is_safe over the fixture's start states: the safe flags must equal the reference's, and the action
+    the shield lets through (the policy's, or (0, -1) when it starts) must match"""
+    obs, path = g['obs'], int(g['path_index'])
+    safe, punish, _, _ = model.shield_is_safe(mlp, obs, ref_idx=None, path_id=path, steps=5, penalty=0)
+    assert np.array_equal(safe, g['safe']), 'safe flags differ from the reference at %s' % np.flatnonzero(safe != g['safe'])
+    assert np.array_equal(punish > 0, g['safe'] == 0)
+    act = model.policy_run_batch(mlp, 2, obs, 1.0)
+    want = g['safe_action']
+    assert np.array_equal(g['shield_started'], 1 - g['safe'])
+    ok = g['safe'] == 1
+    close(act[ok], want[ok], 1e-5, 5e-6, 'G14 actions let through')
+    assert (want[~ok] == np.array([0., -1.], np.float32)).all()          # hier_decision.py:100, 105

@@ -17,42 +17,17 @@ straight 1 of 16, right 4 of 16 (the float64 run of the same lines on the refere
 and 9 of 9, 15 of 16, 15 of 16 rows pick the reference's best path.  Start k of a K-start solve repeats the bits of the single-start
 solve from U[k] on the GPU as it does on the CPU (asserted below)."""
 import ctypes as C
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 
 from env_build_amd import _capi
-from tests._helpers import ROOT, golden
+from tests._helpers import golden
 from tests._grad_cases import TASKS, check_columns, column_tolerance, edge_cases
-from tests.test_gpu_tape_grad import bits, same, synthetic_case, edge_synthetic_case
-from tests.test_gpu_tape_cand import CandModel, WEIGHTS, NATIVE, candidate_tapes, retracked_rows
-from tests.test_gpu_mpc import setup as mpc_setup
+from tests._tape import (NATIVE, WEIGHTS, CandGradModel, bits, candidate_tapes, edge_synthetic_case, load_example, mpc_setup, retracked_rows,
+                         same, synthetic_case)
 
 pytestmark = pytest.mark.gpu
-
-
-class CandGradModel(CandModel):
-    """CandModel + the entries of include/envbuild_cand_grad.h; t_cand_vjp takes and returns torch tensors on the device"""
-
-    def cand_grad_max(self, horizon=25):
-        v = C.c_int32(-1)
-        self.api.rollout_tape_cand_vjp_max(self.h, int(horizon), C.byref(v))
-        return v.value
-
-    def t_cand_vjp(self, obs0, tapes, ri=None, ref_ld=0, path_ids=None, path_id=1, retrack=False, w5=WEIGHTS[0], out5=True, cost=True,
-                   g_obs0=True, g_tapes=True):
-        torch = self.torch
-        K, H, n, nd = tapes.shape[0], tapes.shape[1], obs0.shape[0], self.D - 4 * self.n_veh
-        mk = lambda want, shape: torch.full(shape, float('nan'), device=self.dev) if want else None
-        o5, J, g0, gt = mk(out5, (K, H, 5, n)), mk(cost, (K, n)), mk(g_obs0, (K, n, nd)), mk(g_tapes, (K, H, n, 2))
-        w = None if w5 is None else (C.c_float * 5)(*[float(v) for v in w5])
-        ids = None if path_ids is None else (C.c_int32 * len(path_ids))(*[int(v) for v in path_ids])
-        self.api.rollout_tape_cand_vjp(self.h, n, K, H, self._ptr(obs0), self._ptr(tapes), self._ptr(ri), int(ref_ld),
-                                       None if ids is None else C.cast(ids, C.c_void_p), int(path_id), int(bool(retrack)), w,
-                                       self._ptr(o5), self._ptr(J), self._ptr(g0), self._ptr(gt), self.stream)
-        return o5, J, g0, gt
 
 
 def check_against_the_parents(m, obs0, tapes, ri, pid, what, w5):
@@ -454,9 +429,7 @@ def test_solve_paths_in_selecting_mode():
 
 
 def test_paths_example_runs_a_few_control_steps():
-    spec = importlib.util.spec_from_file_location('mpc_paths', os.path.join(ROOT, 'examples', 'mpc_paths.py'))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = load_example('mpc_paths')
     r = mod.run(n_env=128, control_steps=3, iterations=8)
     import torch
     assert torch.isfinite(r['J_first']).all() and bool((r['J_first'] <= r['J0_first']).all())

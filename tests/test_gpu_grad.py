@@ -3,15 +3,13 @@ fixtures of scripts/gen_golden_grad.py (G15, G16 and the edge scenes of G18) —
 and its invariants; the autograd façade (env_build_amd/grad.py) against the manual chain of C calls; the ADP example.
 
 Tolerance and the cap on excluded rows: tests/_grad_cases.py.  Every check prints max |g - g64| / E per column before it asserts."""
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 
 from env_build_amd import _capi
-from tests._helpers import DeviceModel, ROOT
+from tests._helpers import DeviceModel
 from tests._grad_cases import TASKS, MAX_EXCLUDED, cases, check_columns, edge_cases
+from tests._tape import load_example
 
 pytestmark = pytest.mark.gpu
 
@@ -206,19 +204,12 @@ def test_large_batch_has_the_bits_of_the_small_one_and_repeats_them():
     assert same_bits(again[0], big[0]) and same_bits(again[1], big[1])
 
 
-def _example():
-    spec = importlib.util.spec_from_file_location('adp_policy_gradient', os.path.join(ROOT, 'examples', 'adp_policy_gradient.py'))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 @pytest.mark.parametrize('task,mode', [('left', 'training'), ('right', 'selecting')])
 def test_autograd_through_a_policy_loop_equals_the_manual_chain(task, mode):
     import torch
     from env_build_amd.grad import DifferentiableEnvironmentModel
     from env_build_amd.dynamics_and_models import EnvironmentModel, DevArray
-    ex = _example()
+    ex = load_example('adp_policy_gradient')
     H, B = 5, 96
     dm = DifferentiableEnvironmentModel(task, 0, mode=mode, n_veh=16)
     obs0, ref = ex.start_states(dm, B, seed=3)
@@ -296,6 +287,6 @@ def test_differentiable_model_refuses_what_has_no_reverse_pass():
 
 
 def test_adp_example_runs_one_training_step():
-    r = _example().run(n_env=512, horizon=25, iterations=2)
+    r = load_example('adp_policy_gradient').run(n_env=512, horizon=25, iterations=2)
     assert len(r['losses']) == 2 and all(np.isfinite(r['losses']))
     assert np.isfinite(r['grad_norm']) and r['grad_norm'] > 0.0

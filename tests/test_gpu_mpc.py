@@ -10,37 +10,20 @@ may disagree (the fixtures hold rows on which the reference alone disagrees with
 
 Measured on an MI355X (60 iterations, the defaults), rows that disagree: left 2 of 9, straight 2 of 16, right 3 of 16; the float64
 run of the same lines on the reference's cost: 2 of 9, 1 of 16, 3 of 16."""
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 
-from tests._helpers import ROOT, golden
+from tests._grad_cases import TASKS
+from tests._tape import load_example, mpc_setup
 
 pytestmark = pytest.mark.gpu
-TASKS = ('left', 'straight', 'right')
-NATIVE = {'left': 8, 'straight': 9, 'right': 5}
-
-
-def setup(task):
-    import torch
-    from env_build_amd.dynamics_and_models import EnvironmentModel
-    from env_build_amd.mpc import OpenLoopMPC
-    z = golden('g17_mpc_%s' % task)
-    g5 = golden('g5_rollout_%s_N%d_training_nf0' % (task, NATIVE[task]))
-    rows = z['rows']
-    model = EnvironmentModel(task, 0, mode='training')
-    obs0 = torch.from_numpy(np.ascontiguousarray(g5['obs0'][rows])).to(model.device)
-    ref = torch.from_numpy(np.ascontiguousarray(g5['ref_idx'][rows].astype(np.int32))).to(model.device)
-    return z, model, OpenLoopMPC(model, horizon=int(z['horizon'])), obs0, ref
 
 
 @pytest.mark.parametrize('task', TASKS)
 def test_solver_invariants_and_agreement_with_the_reference_optimiser(task):
     import torch
     from env_build_amd.mpc import cost_from_out5
-    z, model, mpc, obs0, ref = setup(task)
+    z, model, mpc, obs0, ref = mpc_setup(task)
     B = obs0.shape[0]
     u, J, info = mpc.solve(obs0, ref_indexes=ref)
     assert u.shape == (25, B, 2) and J.shape == (B,) and torch.isfinite(J).all()
@@ -77,7 +60,7 @@ def test_solver_invariants_and_agreement_with_the_reference_optimiser(task):
 
 def test_warm_start_and_other_weights():
     import torch
-    z, model, mpc, obs0, ref = setup('straight')
+    z, model, mpc, obs0, ref = mpc_setup('straight')
     u, J, _ = mpc.solve(obs0, ref_indexes=ref, iterations=10)
     w = mpc.warm_start(u)
     u2, J2, info2 = mpc.solve(obs0, ref_indexes=ref, u_init=w, iterations=3)
@@ -93,9 +76,7 @@ def test_warm_start_and_other_weights():
 
 
 def test_mpc_example_runs_a_few_control_steps():
-    spec = importlib.util.spec_from_file_location('mpc_open_loop', os.path.join(ROOT, 'examples', 'mpc_open_loop.py'))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = load_example('mpc_open_loop')
     r = mod.run(n_env=128, control_steps=3, iterations=8)
     import torch
     assert torch.isfinite(r['J_first']).all() and bool((r['J_first'] <= r['J0_first']).all())

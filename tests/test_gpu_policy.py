@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from env_build_amd.synthetic import assemble_obs, make_rollout_inputs  # noqa: E402
 from tests._helpers import DeviceModel, HostModel, oracle_lib  # noqa: E402
-from tests.test_policy_oracle import make_layers, torch_mlp  # noqa: E402
+from tests._policy_cases import make_layers, torch_mlp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 PEN_RTOL = 1e-6
@@ -217,7 +217,7 @@ def test_policy_and_traffic_entry_points_reject_bad_arguments():
 
 # ---- G13: fixtures from the reference's own MLPNet / Policy4Toyota / Preprocessor / LoadPolicy.run_batch ----
 from tests._helpers import close, golden  # noqa: E402
-from tests.test_policy_oracle import G13, g13_layers  # noqa: E402
+from tests._policy_cases import G13, g13_layers  # noqa: E402
 
 
 @pytest.mark.parametrize('name', G13)
@@ -245,7 +245,7 @@ def test_g13_policy_fixtures_on_gpu_through_the_kernel_and_the_facade(name):
     close(lp.obj_value_batch(obs).numpy(), g['values'], 1e-5, 5e-6, 'GPU G13 facade obj_value_batch')
 
 
-from tests.test_policy_oracle import G14, g14_check  # noqa: E402
+from tests._policy_cases import G14, g14_check  # noqa: E402
 
 
 @pytest.mark.parametrize('name', G14)

@@ -456,7 +456,7 @@ def test_env_step_validates_before_it_launches_and_set_paths_failure_keeps_the_o
     native = ['dl', 'du', 'ud', 'ul']
     tr = DeviceModel(task, n_veh=M, modes=[native[i % 4] for i in range(M)])
     rng = np.random.default_rng(0)
-    from tests.test_gpu_parity import _random_scene
+    from tests._env_step_check import random_scene as _random_scene
     ego, cand, _, _, light, _, ref = _random_scene(task, B, M, 5)
     cmode = np.tile(np.array([_capi.VMODE_ID[native[i % 4]] for i in range(M)], np.uint8), (B, 1))
     obs0 = dev.get_obs(ego, cand, cmode, light, ref_idx=ref)

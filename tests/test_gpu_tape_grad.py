@@ -2,113 +2,14 @@
 csrc/eb_rollout_tape_vjp.hip) — against the G16 chain fixtures and the G18 edge chains (bound: tests/_grad_cases.py), bit for bit against the composed path
 (eb_rollout_step launches that keep every pre-step obs, then eb_rollout_chain_vjp) and against eb_rollout_tape's forward, its
 invariants, its refusals, and grad.rollout_tape against a loop of grad.rollout_step under torch.autograd."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from env_build_amd import _capi
-from env_build_amd.synthetic import make_rollout_inputs, assemble_obs
-from tests._helpers import DeviceModel
-from tests._grad_cases import TASKS, MAX_EXCLUDED, NEAR_R, cases, check_columns, check_zero_distance, edge_cases, zero_distance_case
+from tests._grad_cases import TASKS, MAX_EXCLUDED, cases, check_columns, check_zero_distance, edge_cases, zero_distance_case
+from tests._tape import NATIVE, TapeModel, all_same, edge_synthetic_case, same, synthetic_case
 
 pytestmark = pytest.mark.gpu
-NATIVE = {'left': 8, 'straight': 9, 'right': 5}
-
-
-class TapeModel(DeviceModel):
-    """DeviceModel + the tape entries of include/envbuild_grad.h; the t_* methods take and return torch tensors on the device"""
-
-    def __init__(self, task, **kw):
-        self.mode = kw.get('mode', 'training')
-        DeviceModel.__init__(self, task, **kw)
-
-    def to_dev(self, a, dtype=np.float32):
-        return self._in(a, dtype)
-
-    def t_tape_vjp(self, obs0, tape, ri, path_id, g_final=None, g5=None, w5=None, out5=True, obs_out=True, g_obs0=True, g_tape=True):
-        torch = self.torch
-        H, n, nd = tape.shape[0], obs0.shape[0], self.D - 4 * self.n_veh
-        mk = lambda want, shape: torch.full(shape, float('nan'), device=self.dev) if want else None
-        o5, oo, g0, gt = mk(out5, (H, 5, n)), mk(obs_out, (n, self.D)), mk(g_obs0, (n, nd)), mk(g_tape, (H, n, 2))
-        w = None if w5 is None else (C.c_float * 5)(*[float(v) for v in w5])
-        self.api.rollout_tape_vjp(self.h, n, H, self._ptr(obs0), self._ptr(tape), self._ptr(ri), int(path_id), self._ptr(g_final),
-                                  0 if g_final is None else g_final.shape[1], self._ptr(g5), w, self._ptr(o5), self._ptr(oo),
-                                  self._ptr(g0), self._ptr(gt), self.stream)
-        return o5, oo, g0, gt
-
-    def t_step_vjp(self, obs, actions, ri, path_id, g_obs_out, g_out5):
-        """eb_rollout_step_vjp, ld_in == nd -> g_obs_in [n, nd], g_actions [n, 2]"""
-        n, nd = obs.shape[0], self.D - 4 * self.n_veh
-        gi, ga = self.torch.full((n, nd), float('nan'), device=self.dev), self.torch.full((n, 2), float('nan'), device=self.dev)
-        self.api.rollout_step_vjp(self.h, n, self._ptr(obs), self._ptr(actions), self._ptr(ri), int(path_id), self._ptr(g_obs_out),
-                                  g_obs_out.shape[1], self._ptr(g_out5), self._ptr(gi), nd, self._ptr(ga), self.stream)
-        return gi, ga
-
-    def t_composed(self, obs0, tape, ri, path_id, g_final=None, g5=None):
-        """what a user had to do before: H eb_rollout_step launches that keep every pre-step obs, then eb_rollout_chain_vjp"""
-        torch = self.torch
-        H, n, nd = tape.shape[0], obs0.shape[0], self.D - 4 * self.n_veh
-        steps = torch.empty((H + 1, n, self.D), device=obs0.device)
-        steps[0] = obs0
-        o5, sc = torch.empty((H, 5, n), device=obs0.device), torch.empty((n, 2), device=obs0.device)
-        for t in range(H):
-            self.api.rollout_step(self.h, n, self._ptr(steps[t]), self._ptr(tape[t]), self._ptr(ri), int(path_id), self._ptr(steps[t + 1]),
-                                  self._ptr(o5[t]), self._ptr(sc), self.stream)
-        work, g0 = torch.empty((n, nd), device=obs0.device), torch.empty((n, nd), device=obs0.device)
-        gt = torch.empty((H, n, 2), device=obs0.device)
-        self.api.rollout_chain_vjp(self.h, n, H, self._ptr(steps), self._ptr(tape), self._ptr(ri), int(path_id), self._ptr(g_final),
-                                   0 if g_final is None else g_final.shape[1], self._ptr(g5), self._ptr(work), self._ptr(g0),
-                                   self._ptr(gt), self.stream)
-        return o5, steps[H], g0, gt
-
-    def t_forward_tape(self, obs0, tape, ri, path_id):
-        torch = self.torch
-        H, n = tape.shape[0], obs0.shape[0]
-        work, out, o5 = torch.empty_like(obs0), torch.empty_like(obs0), torch.empty((H, 5, n), device=obs0.device)
-        self.api.rollout_tape(self.h, n, H, self._ptr(obs0), self._ptr(tape), self._ptr(ri), int(path_id), self._ptr(work), self._ptr(out),
-                              self._ptr(o5), self.stream)
-        return o5, out
-
-    def max_horizon(self):
-        v = C.c_int32(0)
-        self.api.rollout_tape_vjp_max_horizon(self.h, C.byref(v))
-        return v.value
-
-
-def bits(t):
-    import torch
-    return t.contiguous().view(torch.int32)
-
-
-def same(a, b):
-    import torch
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
-
-
-def all_same(got, want, what):
-    for name, a, b in zip(('out5_steps', 'obs_out', 'g_obs0', 'g_action_tape'), got, want):
-        assert same(a, b), '%s: %s differs in %d of %d words' % (what, name, int((bits(a) != bits(b)).sum()), a.numel())
-
-
-def synthetic_case(m, task, B, H, seed):
-    """-> obs0 [B, D], tape [H, B, 2] (a few actions beyond the +-1.05 clip), ref_idx or None, path_id, cotangents — on the device"""
-    import torch
-    inp = make_rollout_inputs(task, B, m.n_veh, H, seed=seed, n_future=m.n_future)
-    training = m.mode == 'training'
-    ri = inp['ref_idx'].copy()
-    if training:
-        ri[::37] = 5                                   # out of range: no path (DAM:342, 352)
-    trk = m.tracking_error(inp['ego'][:, 3], inp['ego'][:, 4], inp['ego'][:, 5], inp['ego'][:, 0], m.n_future,
-                           ref_idx=np.clip(ri, 0, 2) if training else None, path_id=1)
-    obs0 = assemble_obs(inp['ego'], trk, inp['veh'])
-    tape = inp['actions'].astype(np.float32)
-    tape[:, ::11] *= 1.3
-    g = torch.Generator(device='cuda').manual_seed(seed)
-    nd = m.D - 4 * m.n_veh
-    g_final = torch.randn((B, nd), device='cuda', generator=g)
-    g5 = torch.randn((H, 5, B), device='cuda', generator=g)
-    return m.to_dev(obs0), m.to_dev(tape), (m.to_dev(ri, np.int32) if training else None), 1, g_final, g5
 
 
 def model_for(task, c):
@@ -143,35 +44,6 @@ def test_tape_vjp_meets_the_reference_gradients_and_forward(task):
 def test_tape_vjp_meets_the_edge_chains(task):
     """g18: the chains that start on the junction's exit side and next to the entry lane's walls, held as the g16 chains are"""
     tape_meets_the_reference(task, edge_cases(task)[1], 'g18')
-
-
-def edge_synthetic_case(m, task, B, H, seed):
-    """synthetic_case with every vehicle within 4.5 m of its ego (each record in the near queue: the queue of a tile is full), a
-    third of the egos up to 400 m away (off the closest-point cell grid), a third shifted sideways onto the lane's walls"""
-    import torch
-    inp = make_rollout_inputs(task, B, m.n_veh, H, seed=seed, n_future=m.n_future)
-    rng = np.random.default_rng(seed + 1)
-    ego, kind = inp['ego'], np.arange(B) % 3
-    far, wall = kind == 1, kind == 2
-    ego[far, 3:5] += rng.choice([-1.0, 1.0], (int(far.sum()), 2)) * rng.uniform(60.0, 380.0, (int(far.sum()), 2))
-    ego[wall, 3:5] += rng.choice([-1.0, 1.0], (int(wall.sum()), 2)) * rng.uniform(0.8, 1.8, (int(wall.sum()), 2))
-    rad, ang = 0.3 + 4.2 * np.sqrt(rng.random((B, m.n_veh))), rng.uniform(-np.pi, np.pi, (B, m.n_veh))
-    veh = inp['veh'].reshape(B, m.n_veh, 4)
-    veh[:, :, 0], veh[:, :, 1] = ego[:, 3:4] + rad * np.cos(ang), ego[:, 4:5] + rad * np.sin(ang)
-    assert (np.hypot(veh[:, :, 0] - ego[:, 3:4], veh[:, :, 1] - ego[:, 4:5]) < NEAR_R - 1.0).all() and np.abs(ego[:, 3:5]).max() > 300.0
-    training = m.mode == 'training'
-    ri = inp['ref_idx'].copy()
-    if training:
-        ri[::37] = 5
-    trk = m.tracking_error(ego[:, 3], ego[:, 4], ego[:, 5], ego[:, 0], m.n_future, ref_idx=np.clip(ri, 0, 2) if training else None, path_id=1)
-    obs0 = assemble_obs(ego, trk, veh.reshape(B, -1))
-    tape = inp['actions'].astype(np.float32)
-    tape[:, ::11] *= 1.3
-    g = torch.Generator(device='cuda').manual_seed(seed)
-    nd = m.D - 4 * m.n_veh
-    g_final = torch.randn((B, nd), device='cuda', generator=g)
-    g5 = torch.randn((H, 5, B), device='cuda', generator=g)
-    return m.to_dev(obs0), m.to_dev(tape), (m.to_dev(ri, np.int32) if training else None), 1, g_final, g5
 
 
 @pytest.mark.parametrize('task', TASKS)

@@ -8,7 +8,7 @@ import ctypes as C
 
 import pytest
 
-from tests.test_gpu_tape_grad import TapeModel, NATIVE
+from tests._tape import NATIVE, TapeModel
 
 pytestmark = pytest.mark.gpu
 ENTRIES = ('vjp', 'cand', 'cand_vjp', 'sample', 'ilqr')

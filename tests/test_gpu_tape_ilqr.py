@@ -9,107 +9,15 @@ Bounded, by |v - v64| <= 4 E + 2^-20 max|v64| per column (tests/_grad_cases.py),
 its float64 run: l_zz / l_uu against ilqr.lq_reference, gains_out / dv against ilqr.riccati_reference on the kernel's own model; the
 (row, step) pairs at which the two precisions or the kernel take different active sets are excluded together with every earlier step
 of the row, at most 1 % of the pairs of each test, counted inside that test.  The kernel's set is read off its k: a component equal to the bound -1 - u or 1 - u is clamped."""
-import ctypes as C
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 
-from tests._helpers import ROOT
 from tests._grad_cases import TASKS, MAX_EXCLUDED
-from tests.test_gpu_tape_grad import bits, same, synthetic_case, edge_synthetic_case
-from tests.test_gpu_tape_cand import CandModel, NATIVE, WEIGHTS
-from tests.test_gpu_mpc import setup as mpc_setup
+from tests._tape import (ILQR_OUT as OUT, NATIVE, WEIGHTS, IlqrModel, bits, bound_check, diverged, edge_synthetic_case, load_example, mpc_setup,
+                         same, same_numbers, synthetic_case)
 
 pytestmark = pytest.mark.gpu
-OUT = ('cost', 'best_index', 'best_cost', 'u', 'x', 'gains', 'dv', 'cand', 'lq')
 ALPHAS = (1.0, 0.5, 0.25, 0.125, 0.0625, 0.03125, 0.015625)
-
-
-class IlqrModel(CandModel):
-    """CandModel + the entries of include/envbuild_ilqr.h; t_ilqr takes and returns torch tensors on the device"""
-
-    def ilqr_max(self, horizon=25):
-        a, h = C.c_int32(0), C.c_int32(0)
-        self.api.rollout_tape_ilqr_max(self.h, int(horizon), C.byref(a), C.byref(h))
-        return a.value, h.value
-
-    def t_ilqr(self, obs0, u_nom, ri=None, path_id=1, x_nom=None, gains=None, alphas=(), mu=None, w5=WEIGHTS[0], want=OUT, n_alpha=None,
-               out=None):
-        torch = self.torch
-        H, n = u_nom.shape[0], obs0.shape[0]
-        K1 = 1 + (len(alphas) if n_alpha is None else n_alpha)
-        shapes = dict(cost=(K1, n), best_index=(n,), best_cost=(n,), u=(H, n, 2), x=(H, 6, n), gains=(H, 14, n), dv=(2, n),
-                      cand=(K1, H, n, 2), lq=(H, 157, n))
-        out = {} if out is None else out
-        for k in want:
-            if k not in out:
-                out[k] = (torch.full(shapes[k], -7, dtype=torch.int32, device=self.dev) if k == 'best_index'
-                          else torch.full(shapes[k], float('nan'), device=self.dev))
-        al = None if alphas is None else (C.c_float * max(1, len(alphas)))(*[float(v) for v in alphas])
-        w = None if w5 is None else (C.c_float * 5)(*[float(v) for v in w5])
-        self.api.rollout_tape_ilqr(self.h, n, H, K1 - 1, self._ptr(obs0), self._ptr(u_nom), self._ptr(x_nom), self._ptr(gains), self._ptr(ri),
-                                   int(path_id), al, self._ptr(mu), w, *[self._ptr(out.get(k)) for k in OUT], self.stream)
-        return out
-
-    def cand_cost(self, obs0, tapes, ri, pid, w5):
-        """eb_rollout_tape_cand's cost [K, n] of the tapes [K, H, n, 2], in chunks of its limit"""
-        limit = self.cand_max(tapes.shape[1])
-        return self.torch.cat([self.t_cand(obs0, tapes[k:k + limit].contiguous(), ri, 0, None, pid, False, w5, out5=False)[1]
-                               for k in range(0, tapes.shape[0], limit)])
-
-    def chain_states(self, obs0, tapes, ri, pid):
-        """the pre-step obs [K, H, n, D] of every step of the tapes [K, H, n, 2]: H eb_rollout_step launches over K * n rows"""
-        torch = self.torch
-        K, H, n = tapes.shape[0], tapes.shape[1], obs0.shape[0]
-        rows = obs0.repeat(K, 1).contiguous()
-        rr = None if ri is None else ri.repeat(K).contiguous()
-        steps = torch.empty((H + 1, K * n, self.D), device=obs0.device)
-        steps[0] = rows
-        o5, sc = torch.empty((5, K * n), device=obs0.device), torch.empty((K * n, 2), device=obs0.device)
-        for t in range(H):
-            a = tapes[:, t].reshape(K * n, 2).contiguous()
-            self.api.rollout_step(self.h, K * n, self._ptr(steps[t]), self._ptr(a), self._ptr(rr), int(pid), self._ptr(steps[t + 1]),
-                                  self._ptr(o5), self._ptr(sc), self.stream)
-        return steps[:H].view(H, K, n, self.D).permute(1, 0, 2, 3).contiguous()
-
-    def unit_vjps(self, pre, tape, ri, pid, w5):
-        """eb_rollout_step_vjp over the rows pre [H, n, D] with the ten cotangents of the header in ONE launch -> [H, n, 10, 11]: row
-        r < 9: (g_obs_in[0..8], g_actions) for g_obs_out = e_r, g_out5 = 0; row 9: for g_obs_out = 0, g_out5 = w5"""
-        torch = self.torch
-        H, n, D = pre.shape
-        nd = D - 4 * self.n_veh
-        N = H * n * 10
-        obs = pre.reshape(H * n, 1, D).expand(H * n, 10, D).reshape(N, D).contiguous()
-        act = tape.reshape(H * n, 1, 2).expand(H * n, 10, 2).reshape(N, 2).contiguous()
-        rr = None if ri is None else ri.view(1, n, 1).expand(H, n, 10).reshape(N).contiguous()
-        g_obs = torch.zeros((H * n, 10, nd), device=pre.device)
-        for r in range(9):
-            g_obs[:, r, r] = 1.0
-        g5 = torch.zeros((5, H * n, 10), device=pre.device)
-        g5[:, :, 9] = torch.tensor([float(v) for v in w5], device=pre.device).view(5, 1)
-        gi, ga = self.t_step_vjp(obs, act, rr, pid, g_obs.reshape(N, nd).contiguous(), g5.reshape(5, N).contiguous())
-        return torch.cat([gi[:, :9], ga], 1).view(H, n, 10, 11)
-
-
-def same_numbers(a, b):
-    import torch
-    return a.shape == b.shape and bool(((a == b) | (torch.isnan(a) & torch.isnan(b))).all())
-
-
-def bound_check(got, ref32, ref64, keep, what):
-    got, ref32, ref64 = (np.asarray(v, np.float64).reshape(-1, np.shape(v)[-1])[keep.reshape(-1)] for v in (got, ref32, ref64))
-    if not len(got):
-        return
-    E = np.abs(ref32 - ref64).max(0)
-    tol = 4.0 * E + 2.0 ** -20 * np.abs(ref64).max(0)
-    err = np.abs(got - ref64).max(0)
-    print('%-60s worst err / tolerance %.3f, worst err / E %.2f' % (
-        what, float((err / np.maximum(tol, 1e-300)).max()), float(np.where(E > 0, err / np.maximum(E, 1e-300), 0.0).max())))
-    assert np.isfinite(got).all(), '%s: not finite' % what
-    assert (err <= tol).all(), '%s: columns %s exceed 4 E + 2^-20 max|v64|: err %s, tol %s' % (
-        what, np.nonzero(err > tol)[0], err[err > tol], tol[err > tol])
 
 
 def sets_from_k(k, u):
@@ -120,11 +28,6 @@ def sets_from_k(k, u):
     state = np.where(k == f(-1) - u, 'L', np.where(k == f(1) - u, 'U', 'F'))
     names = np.char.add(state[:, 0], state[:, 1])
     return np.vectorize(ACTIVE_SETS.index)(names)
-
-
-def diverged(a, b):
-    d = a != b
-    return np.flip(np.logical_or.accumulate(np.flip(d, 0), 0), 0)
 
 
 def new_count():
@@ -436,9 +339,7 @@ def test_polished_ilqr_never_ends_above_the_default_solver(task):
 
 def test_ilqr_example_runs_a_few_control_steps():
     import torch
-    spec = importlib.util.spec_from_file_location('mpc_ilqr', os.path.join(ROOT, 'examples', 'mpc_ilqr.py'))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = load_example('mpc_ilqr')
     r = mod.run(n_env=128, control_steps=3, iterations=4)
     assert torch.isfinite(r['J_first']).all() and torch.isfinite(r['reward_sum']).all() and torch.isfinite(r['J_last']).all()
     slack = 1e-5 * r['J0_first'].abs() + 1e-5              # J0 is the kernel's sum, J the independent evaluation's

@@ -12,54 +12,16 @@ NaN tape is finite.  test_a_nan_env_leaves_the_others_alone therefore runs both:
 its costs stay finite, the other envs' bits are unchanged) and a NaN ROW of obs0 (every cost of that env is NaN: index 0, the other
 envs' bits unchanged)."""
 import ctypes as C
-import glob
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 
 from env_build_amd import _capi
-from tests._helpers import GOLDEN, ROOT, golden
+from tests._helpers import golden
 from tests._grad_cases import TASKS
-from tests.test_gpu_tape_grad import bits, same, synthetic_case, edge_synthetic_case
-from tests.test_gpu_tape_cand import CandModel, NATIVE, WEIGHTS
-from tests.test_gpu_mpc import setup as mpc_setup
+from tests._tape import G5, NATIVE, WEIGHTS, SampleModel, bits, edge_synthetic_case, load_example, mpc_setup, same, synthetic_case
 
 pytestmark = pytest.mark.gpu
-
-
-class SampleModel(CandModel):
-    """CandModel + the entries of include/envbuild_sample.h; t_sample takes and returns torch tensors on the device"""
-
-    def sample_max(self, horizon=25):
-        v = C.c_int32(0)
-        self.api.rollout_tape_sample_max(self.h, int(horizon), C.byref(v))
-        return v.value
-
-    def t_sample(self, obs0, nominal, S, ri=None, path_id=1, env_ids=None, seed=0, counter=0, sigma=(0.3, 0.3), beta=0.0, inv_lambda=1.0,
-                 w5=WEIGHTS[0], want=('cost', 'best_tape', 'best_cost', 'best_index', 'mean_tape', 'samples')):
-        torch = self.torch
-        H, n = nominal.shape[0], obs0.shape[0]
-        shapes = dict(cost=(S, n), best_tape=(H, n, 2), best_cost=(n,), best_index=(n,), mean_tape=(H, n, 2), samples=(S, H, n, 2))
-        out = {}
-        for k in want:
-            out[k] = (torch.full(shapes[k], -7, dtype=torch.int32, device=self.dev) if k == 'best_index'
-                      else torch.full(shapes[k], float('nan'), device=self.dev))
-        sig = None if sigma is None else (C.c_float * 2)(float(sigma[0]), float(sigma[1]))
-        w = None if w5 is None else (C.c_float * 5)(*[float(v) for v in w5])
-        self.api.rollout_tape_sample(self.h, n, int(S), H, self._ptr(obs0), self._ptr(nominal), self._ptr(ri), int(path_id),
-                                     self._ptr(env_ids), int(seed), int(counter), sig, float(beta), float(inv_lambda), w,
-                                     self._ptr(out.get('cost')), self._ptr(out.get('best_tape')), self._ptr(out.get('best_cost')),
-                                     self._ptr(out.get('best_index')), self._ptr(out.get('mean_tape')), self._ptr(out.get('samples')),
-                                     self.stream)
-        return out
-
-    def cand_cost(self, obs0, tapes, ri, pid, w5):
-        """eb_rollout_tape_cand's cost [K, n] of the tapes [K, H, n, 2], in chunks of its limit"""
-        limit = self.cand_max(tapes.shape[1])
-        return self.torch.cat([self.t_cand(obs0, tapes[k:k + limit].contiguous(), ri, 0, None, pid, False, w5, out5=False)[1]
-                               for k in range(0, tapes.shape[0], limit)])
 
 
 def mean_bound(S):
@@ -145,9 +107,6 @@ def test_crowded_remote_and_near_wall_scenes(task):
             obs0, tape, ri = obs0[:B].contiguous(), tape[:, :B].contiguous(), None if ri is None else ri[:B].contiguous()
             out = check_launch(m, obs0, tape, ri, pid, S, 'edge %s N%d S%d' % (task, n_veh, S), beta=0.7, w5=WEIGHTS[3])
             assert bool((out['cost'] > 0).all())
-
-
-G5 = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(GOLDEN, 'g5_rollout_*.npz')))
 
 
 @pytest.mark.parametrize('name', G5)
@@ -381,9 +340,7 @@ def test_hybrid_never_ends_above_the_default_solver(task):
 
 def test_sampling_example_runs_a_few_control_steps():
     import torch
-    spec = importlib.util.spec_from_file_location('mpc_sampling', os.path.join(ROOT, 'examples', 'mpc_sampling.py'))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = load_example('mpc_sampling')
     r = mod.run(n_env=128, control_steps=3, iterations=4, n_samples=128)
     assert torch.isfinite(r['J_first']).all() and torch.isfinite(r['reward_sum']).all() and torch.isfinite(r['J_last']).all()
     slack = 1e-5 * r['J0_first'].abs() + 1e-5              # J0 is the kernel's sum, J the independent evaluation's

@@ -1,59 +1,17 @@
-"""CPU (-m "not gpu"): the gradient ABI (include/envbuild_grad.h) is bound and exported, a library without it is refused cleanly,
-the gradient fixtures are self-consistent and G18 reaches every branch it was built for, the reverse pass's arithmetic
-(csrc/eb_grad_device.h, run on the host) meets them, and — where the reference tree is present — the generator reproduces them."""
-import ctypes as C
+"""CPU (-m "not gpu"): the gradient fixtures are self-consistent and G18 reaches every branch it was built for, the reverse pass's
+arithmetic (csrc/eb_grad_device.h, run on the host) meets them, and — where the reference tree is present — the generator reproduces
+them.  The ABI of include/envbuild_grad.h: tests/test_family_abi.py."""
 import os
-import re
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from env_build_amd import _capi, build as eb_build
-from tests._helpers import ROOT, golden, oracle_lib, _p
+from env_build_amd import _capi
+from tests._helpers import ROOT, build_host_harness, golden, _p
 from tests._grad_cases import (TASKS, MAX_EXCLUDED, WALLS, cases, check_columns, check_zero_distance, edge_cases, edge_census,
                                 step_and_edge_cases, zero_distance_case)
-
-HEADER = os.path.join(ROOT, 'include', 'envbuild_grad.h')
-
-
-def header_symbols():
-    src = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(eb_[a-z0-9_]+)\s*\(', src)))
-
-
-def test_grad_header_declares_what_ctypes_binds():
-    assert sorted(_capi.GRAD_PROTOTYPES) == header_symbols()
-    assert not set(_capi.GRAD_PROTOTYPES) & set(_capi.PROTOTYPES)          # a table of its own: envbuild.h's set is the oracle's too
-    assert _capi.EB_ABI_VERSION == 5
-    src = open(HEADER).read()
-    assert int(re.search(r'#define EB_GRAD_ABI_VERSION (\d+)', src).group(1)) == _capi.EB_GRAD_ABI_VERSION
-
-
-def test_hip_library_exports_the_gradient_entries_and_a_gfx950_vjp_kernel():
-    lib_path = eb_build.build()            # hipcc --offload-arch=gfx950 (cross-compiles without a GPU)
-    import torch  # noqa: F401  (binds the HIP runtime torch ships before ours, as the product does)
-    lib = C.CDLL(lib_path)
-    for name in _capi.GRAD_PROTOTYPES:
-        assert hasattr(lib, name), name
-    assert lib.eb_grad_abi_version() == _capi.EB_GRAD_ABI_VERSION
-    blob = open(lib_path, 'rb').read()
-    assert b'gfx950' in blob and b'rollout_step_vjp_kernel' in blob
-    assert 'eb_rollout_vjp.hip' in eb_build.SOURCES
-    # the forward kernels' hash (profiles/ ties HBM-traffic records to it) does not see the reverse pass
-    assert 'eb_rollout_vjp.hip' not in eb_build.KERNEL_SOURCES['rollout']
-
-
-def test_a_library_without_the_reverse_pass_is_refused_cleanly():
-    api = oracle_lib()                     # CApi binds every PROTOTYPES entry on it, as before
-    assert api.backend == 'oracle'
-    for name in ('rollout_step_vjp', 'rollout_chain_vjp', 'grad_abi_version'):
-        with pytest.raises(_capi.EbError) as e:
-            getattr(api, name)
-        assert 'reverse pass' in str(e.value)
-    with pytest.raises(_capi.EbError):
-        api.grad_fn('eb_rollout_step_vjp')
 
 
 def test_differentiable_model_refuses_fp16_state():
@@ -153,11 +111,7 @@ def test_fixture_forward_equals_the_rollout_fixtures(task):
 @pytest.fixture(scope='module')
 def host_harness(tmp_path_factory):
     """tests/_grad_host_harness.hip: the kernel's __host__ __device__ arithmetic compiled for the host"""
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    out = str(tmp_path_factory.mktemp('grad_host') / 'libgrad_host.so')
-    subprocess.check_call([hipcc, '--offload-arch=gfx950', '-O2', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared',
-                           '-I', eb_build.CSRC, os.path.join(ROOT, 'tests', '_grad_host_harness.hip'), '-o', out])
-    return C.CDLL(out)
+    return build_host_harness(tmp_path_factory, '_grad_host_harness.hip', 'grad_host')
 
 
 def host_step_vjp(h, task, c, obs):

@@ -2,41 +2,12 @@
 eb_shield_is_safe) against a plain torch fp32 restatement of utils/model.py:18-43 + utils/policy.py:85-92, and
 its deterministic exp / tanh against NumPy.  Tolerance 1e-5 (relative to the layer scale): the reference's
 TensorFlow matmul leaves the summation order open, the contract of include/envbuild.h fixes one."""
-import glob
-import os
-import sys
-
 import numpy as np
 import pytest
-import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from env_build_amd.policy import orthogonal  # noqa: E402
-from env_build_amd.synthetic import assemble_obs, make_rollout_inputs  # noqa: E402
-from tests._helpers import GOLDEN, HostModel, close, golden, oracle_lib  # noqa: E402
-
-ACTS = {'linear': lambda x: x, 'relu': torch.relu, 'elu': torch.nn.functional.elu, 'tanh': torch.tanh}
-
-
-def make_layers(rng, obs_dim, n_hidden, n_units, out_dim, bias_scale=0.1):
-    dims = [obs_dim] + [n_units] * n_hidden + [out_dim]
-    layers = []
-    for L in range(n_hidden + 1):
-        gain = np.sqrt(2.) if L < n_hidden else 1.
-        layers.append((orthogonal(rng, dims[L], dims[L + 1], gain),
-                       (bias_scale * rng.standard_normal(dims[L + 1])).astype(np.float32)))
-    return layers
-
-
-def torch_mlp(layers, obs, hidden_act, out_act, scale=None):
-    x = torch.from_numpy(obs)
-    if scale is not None:
-        x = x * torch.from_numpy(scale)
-    for L, (k, b) in enumerate(layers):
-        x = x @ torch.from_numpy(k) + torch.from_numpy(b)
-        x = ACTS[out_act if L == len(layers) - 1 else hidden_act](x)
-    return x.numpy()
+from env_build_amd.synthetic import assemble_obs, make_rollout_inputs
+from tests._helpers import HostModel, close, golden, oracle_lib
+from tests._policy_cases import G13, G14, g13_layers, g14_check, make_layers, torch_mlp
 
 
 @pytest.mark.parametrize('obs_dim,n_hidden,n_units,out_dim,hact,oact', [
@@ -133,15 +104,6 @@ def test_mlp_argument_errors():
 
 
 # ---- G13: the reference's own MLPNet / Policy4Toyota / Preprocessor / LoadPolicy.run_batch over the tf.keras stand-in ----
-G13 = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(GOLDEN, 'g13_policy_*.npz')))
-
-
-def g13_layers(g, model):
-    n = 2 * (int(g['hidden']) + 1)
-    ws = [g['%s_w%d' % (model, i)] for i in range(n)]
-    return [(ws[2 * i], ws[2 * i + 1]) for i in range(n // 2)]        # Keras order: kernel, bias per layer
-
-
 @pytest.mark.parametrize('name', G13)
 def test_g13_policy_network_against_the_reference_classes(name):
     """actions = action_range * tanh(first act_dim logits of MLPNet(obs * obs_scale)), values = relu head of obj_v:
@@ -158,24 +120,6 @@ def test_g13_policy_network_against_the_reference_classes(name):
 
 
 # ---- G14: HierarchicalDecision.is_safe / safe_shield (hier_decision.py:89-107) from the reference's own method bodies ----
-G14 = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(GOLDEN, 'g14_shield_*.npz')))
-
-
-def g14_check(model, g, mlp):
-    """eb_shield_is_safe over the fixture's start states: the safe flags must equal the reference's, and the action
-    the shield lets through (the policy's, or (0, -1) when it starts) must match"""
-    obs, path = g['obs'], int(g['path_index'])
-    safe, punish, _, _ = model.shield_is_safe(mlp, obs, ref_idx=None, path_id=path, steps=5, penalty=0)
-    assert np.array_equal(safe, g['safe']), 'safe flags differ from the reference at %s' % np.flatnonzero(safe != g['safe'])
-    assert np.array_equal(punish > 0, g['safe'] == 0)
-    act = model.policy_run_batch(mlp, 2, obs, 1.0)
-    want = g['safe_action']
-    assert np.array_equal(g['shield_started'], 1 - g['safe'])
-    ok = g['safe'] == 1
-    close(act[ok], want[ok], 1e-5, 5e-6, 'G14 actions let through')
-    assert (want[~ok] == np.array([0., -1.], np.float32)).all()          # hier_decision.py:100, 105
-
-
 @pytest.mark.parametrize('name', G14)
 def test_g14_shield_against_the_reference_methods(name):
     g = golden(name)

@@ -1,64 +1,8 @@
-"""CPU (-m "not gpu"): the candidate-tape ABI (include/envbuild_cand.h) is declared as ctypes binds it, exported by the built library
-next to a gfx950 kernel, and refused cleanly by a library without it; the solver's fused line search (env_build_amd/mpc.py:
+"""CPU (-m "not gpu"): the candidate-tape family on the host (the ABI of include/envbuild_cand.h: tests/test_family_abi.py): the solver's
+fused line search (env_build_amd/mpc.py:
 projected_gradient with evaluate_many) reproduces the sequential one bit for bit on a non-convex toy cost; the K-start selection
 rule (mpc.best_start) picks the first minimum and never a NaN."""
-import ctypes as C
-import os
-import re
-
 import pytest
-
-from env_build_amd import _capi, build as eb_build
-from tests._helpers import ROOT, oracle_lib
-
-HEADER = os.path.join(ROOT, 'include', 'envbuild_cand.h')
-
-
-def header_source():
-    return re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-
-
-def test_cand_header_declares_what_ctypes_binds():
-    src = header_source()
-    assert sorted(_capi.CAND_PROTOTYPES) == sorted(set(re.findall(r'\b(eb_[a-z0-9_]+)\s*\(', src)))
-    for name, (_res, args) in _capi.CAND_PROTOTYPES.items():
-        m = re.search(r'\bint\s+%s\s*\(([^)]*)\)\s*;' % name, src)
-        assert m, '%s is not declared in include/envbuild_cand.h' % name
-        declared = [a for a in m.group(1).split(',') if a.strip() != 'void']
-        assert len(declared) == len(args), name
-    # a table of its own: envbuild.h's set is the oracle's too, envbuild_grad.h's is pinned by its own tests
-    assert not set(_capi.CAND_PROTOTYPES) & set(_capi.PROTOTYPES)
-    assert not set(_capi.CAND_PROTOTYPES) & set(_capi.GRAD_PROTOTYPES)
-    assert _capi.EB_ABI_VERSION == 5 and _capi.EB_GRAD_ABI_VERSION == 2 and _capi.EB_CAND_ABI_VERSION == 1
-    assert int(re.search(r'#define EB_CAND_ABI_VERSION (\d+)', src).group(1)) == 1
-    grad = open(os.path.join(ROOT, 'include', 'envbuild_grad.h')).read()
-    assert int(re.search(r'#define EB_GRAD_ABI_VERSION (\d+)', grad).group(1)) == 2
-
-
-def test_hip_library_exports_the_candidate_entries_and_a_gfx950_kernel():
-    lib_path = eb_build.build()            # hipcc --offload-arch=gfx950 (cross-compiles without a GPU)
-    import torch  # noqa: F401  (binds the HIP runtime torch ships before ours, as the product does)
-    lib = C.CDLL(lib_path)
-    for name in _capi.CAND_PROTOTYPES:
-        assert hasattr(lib, name), name
-    assert lib.eb_cand_abi_version() == 1
-    blob = open(lib_path, 'rb').read()
-    assert b'gfx950' in blob and b'rollout_tape_cand_kernel' in blob
-    assert 'eb_rollout_tape_cand.hip' in eb_build.SOURCES and 'eb_cand.h' in eb_build.HEADERS
-    # a translation unit of its own: the forward kernels' hashes (profiles/ ties HBM-traffic records to them) do not see it
-    for files in eb_build.KERNEL_SOURCES.values():
-        assert 'eb_rollout_tape_cand.hip' not in files and 'eb_cand.h' not in files
-
-
-def test_a_library_without_the_candidate_entries_is_refused_cleanly():
-    api = oracle_lib()                     # CApi binds every PROTOTYPES entry on it, as before
-    assert api.backend == 'oracle'
-    for name in ('rollout_tape_cand', 'rollout_tape_cand_max', 'cand_abi_version'):
-        with pytest.raises(_capi.EbError) as e:
-            getattr(api, name)
-        assert 'candidate-tape' in str(e.value)
-    with pytest.raises(_capi.EbError):
-        api.cand_fn('eb_rollout_tape_cand')
 
 
 # ---- the solver's fused line search, on the CPU ----

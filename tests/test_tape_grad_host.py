@@ -1,6 +1,7 @@
-"""CPU (-m "not gpu"): the one-launch value and gradient of an open-loop rollout (eb_rollout_tape_vjp) is declared, bound and
-exported; a library without it is refused cleanly; its per-env reverse sweep (csrc/eb_tape_grad_device.h, the text the kernel runs,
-compiled for the host) meets every G16 chain fixture and every G18 edge chain under the bound of tests/_grad_cases.py; the solver's update rule
+"""CPU (-m "not gpu"): the one-launch value and gradient of an open-loop rollout (eb_rollout_tape_vjp: the entries envbuild_grad.h gained
+with its version 2; the header as a family: tests/test_family_abi.py) is declared, bound and exported; a library without it is refused
+cleanly; its per-env reverse sweep (csrc/eb_tape_grad_device.h, the text the kernel runs, compiled for the host) meets every G16 chain
+fixture and every G18 edge chain under the bound of tests/_grad_cases.py; the solver's update rule
 (env_build_amd/mpc.py, device-agnostic torch) does what it promises on a problem with a known answer; the MPC fixtures
 (scripts/gen_golden_mpc.py) are self-consistent."""
 import ctypes as C
@@ -13,7 +14,7 @@ import numpy as np
 import pytest
 
 from env_build_amd import _capi, build as eb_build
-from tests._helpers import ROOT, HostModel, golden, oracle_lib, _p
+from tests._helpers import ROOT, HostModel, build_host_harness, golden, oracle_lib, _p
 from tests._grad_cases import TASKS, MAX_EXCLUDED, cases, chain_and_edge_cases, check_columns
 
 HEADER = os.path.join(ROOT, 'include', 'envbuild_grad.h')
@@ -62,11 +63,7 @@ def test_a_library_without_the_tape_entries_is_refused_cleanly():
 @pytest.fixture(scope='module')
 def host_harness(tmp_path_factory):
     """tests/_tape_grad_host_harness.hip: the kernel's __host__ __device__ reverse sweep compiled for the host"""
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    out = str(tmp_path_factory.mktemp('tape_grad_host') / 'libtape_grad_host.so')
-    subprocess.check_call([hipcc, '--offload-arch=gfx950', '-O2', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared',
-                           '-I', eb_build.CSRC, os.path.join(ROOT, 'tests', '_tape_grad_host_harness.hip'), '-o', out])
-    return C.CDLL(out)
+    return build_host_harness(tmp_path_factory, '_tape_grad_host_harness.hip', 'tape_grad_host')
 
 
 def oracle_forward(task, c):

@@ -1,5 +1,4 @@
-"""CPU (-m "not gpu"): the iLQR ABI (include/envbuild_ilqr.h) is declared as ctypes binds it, exported by the built library next to a
-gfx950 kernel, kept out of the hashed forward sources, and refused cleanly by a library without it; the per-env text of the kernel
+"""CPU (-m "not gpu"): the iLQR family on the host (the ABI of include/envbuild_ilqr.h: tests/test_family_abi.py): the per-env text of the kernel
 (csrc/eb_ilqr_device.h, compiled for the host) is driven over the CPU oracle's forward on the G17 start rows and on G18's edge chains:
   A, B, l_z, l_u   equal grad::env_vjp with unit cotangents numerically (+0 and -0 alike);
   l_zz, l_uu       within |v - v64| <= 4 E + 2^-20 max|v64| of ilqr.lq_reference in float64, E the restatement's own float32 run's
@@ -10,89 +9,24 @@ gfx950 kernel, kept out of the hashed forward sources, and refused cleanly by a 
 The restatement of the feedback law is the header's bit for bit; the box QP meets a brute-force search; ILQRMPC's update rule
 (mpc.ilqr_loop) reaches the known optimum of a toy LQ problem in one iteration at alpha = 1."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from env_build_amd import _capi, build as eb_build
-from tests._helpers import ROOT, HostModel, golden, oracle_lib, _p
+from env_build_amd import _capi
+from tests._helpers import HostModel, build_host_harness, golden, oracle_lib, _p
 from tests._grad_cases import TASKS, MAX_EXCLUDED, edge_cases
+from tests._tape import NATIVE, bound_check, diverged, same_numbers
 
-HEADER = os.path.join(ROOT, 'include', 'envbuild_ilqr.h')
-NATIVE = {'left': 8, 'straight': 9, 'right': 5}
 W5 = np.array([-1.0, 10.0, 0.0, 0.0, 0.0], np.float32)
 W5_ALL = np.array([-0.5, 3.0, 2.0, 0.25, 1.5], np.float32)          # every row of out5 carries weight
-
-
-def header_source():
-    return re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-
-
-def test_ilqr_header_declares_what_ctypes_binds():
-    src = header_source()
-    assert sorted(_capi.ILQR_PROTOTYPES) == sorted(set(re.findall(r'\b(eb_[a-z0-9_]+)\s*\(', src)))
-    for name, (_res, args) in _capi.ILQR_PROTOTYPES.items():
-        m = re.search(r'\bint\s+%s\s*\(([^)]*)\)\s*;' % name, src)
-        assert m, '%s is not declared in include/envbuild_ilqr.h' % name
-        declared = [a for a in m.group(1).split(',') if a.strip() != 'void']
-        assert len(declared) == len(args), name
-    assert len(_capi.ILQR_PROTOTYPES['eb_rollout_tape_ilqr'][1]) == 23
-    for other in (_capi.PROTOTYPES, _capi.GRAD_PROTOTYPES, _capi.CAND_PROTOTYPES, _capi.CAND_GRAD_PROTOTYPES, _capi.SAMPLE_PROTOTYPES):
-        assert not set(_capi.ILQR_PROTOTYPES) & set(other)
-    assert _capi.EB_ILQR_ABI_VERSION == 1 and int(re.search(r'#define EB_ILQR_ABI_VERSION (\d+)', src).group(1)) == 1
-
-
-def test_the_five_older_abi_numbers_are_unchanged():
-    assert (_capi.EB_ABI_VERSION, _capi.EB_GRAD_ABI_VERSION, _capi.EB_CAND_ABI_VERSION, _capi.EB_CAND_GRAD_ABI_VERSION,
-            _capi.EB_SAMPLE_ABI_VERSION) == (5, 2, 1, 1, 1)
-    for header, macro, want in (('envbuild.h', 'EB_ABI_VERSION', 5), ('envbuild_grad.h', 'EB_GRAD_ABI_VERSION', 2),
-                                ('envbuild_cand.h', 'EB_CAND_ABI_VERSION', 1), ('envbuild_cand_grad.h', 'EB_CAND_GRAD_ABI_VERSION', 1),
-                                ('envbuild_sample.h', 'EB_SAMPLE_ABI_VERSION', 1)):
-        text = open(os.path.join(ROOT, 'include', header)).read()
-        assert int(re.search(r'#define %s (\d+)' % macro, text).group(1)) == want, header
-
-
-def test_hip_library_exports_the_ilqr_entries_and_a_gfx950_kernel():
-    lib_path = eb_build.build()            # hipcc --offload-arch=gfx950 (cross-compiles without a GPU)
-    import torch  # noqa: F401  (binds the HIP runtime torch ships before ours, as the product does)
-    lib = C.CDLL(lib_path)
-    for name in _capi.ILQR_PROTOTYPES:
-        assert hasattr(lib, name), name
-    assert lib.eb_ilqr_abi_version() == 1
-    blob = open(lib_path, 'rb').read()
-    assert b'gfx950' in blob and b'rollout_tape_ilqr_kernel' in blob
-    assert 'eb_rollout_tape_ilqr.hip' in eb_build.SOURCES
-    for f in ('eb_ilqr.h', 'eb_ilqr_device.h'):
-        assert f in eb_build.HEADERS
-    # a translation unit of its own: the forward kernels' hashes (profiles/ ties HBM-traffic records to them) do not see it
-    for files in eb_build.KERNEL_SOURCES.values():
-        for f in ('eb_rollout_tape_ilqr.hip', 'eb_ilqr.h', 'eb_ilqr_device.h'):
-            assert f not in files
-
-
-def test_a_library_without_the_ilqr_entries_is_refused_cleanly():
-    api = oracle_lib()                     # CApi binds every PROTOTYPES entry on it, as before
-    assert api.backend == 'oracle'
-    for name in ('rollout_tape_ilqr', 'rollout_tape_ilqr_max', 'ilqr_abi_version'):
-        with pytest.raises(_capi.EbError) as e:
-            getattr(api, name)
-        assert 'iLQR' in str(e.value)
-    with pytest.raises(_capi.EbError):
-        api.ilqr_fn('eb_rollout_tape_ilqr')
 
 
 # ---- the kernel's per-env text on the host ----
 @pytest.fixture(scope='module')
 def harness(tmp_path_factory):
     """tests/_ilqr_host_harness.hip: csrc/eb_ilqr_device.h compiled for the host, with the flags of the tape-gradient harness"""
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    out = str(tmp_path_factory.mktemp('ilqr_host') / 'libilqr_host.so')
-    subprocess.check_call([hipcc, '--offload-arch=gfx950', '-O2', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared',
-                           '-I', eb_build.CSRC, os.path.join(ROOT, 'tests', '_ilqr_host_harness.hip'), '-o', out])
-    return C.CDLL(out)
+    return build_host_harness(tmp_path_factory, '_ilqr_host_harness.hip', 'ilqr_host')
 
 
 class Scene(object):
@@ -139,30 +73,6 @@ def host_ilqr(h, s, w5, mu=None):
     h.host_ilqr(_capi.TASK_ID[s.task], n, H, D, s.nd, s.n_veh, _p(s.pre), _p(s.tape), _p(s.has_path), _p(w5), _p(mu), _p(lq), _p(gains),
                 _p(dv), _p(sets))
     return lq, gains, dv, sets
-
-
-def bound_check(got, ref32, ref64, keep, what):
-    """got / ref32 / ref64: [..., C], keep: [...] bool — |got - ref64| <= 4 E + 2^-20 max|ref64| per column over the kept entries"""
-    got, ref32, ref64 = (np.asarray(v, np.float64).reshape(-1, np.shape(v)[-1])[keep.reshape(-1)] for v in (got, ref32, ref64))
-    E = np.abs(ref32 - ref64).max(0)
-    tol = 4.0 * E + 2.0 ** -20 * np.abs(ref64).max(0)
-    err = np.abs(got - ref64).max(0)
-    print('%-50s worst err / tolerance %.3f (column %d), worst err / E %.2f' % (
-        what, float((err / np.maximum(tol, 1e-300)).max()), int((err / np.maximum(tol, 1e-300)).argmax()),
-        float(np.where(E > 0, err / np.maximum(E, 1e-300), 0.0).max())))
-    assert np.isfinite(got).all(), '%s: not finite' % what
-    assert (err <= tol).all(), '%s: columns %s exceed 4 E + 2^-20 max|v64|: err %s, tol %s' % (
-        what, np.nonzero(err > tol)[0], err[err > tol], tol[err > tol])
-
-
-def same_numbers(a, b):
-    return bool(((a == b) | (np.isnan(a) & np.isnan(b))).all())
-
-
-def diverged(sets_a, sets_b):
-    """[H, B] bool: step t of row b, or a LATER step of it, has different active sets in a and b (the sweep runs backwards)"""
-    d = sets_a != sets_b
-    return np.flip(np.logical_or.accumulate(np.flip(d, 0), 0), 0)
 
 
 @pytest.mark.parametrize('task', TASKS)
@@ -215,6 +125,7 @@ def test_backward_sweep_on_the_host(task, harness):
         seen |= set(np.unique(sets[~bad]).tolist())
         assert np.isfinite(gains).all() and np.isfinite(dv).all()
         keep = ~bad
+        assert keep.any()
         bound_check(np.moveaxis(gains, 1, 2), np.moveaxis(g32, 1, 2), np.moveaxis(g64, 1, 2), keep, 'host gains %s %s' % (task, s.name))
         row_ok = keep.all(0)
         if row_ok.any():

@@ -1,72 +1,10 @@
-"""CPU (-m "not gpu"): the sampled-tape ABI (include/envbuild_sample.h) is declared as ctypes binds it, exported by the built library
-next to a gfx950 kernel, kept out of the hashed forward sources, and refused cleanly by a library without it; the NumPy / torch
+"""CPU (-m "not gpu"): the sampled-tape family on the host (the ABI of include/envbuild_sample.h: tests/test_family_abi.py): the NumPy / torch
 restatement of the noise and the samples (env_build_amd/sample.py) has the moments, the AR(1) correlation, the repeatability and the
 env-id keying the header states; SamplingMPC's loop (mpc.sampling_loop) is elitist on a non-convex toy cost."""
-import ctypes as C
 import math
-import os
-import re
 
 import numpy as np
 import pytest
-
-from env_build_amd import _capi, build as eb_build
-from tests._helpers import ROOT, oracle_lib
-
-HEADER = os.path.join(ROOT, 'include', 'envbuild_sample.h')
-
-
-def header_source():
-    return re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-
-
-def test_sample_header_declares_what_ctypes_binds():
-    src = header_source()
-    assert sorted(_capi.SAMPLE_PROTOTYPES) == sorted(set(re.findall(r'\b(eb_[a-z0-9_]+)\s*\(', src)))
-    for name, (_res, args) in _capi.SAMPLE_PROTOTYPES.items():
-        m = re.search(r'\bint\s+%s\s*\(([^)]*)\)\s*;' % name, src)
-        assert m, '%s is not declared in include/envbuild_sample.h' % name
-        declared = [a for a in m.group(1).split(',') if a.strip() != 'void']
-        assert len(declared) == len(args), name
-    assert len(_capi.SAMPLE_PROTOTYPES['eb_rollout_tape_sample'][1]) == 22
-    # a table of its own
-    for other in (_capi.PROTOTYPES, _capi.GRAD_PROTOTYPES, _capi.CAND_PROTOTYPES, _capi.CAND_GRAD_PROTOTYPES):
-        assert not set(_capi.SAMPLE_PROTOTYPES) & set(other)
-    assert _capi.EB_SAMPLE_ABI_VERSION == 1 and int(re.search(r'#define EB_SAMPLE_ABI_VERSION (\d+)', src).group(1)) == 1
-
-
-def test_the_four_older_abi_numbers_are_unchanged():
-    assert (_capi.EB_ABI_VERSION, _capi.EB_GRAD_ABI_VERSION, _capi.EB_CAND_ABI_VERSION, _capi.EB_CAND_GRAD_ABI_VERSION) == (5, 2, 1, 1)
-    for header, macro, want in (('envbuild.h', 'EB_ABI_VERSION', 5), ('envbuild_grad.h', 'EB_GRAD_ABI_VERSION', 2),
-                                ('envbuild_cand.h', 'EB_CAND_ABI_VERSION', 1), ('envbuild_cand_grad.h', 'EB_CAND_GRAD_ABI_VERSION', 1)):
-        text = open(os.path.join(ROOT, 'include', header)).read()
-        assert int(re.search(r'#define %s (\d+)' % macro, text).group(1)) == want, header
-
-
-def test_hip_library_exports_the_sample_entries_and_a_gfx950_kernel():
-    lib_path = eb_build.build()            # hipcc --offload-arch=gfx950 (cross-compiles without a GPU)
-    import torch  # noqa: F401  (binds the HIP runtime torch ships before ours, as the product does)
-    lib = C.CDLL(lib_path)
-    for name in _capi.SAMPLE_PROTOTYPES:
-        assert hasattr(lib, name), name
-    assert lib.eb_sample_abi_version() == 1
-    blob = open(lib_path, 'rb').read()
-    assert b'gfx950' in blob and b'rollout_tape_sample_kernel' in blob
-    assert 'eb_rollout_tape_sample.hip' in eb_build.SOURCES and 'eb_sample.h' in eb_build.HEADERS
-    # a translation unit of its own: the forward kernels' hashes (profiles/ ties HBM-traffic records to them) do not see it
-    for files in eb_build.KERNEL_SOURCES.values():
-        assert 'eb_rollout_tape_sample.hip' not in files and 'eb_sample.h' not in files
-
-
-def test_a_library_without_the_sample_entries_is_refused_cleanly():
-    api = oracle_lib()                     # CApi binds every PROTOTYPES entry on it, as before
-    assert api.backend == 'oracle'
-    for name in ('rollout_tape_sample', 'rollout_tape_sample_max', 'sample_abi_version'):
-        with pytest.raises(_capi.EbError) as e:
-            getattr(api, name)
-        assert 'sampled-tape' in str(e.value)
-    with pytest.raises(_capi.EbError):
-        api.sample_fn('eb_rollout_tape_sample')
 
 
 # ---- the restatement of the noise and the samples ----
