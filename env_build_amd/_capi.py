@@ -204,6 +204,24 @@ FAMILIES = {
     'ilqr': ('envbuild_ilqr.h', 'iLQR iteration', 'iLQR', 'eb_ilqr_abi_version', EB_ILQR_ABI_VERSION, ILQR_PROTOTYPES),
 }
 
+# include/envbuild_mlp_f16.h: the policy handle's inference precision (binary16 operands on the matrix cores).  A table with a version
+# of its own like the others, kept in a SECOND family table: FAMILIES is the tape-and-gradient set its tests enumerate.
+EB_MLP_F16_ABI_VERSION = 1
+MLP_PRECISION_ID = {'fp32': 0, 'fp16': 1}                              # EB_MLP_PRECISION_*
+MLP_F16_PROTOTYPES = {
+    'eb_mlp_f16_abi_version': (C.c_int, []),
+    'eb_mlp_set_precision': (C.c_int, [_P, _I]),
+    'eb_mlp_get_precision': (C.c_int, [_P, C.POINTER(_I)]),
+}
+MORE_FAMILIES = {
+    'mlp_f16': ('envbuild_mlp_f16.h', 'fp16 policy', 'fp16-policy', 'eb_mlp_f16_abi_version', EB_MLP_F16_ABI_VERSION, MLP_F16_PROTOTYPES),
+}
+
+
+def family_row(family):
+    """The six-tuple of one optional family, FAMILIES first, then MORE_FAMILIES."""
+    return FAMILIES[family] if family in FAMILIES else MORE_FAMILIES[family]
+
 
 class EbError(RuntimeError):
     pass
@@ -225,9 +243,9 @@ class CApi(object):
         self.backend = self.lib.eb_backend().decode()
 
     def family_fn(self, family, symbol):
-        """The raw ctypes function of one entry of an optional family (a key of FAMILIES), the family bound on first use; EbError when
-        this library does not export it or speaks another version of it."""
-        header, label, abi, version_symbol, version, prototypes = FAMILIES[family]
+        """The raw ctypes function of one entry of an optional family (a key of FAMILIES or MORE_FAMILIES), the family bound on first use;
+        EbError when this library does not export it or speaks another version of it."""
+        header, label, abi, version_symbol, version, prototypes = family_row(family)
         fns = self.__dict__.setdefault('_%s_fns' % family, {})
         if not fns:
             missing = [n for n in prototypes if not hasattr(self.lib, n)]
@@ -258,6 +276,9 @@ class CApi(object):
 
     def ilqr_fn(self, symbol):
         return self.family_fn('ilqr', symbol)
+
+    def mlp_f16_fn(self, symbol):
+        return self.family_fn('mlp_f16', symbol)
 
     def check(self, rc):
         if rc != 0:
@@ -305,7 +326,7 @@ class CApi(object):
     def __getattr__(self, name):
         # eb_xxx(...) with return-code checking: api.rollout_step(h, ...)
         sym = 'eb_' + name
-        family = next((f for f, row in FAMILIES.items() if sym in row[5]), None)
+        family = next((f for table in (FAMILIES, MORE_FAMILIES) for f, row in table.items() if sym in row[5]), None)
         fn = self.family_fn(family, sym) if family else getattr(self.lib, sym)
 
         def call(*args):

@@ -27,6 +27,8 @@
 #include "eb_sample.h"
 #include "../../include/envbuild_ilqr.h"
 #include "eb_ilqr.h"
+#include "../../include/envbuild_mlp_f16.h"
+#include "eb_policy_f16.h"
 #include "eb_grad.h"
 #include "eb_kernels.h"
 
@@ -1556,6 +1558,8 @@ struct eb_mlp_s {
     float* d_scale;
     bool has_scale;
     unsigned layers_set;
+    int precision;                   // EB_MLP_PRECISION_* (include/envbuild_mlp_f16.h); both packings are kept, this picks the kernel
+    uint16_t* d_w16[EB_MLP_MAX_HIDDEN + 1];   // the binary16 packing of every layer (eb_policy_f16.hip)
 };
 
 static int mlp_layer_dims(const eb_mlp_s* m, int layer, int* k_real, int* cols_real, int* k_pad, int* col_tiles) {
@@ -1565,6 +1569,12 @@ static int mlp_layer_dims(const eb_mlp_s* m, int layer, int* k_real, int* cols_r
     *k_pad = layer == 0 ? m->k_pad0 : m->units;
     *col_tiles = out ? 1 : m->units / 32;
     return 0;
+}
+
+// halves of a layer's binary16 packing: k padded to 16 (layer 0) or the padded width, times the tile columns
+static size_t mlp_f16_elems(const eb_mlp_s* m, int layer) {
+    const int kp = layer == 0 ? eb::mlp_f16_k_pad0(m->cfg.obs_dim) : m->units;
+    return (size_t)kp * (layer == m->cfg.n_hidden ? 32 : m->units);
 }
 
 static int mlp_args(eb_mlp m, int32_t n, const float* obs, float* out, int head, float action_range, eb::MlpArgs* A,
@@ -1585,6 +1595,22 @@ static int mlp_args(eb_mlp m, int32_t n, const float* obs, float* out, int head,
     for (int L = m->cfg.n_hidden; L < eb::MLP_MAX_HIDDEN; ++L) A->hid[L] = eb::MlpLayer{nullptr, nullptr, 0, 0};
     A->outl.w = m->d_w[m->cfg.n_hidden]; A->outl.b = m->d_b[m->cfg.n_hidden]; A->outl.k_pad = m->units; A->outl.pad_ = 0;
     return EB_OK;
+}
+
+// the launch of one policy evaluation by the handle's precision: the fp32 arguments restated for the binary16 kernel
+static hipError_t mlp_launch(eb_mlp m, const eb::MlpArgs& A, hipStream_t s) {
+    if (m->precision == EB_MLP_PRECISION_F32) return eb::launch_mlp(A, s);
+    eb::MlpF16Args H;
+    H.obs = A.obs; H.scale = A.scale; H.out = A.out;
+    H.n = A.n; H.obs_dim = A.obs_dim; H.n_hidden = A.n_hidden; H.units = A.units; H.n_units = m->cfg.n_units;
+    H.out_dim = A.out_dim; H.hidden_act = A.hidden_act; H.out_act = A.out_act; H.head = A.head;
+    H.action_range = A.action_range;
+    H.row_stride = eb::mlp_f16_row_stride(m->cfg.obs_dim, m->units);
+    for (int L = 0; L < eb::MLP_MAX_HIDDEN; ++L)
+        H.hid[L] = L < m->cfg.n_hidden ? eb::MlpF16Layer{m->d_w16[L], m->d_b[L], L == 0 ? eb::mlp_f16_k_pad0(m->cfg.obs_dim) : m->units, 0}
+                                       : eb::MlpF16Layer{nullptr, nullptr, 0, 0};
+    H.outl = eb::MlpF16Layer{m->d_w16[m->cfg.n_hidden], m->d_b[m->cfg.n_hidden], m->units, 0};
+    return eb::launch_mlp_f16(H, s);
 }
 
 extern "C" {
@@ -1660,6 +1686,7 @@ int eb_mlp_create(const eb_mlp_config* cfg, eb_mlp* out) {
         mlp_layer_dims(m, L, &kr, &cr, &kp, &ct);
         hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->d_w[L]), sizeof(float) * (size_t)kp * ct * 32);
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_b[L]), sizeof(float) * ct * 32);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_w16[L]), sizeof(uint16_t) * mlp_f16_elems(m, L));
         if (e != hipSuccess) { eb_mlp_destroy(m); return fail_hip("hipMalloc(mlp layer)", e); }
     }
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->d_scale), sizeof(float) * cfg->obs_dim);
@@ -1673,6 +1700,7 @@ int eb_mlp_destroy(eb_mlp m) {
     for (int L = 0; L <= EB_MLP_MAX_HIDDEN; ++L) {
         if (m->d_w[L]) (void)hipFree(m->d_w[L]);
         if (m->d_b[L]) (void)hipFree(m->d_b[L]);
+        if (m->d_w16[L]) (void)hipFree(m->d_w16[L]);
     }
     if (m->d_scale) (void)hipFree(m->d_scale);
     delete m;
@@ -1687,8 +1715,13 @@ int eb_mlp_set_layer(eb_mlp m, int32_t layer, const float* kernel, const float* 
     if (layer == m->cfg.n_hidden) eb::pack_weights16(kernel, kr, cr, kp, wp.data());   // (<= 2 tiles of 16: fits the 32-column buffer)
     else eb::pack_weights(kernel, kr, cr, kp, ct, wp.data());
     std::copy(bias, bias + cr, bp.begin());
+    // the binary16 packing next to the fp32 one: switching precision never needs the weights again (envbuild_mlp_f16.h)
+    std::vector<uint16_t> hp(mlp_f16_elems(m, layer), 0);
+    if (layer == m->cfg.n_hidden) eb::pack_weights16_f16(kernel, kr, cr, m->units, hp.data());
+    else eb::pack_weights_f16(kernel, kr, cr, layer == 0 ? eb::mlp_f16_k_pad0(m->cfg.obs_dim) : m->units, ct, hp.data());
     EB_HIP(hipSetDevice(m->cfg.device));
     EB_HIP(hipMemcpy(m->d_w[layer], wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
+    EB_HIP(hipMemcpy(m->d_w16[layer], hp.data(), hp.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     EB_HIP(hipMemcpy(m->d_b[layer], bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
     m->layers_set |= 1u << layer;
     return EB_OK;
@@ -1709,7 +1742,7 @@ int eb_mlp_forward(eb_mlp m, int32_t n, const float* obs, float* out, void* stre
     int rc = mlp_args(m, n, obs, out, eb::MLP_HEAD_LOGITS, 0.0f, &A, "eb_mlp_forward: null handle");
     if (rc || n == 0) return rc;
     EB_HIP(hipSetDevice(m->cfg.device));
-    EB_HIP(eb::launch_mlp(A, (hipStream_t)stream));
+    EB_HIP(mlp_launch(m, A, (hipStream_t)stream));
     return EB_OK;
 }
 
@@ -1718,7 +1751,7 @@ int eb_policy_run_batch(eb_mlp m, int32_t n, const float* obs, float action_rang
     int rc = mlp_args(m, n, obs, actions, eb::MLP_HEAD_ACTION, action_range, &A, "eb_policy_run_batch: null handle");
     if (rc || n == 0) return rc;
     EB_HIP(hipSetDevice(m->cfg.device));
-    EB_HIP(eb::launch_mlp(A, (hipStream_t)stream));
+    EB_HIP(mlp_launch(m, A, (hipStream_t)stream));
     return EB_OK;
 }
 
@@ -1745,7 +1778,7 @@ int eb_shield_is_safe(eb_handle h, eb_mlp policy, int32_t n_env, const float* ob
         float* dst = (t & 1) ? obs_b : obs_a;
         rc = mlp_args(policy, n_env, cur, actions, eb::MLP_HEAD_ACTION, action_range, &A, "eb_shield_is_safe: null policy");
         if (rc) return rc;
-        EB_HIP(eb::launch_mlp(A, s));
+        EB_HIP(mlp_launch(policy, A, s));
         const ShieldArgs sh{punish, safe, penalty == EB_PENALTY_VEH2VEH4REAL ? 3 : 2, t == 0, t == steps - 1};   // rows of rollout_out's outputs (DAM:126)
         RolloutLaunch r{cur, dst, actions, ref_idx, path_id, out5};
         r.shield = &sh;
@@ -1753,6 +1786,24 @@ int eb_shield_is_safe(eb_handle h, eb_mlp policy, int32_t n_env, const float* ob
         if (rc) return rc;
         cur = dst;
     }
+    return EB_OK;
+}
+
+// ---- include/envbuild_mlp_f16.h: the handle's inference precision ----
+int eb_mlp_f16_abi_version(void) { return EB_MLP_F16_ABI_VERSION; }
+
+int eb_mlp_set_precision(eb_mlp m, int32_t precision) {
+    if (!m) return fail(EB_EINVAL, "eb_mlp_set_precision: null handle");
+    if (precision != EB_MLP_PRECISION_F32 && precision != EB_MLP_PRECISION_F16)
+        return fail(EB_EINVAL, "eb_mlp_set_precision: unknown precision (EB_MLP_PRECISION_F32 or EB_MLP_PRECISION_F16)");
+    m->precision = precision;
+    return EB_OK;
+}
+
+int eb_mlp_get_precision(eb_mlp m, int32_t* precision) {
+    if (!m) return fail(EB_EINVAL, "eb_mlp_get_precision: null handle");
+    if (!precision) return fail(EB_EINVAL, "eb_mlp_get_precision: null output pointer");
+    *precision = m->precision;
     return EB_OK;
 }
 

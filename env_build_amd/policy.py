@@ -3,7 +3,8 @@
 the 'scale' observation preprocessor (utils/preprocessor.py:116-123).
 
 Same names, constructor arguments and methods as the reference; the arithmetic is one fused HIP kernel per call
-(env_build_amd/csrc/eb_policy.hip: fp32 matrix cores, the whole network in one launch).  Training (optimisers,
+(env_build_amd/csrc/eb_policy.hip: fp32 matrix cores, the whole network in one launch; with precision='fp16' the opt-in
+binary16 kernel of env_build_amd/csrc/eb_policy_f16.hip, include/envbuild_mlp_f16.h).  Training (optimisers,
 stochastic sampling, log-probabilities) is out of scope — the shield and the path selection only ever call
 `run_batch` / `obj_value_batch`.
 
@@ -22,7 +23,7 @@ import torch
 from . import _capi
 from .dynamics_and_models import DevArray, _dev, _resolve_device, _stream
 
-__all__ = ['MLPNet', 'Policy4Toyota', 'LoadPolicy', 'orthogonal']
+__all__ = ['MLPNet', 'Policy4Toyota', 'LoadPolicy', 'orthogonal', 'mlp_f16_reference']
 
 
 def orthogonal(rng, rows, cols, gain):
@@ -35,8 +36,99 @@ def orthogonal(rng, rows, cols, gain):
     return (gain * q[:rows, :cols]).astype(np.float32)
 
 
+def _fma32(a, b, c):
+    """fmaf on float32 arrays through float64: the product is exact there, the sum rounds twice (float64, then float32)."""
+    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(np.float32)
+
+
+def _exp_det(x0):
+    """csrc/eb_policy.hip:exp_det (the oracle's eb_expf) on a float32 array."""
+    x0 = np.asarray(x0, np.float32)
+    with np.errstate(all='ignore'):
+        x = np.where(x0 > 88, np.float32(88), np.where(x0 < -87, np.float32(-87), x0)).astype(np.float32)
+        fx = np.rint(x * np.float32(1.44269504088896341)).astype(np.float32)
+        r = _fma32(-fx, np.float32(0.693359375), x)
+        r = _fma32(-fx, np.float32(-2.12194440e-4), r)
+        z = r * r
+        p = np.full_like(r, 1.9875691500e-4)
+        for c in (1.3981999507e-3, 8.3334519073e-3, 4.1665795894e-2, 1.6666665459e-1, 5.0000001201e-1):
+            p = _fma32(p, r, np.float32(c))
+        y = _fma32(p, z, r) + np.float32(1)
+        n = np.where(np.isnan(x0), 0, fx).astype(np.int32)
+        v = y * ((n + 127).astype(np.uint32) << np.uint32(23)).view(np.float32)
+    return np.where(np.isnan(x0), x0, v).astype(np.float32)
+
+
+def _tanh_det(x):
+    """csrc/eb_policy.hip:tanh_det (the oracle's eb_tanhf) on a float32 array."""
+    x = np.asarray(x, np.float32)
+    with np.errstate(all='ignore'):
+        ax = np.abs(x)
+        s = _exp_det(ax + ax)
+        t = np.float32(1) - np.float32(2) / (s + np.float32(1))
+        big = np.where(x < 0, -t, t)
+        z = x * x
+        p = np.full_like(x, -5.70498872745e-3)
+        for c in (2.06390887954e-2, -5.37397155531e-2, 1.33314422036e-1, -3.33332819422e-1):
+            p = _fma32(p, z, np.float32(c))
+        small = _fma32(p * z, x, x)
+        sat = np.where(x > 0, np.float32(1), np.float32(-1))
+    return np.where(ax > 44, sat, np.where(ax >= 0.625, big, small)).astype(np.float32)
+
+
+def _act_det(act, x):
+    x = np.asarray(x, np.float32)
+    if act == 'relu':
+        return np.where(x > 0, x, np.float32(0)).astype(np.float32)
+    if act == 'elu':
+        with np.errstate(all='ignore'):
+            return np.where(x > 0, x, _exp_det(x) - np.float32(1)).astype(np.float32)
+    if act == 'tanh':
+        return _tanh_det(x)
+    return x
+
+
+def mlp_f16_reference(layers, obs, hidden_act, out_act, obs_scale=None, accumulate=np.float32, k_block=None, reverse=False):
+    """The arithmetic contract of include/envbuild_mlp_f16.h in NumPy — the counterpart of `sample.sample_tapes_reference`: what
+    eb_mlp_forward gives on a handle whose precision is 'fp16', up to the order of each sum.
+
+    layers: [(kernel [in, out], bias [out]), ...]; obs [n, in] float32.  Inputs, weights and hidden activations are rounded with
+    astype(np.float16) (IEEE round-to-nearest-even, overflow to inf, subnormals kept: so does the kernel); biases stay float32;
+    a pre-activation is the bias plus the products (exact in float32) summed in `accumulate` (np.float32 or np.float64) in ascending
+    k; the activation is the deterministic float32 one (its fused multiply-adds go through float64 here: a last-bit difference from
+    fmaf is possible where that rounds twice), and the output layer's result is float32.
+
+    k_block / reverse give a second accumulation order for tests: the products of each block of k_block consecutive k are summed
+    exactly (float64), rounded once to `accumulate`, and the blocks are added in ascending (or, with reverse, descending) order.
+    The kernel's own order is neither: the contract leaves it open."""
+    acc_t = np.dtype(accumulate).type
+    x = np.asarray(obs, np.float32)
+    if obs_scale is not None:
+        x = x * np.asarray(obs_scale, np.float32)
+    with np.errstate(all='ignore'):
+        x = x.astype(np.float16)
+        for L, (w, b) in enumerate(layers):
+            w16 = np.asarray(w, np.float32).astype(np.float16)
+            K = w16.shape[0]
+            acc = np.broadcast_to(np.asarray(b, np.float32).astype(acc_t), (x.shape[0], w16.shape[1])).copy()
+            if k_block is None:
+                for k in range(K):       # float32 products of binary16 values are exact
+                    acc = acc + (x[:, k:k + 1].astype(np.float32) * w16[k:k + 1, :].astype(np.float32)).astype(acc_t)
+            else:
+                starts = list(range(0, K, k_block))
+                for k0 in (reversed(starts) if reverse else starts):
+                    part = x[:, k0:k0 + k_block].astype(np.float64) @ w16[k0:k0 + k_block, :].astype(np.float64)
+                    acc = acc + part.astype(acc_t)
+            pre = acc.astype(np.float32)
+            if L == len(layers) - 1:
+                return _act_det(out_act, pre)
+            x = _act_det(hidden_act, pre).astype(np.float16)
+
+
 class MLPNet(object):
-    """utils/model.py:18-43.  `hidden_activation` / `output_activation` in {'elu', 'relu', 'tanh', 'linear', None}."""
+    """utils/model.py:18-43.  `hidden_activation` / `output_activation` in {'elu', 'relu', 'tanh', 'linear', None}.
+    `precision` in {'fp32', 'fp16'}: 'fp32' (the default) is the bit-exact fp32 chain; 'fp16' evaluates with binary16 operands on the
+    matrix cores (include/envbuild_mlp_f16.h) — faster, not reproducible bit for bit on the CPU."""
 
     def __init__(self, input_dim, num_hidden_layers, num_hidden_units, hidden_activation, output_dim, **kwargs):
         self.name = kwargs.get('name', 'mlp')
@@ -52,6 +144,8 @@ class MLPNet(object):
         self.api = _capi.hip_api()
         self._obs_scale = None
         self._handle = None
+        self.precision = kwargs.get('precision', 'fp32')
+        self._check_precision(self.precision)
         rng = np.random.default_rng(kwargs.get('seed', 0))
         dims = [self.input_dim] + [self.num_hidden_units] * self.num_hidden_layers + [self.output_dim]
         w = []
@@ -76,11 +170,29 @@ class MLPNet(object):
         self._obs_scale = None if obs_scale is None else np.ascontiguousarray(obs_scale, np.float32)
         self._rebuild()
 
+    @staticmethod
+    def _check_precision(precision):
+        if precision not in _capi.MLP_PRECISION_ID:
+            raise ValueError("precision must be 'fp32' or 'fp16', got %r" % (precision,))
+
+    def set_precision(self, precision):
+        """'fp32' | 'fp16': what every later forward, `mode` and the native shield evaluate this network with.  The weights are kept
+        in both packings, so the switch is a flag."""
+        self._check_precision(precision)
+        self.api.mlp_set_precision(self._handle, _capi.MLP_PRECISION_ID[precision])
+        self.precision = precision
+
     def _rebuild(self):
         layers = list(zip(self._weights[0::2], self._weights[1::2]))
         index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         new = self.api.mlp_create_from(self.input_dim, self.num_hidden_layers, self.num_hidden_units, self.output_dim,
                                        self.hidden_activation, self.output_activation, layers, self._obs_scale, index)
+        if self.precision != 'fp32':
+            try:
+                self.api.mlp_set_precision(new, _capi.MLP_PRECISION_ID[self.precision])
+            except Exception:
+                self.api.lib.eb_mlp_destroy(new)
+                raise
         if self._handle is not None:
             torch.cuda.synchronize(self.device)
             self.api.lib.eb_mlp_destroy(self._handle)
@@ -123,16 +235,19 @@ class MLPNet(object):
 
 class Policy4Toyota(object):
     """utils/policy.py:19-101, inference side.  `args` carries obs_dim, act_dim, num_hidden_layers, num_hidden_units,
-    hidden_activation, policy_out_activation, action_range, deterministic_policy (as the experiment's config.json)."""
+    hidden_activation, policy_out_activation, action_range, deterministic_policy (as the experiment's config.json), and optionally
+    policy_precision ('fp32', the default, or 'fp16': MLPNet's `precision`, for both networks)."""
 
     def __init__(self, args, device=None, seed=0):
         self.args = args
         obs_dim, act_dim = int(args.obs_dim), int(args.act_dim)
         n_hiddens, n_units, act = int(args.num_hidden_layers), int(args.num_hidden_units), args.hidden_activation
+        precision = getattr(args, 'policy_precision', 'fp32') or 'fp32'
         self.policy = MLPNet(obs_dim, n_hiddens, n_units, act, act_dim * 2, name='policy',
-                             output_activation=getattr(args, 'policy_out_activation', 'linear'), device=device, seed=seed)
+                             output_activation=getattr(args, 'policy_out_activation', 'linear'), device=device, seed=seed,
+                             precision=precision)
         self.obj_v = MLPNet(obs_dim, n_hiddens, n_units, act, 1, name='obj_v', output_activation='relu',
-                            device=device, seed=seed + 1)
+                            device=device, seed=seed + 1, precision=precision)
         self.models = (self.obj_v, self.policy,)
 
     def get_weights(self):
