@@ -217,10 +217,29 @@ MORE_FAMILIES = {
     'mlp_f16': ('envbuild_mlp_f16.h', 'fp16 policy', 'fp16-policy', 'eb_mlp_f16_abi_version', EB_MLP_F16_ABI_VERSION, MLP_F16_PROTOTYPES),
 }
 
+# include/envbuild_policy_rollout.h: `steps` x [policy -> model step] in one launch.  A table with a version of its own like the others,
+# kept in a THIRD family table: the first two are the sets their tests enumerate.
+EB_POLICY_ROLLOUT_ABI_VERSION = 1
+POLICY_ROLLOUT_PROTOTYPES = {
+    'eb_policy_rollout_abi_version': (C.c_int, []),
+    'eb_policy_rollout_supported': (C.c_int, [_P, _P, C.POINTER(_I)]),
+    # (h, policy, n_env, steps, obs_in, ref_idx, path_id, action_range, penalty, obs_out, out5_steps, actions_steps, obs_steps, punish,
+    #  safe, stream)
+    'eb_policy_rollout': (C.c_int, [_P, _P, _I, _I, _P, _P, _I, C.c_float, _I, _P, _P, _P, _P, _P, _P, _P]),
+}
+POLICY_FAMILIES = {
+    'policy_rollout': ('envbuild_policy_rollout.h', 'closed-loop policy rollout', 'policy-rollout', 'eb_policy_rollout_abi_version',
+                       EB_POLICY_ROLLOUT_ABI_VERSION, POLICY_ROLLOUT_PROTOTYPES),
+}
+_FAMILY_TABLES = (FAMILIES, MORE_FAMILIES, POLICY_FAMILIES)
+
 
 def family_row(family):
-    """The six-tuple of one optional family, FAMILIES first, then MORE_FAMILIES."""
-    return FAMILIES[family] if family in FAMILIES else MORE_FAMILIES[family]
+    """The six-tuple of one optional family: FAMILIES first, then MORE_FAMILIES, then POLICY_FAMILIES."""
+    for table in _FAMILY_TABLES:
+        if family in table:
+            return table[family]
+    raise KeyError(family)
 
 
 class EbError(RuntimeError):
@@ -243,7 +262,7 @@ class CApi(object):
         self.backend = self.lib.eb_backend().decode()
 
     def family_fn(self, family, symbol):
-        """The raw ctypes function of one entry of an optional family (a key of FAMILIES or MORE_FAMILIES), the family bound on first use;
+        """The raw ctypes function of one entry of an optional family (a key of FAMILIES, MORE_FAMILIES or POLICY_FAMILIES), the family bound on first use;
         EbError when this library does not export it or speaks another version of it."""
         header, label, abi, version_symbol, version, prototypes = family_row(family)
         fns = self.__dict__.setdefault('_%s_fns' % family, {})
@@ -279,6 +298,9 @@ class CApi(object):
 
     def mlp_f16_fn(self, symbol):
         return self.family_fn('mlp_f16', symbol)
+
+    def policy_rollout_fn(self, symbol):
+        return self.family_fn('policy_rollout', symbol)
 
     def check(self, rc):
         if rc != 0:
@@ -326,7 +348,7 @@ class CApi(object):
     def __getattr__(self, name):
         # eb_xxx(...) with return-code checking: api.rollout_step(h, ...)
         sym = 'eb_' + name
-        family = next((f for table in (FAMILIES, MORE_FAMILIES) for f, row in table.items() if sym in row[5]), None)
+        family = next((f for table in _FAMILY_TABLES for f, row in table.items() if sym in row[5]), None)
         fn = self.family_fn(family, sym) if family else getattr(self.lib, sym)
 
         def call(*args):

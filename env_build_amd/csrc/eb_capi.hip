@@ -29,6 +29,8 @@
 #include "eb_ilqr.h"
 #include "../../include/envbuild_mlp_f16.h"
 #include "eb_policy_f16.h"
+#include "../../include/envbuild_policy_rollout.h"
+#include "eb_policy_rollout.h"
 #include "eb_grad.h"
 #include "eb_kernels.h"
 
@@ -2145,6 +2147,81 @@ int eb_rollout_tape_ilqr(eb_handle h, int32_t n_env, int32_t horizon, int32_t n_
     fill_tape_scene(h, n_env, horizon, A);
     A.n_alpha = n_alpha; A.path_id = path_id;
     EB_HIP(eb::launch_rollout_tape_ilqr(h->cfg.task, A, (hipStream_t)stream));
+    return EB_OK;
+}
+
+}  // extern "C"
+
+// ---- include/envbuild_policy_rollout.h: `steps` x [policy -> model step] in one launch (eb_policy_rollout.hip) ----
+// the first condition of eb_policy_rollout_supported's list this pair of handles does not meet, in g_err; true when there is none
+static bool policy_rollout_fits(eb_handle h, eb_mlp m) {
+    const int D = obs_dim(h->cfg);
+    if (m->precision != EB_MLP_PRECISION_F16)
+        fail(EB_EINVAL, "eb_policy_rollout: the policy's precision must be EB_MLP_PRECISION_F16 (eb_mlp_set_precision)");
+    else if (m->cfg.obs_dim != D)
+        fail_limit("eb_policy_rollout: the policy's obs_dim %d is not the model's %d", (int)m->cfg.obs_dim, D);
+    else if (m->cfg.out_dim != 4)
+        fail_limit("eb_policy_rollout: the policy's out_dim %d is not 4 (mean and log-std of two actions)", (int)m->cfg.out_dim);
+    else if (m->units > eb::PR_MAX_UNITS)
+        fail_limit("eb_policy_rollout: hidden width %d pads to %d, beyond the kernel's limit of %d", (int)m->cfg.n_units, m->units, eb::PR_MAX_UNITS);
+    else if (h->cfg.n_veh > eb::PR_MAX_VEH)
+        fail_limit("eb_policy_rollout: n_veh %d exceeds the kernel's limit of %d vehicle slots", (int)h->cfg.n_veh, eb::PR_MAX_VEH);
+    else if (h->cfg.n_future != 0)
+        fail_limit("eb_policy_rollout: n_future %d is not supported (0, the reference's default)", (int)h->cfg.n_future);
+    else if (m->cfg.device != h->cfg.device)
+        fail(EB_EINVAL, "eb_policy_rollout: policy and model live on different devices");
+    else
+        return true;
+    return false;
+}
+
+extern "C" {
+
+int eb_policy_rollout_abi_version(void) { return EB_POLICY_ROLLOUT_ABI_VERSION; }
+
+int eb_policy_rollout_supported(eb_handle h, eb_mlp policy, int32_t* ok) {
+    if (!h) return fail(EB_EINVAL, "eb_policy_rollout_supported: null handle");
+    if (!policy) return fail(EB_EINVAL, "eb_policy_rollout_supported: null policy");
+    if (!ok) return fail(EB_EINVAL, "eb_policy_rollout_supported: null output pointer");
+    *ok = policy_rollout_fits(h, policy) ? 1 : 0;
+    return EB_OK;
+}
+
+int eb_policy_rollout(eb_handle h, eb_mlp policy, int32_t n_env, int32_t steps, const float* obs_in, const int32_t* ref_idx,
+                      int32_t path_id, float action_range, int32_t penalty, float* obs_out, float* out5_steps,
+                      float* actions_steps, float* obs_steps, float* punish, uint8_t* safe, void* stream) {
+    if (h && policy && n_env == 0) return EB_OK;
+    int rc = check_tape(h, "eb_policy_rollout: null handle");
+    if (rc) return rc;
+    if (!policy) return fail(EB_EINVAL, "eb_policy_rollout: null policy");
+    if (n_env < 0 || steps < 1 || !obs_in || !obs_out || obs_in == obs_out) return fail(EB_EINVAL, "eb_policy_rollout: bad argument");
+    if (penalty != EB_PENALTY_VEH2VEH4REAL && penalty != EB_PENALTY_REAL_PUNISH_TERM) return fail(EB_EINVAL, "eb_policy_rollout: unknown penalty");
+    if (!policy_rollout_fits(h, policy)) return EB_EINVAL;
+    if (policy->layers_set != (1u << (policy->cfg.n_hidden + 1)) - 1u)
+        return fail(EB_ESTATE, "eb_policy_rollout: eb_mlp_set_layer has not been called for every layer");
+    rc = check_path_arg(h, &ref_idx, &path_id);
+    if (rc) return rc;
+    EB_HIP(hipSetDevice(h->cfg.device));
+    eb::PolicyRolloutArgs A;
+    std::memset(&A, 0, sizeof A);
+    fill_tape_scene(h, n_env, steps, A);
+    A.obs0 = obs_in; A.ref_idx = ref_idx; A.path_id = path_id;
+    A.obs_out = obs_out; A.out5_steps = out5_steps; A.actions_steps = actions_steps; A.obs_steps = obs_steps;
+    A.punish = punish; A.safe = safe;
+    A.penalty_row = penalty == EB_PENALTY_VEH2VEH4REAL ? 3 : 2;               // rows of rollout_out's outputs (DAM:126)
+    A.nv_magic = eb::div_magic(A.n_veh);
+    // the policy, as mlp_launch hands it to the binary16 kernel
+    const eb_mlp_s* m = policy;
+    A.scale = m->has_scale ? m->d_scale : nullptr;
+    A.n_hidden = m->cfg.n_hidden; A.units = m->units; A.n_units = m->cfg.n_units;
+    A.hidden_act = m->cfg.hidden_act; A.out_act = m->cfg.out_act;
+    A.action_range = action_range;
+    A.row_stride = eb::mlp_f16_row_stride(m->cfg.obs_dim, m->units);
+    for (int L = 0; L < eb::MLP_MAX_HIDDEN; ++L)
+        A.hid[L] = L < m->cfg.n_hidden ? eb::MlpF16Layer{m->d_w16[L], m->d_b[L], L == 0 ? eb::mlp_f16_k_pad0(m->cfg.obs_dim) : m->units, 0}
+                                       : eb::MlpF16Layer{nullptr, nullptr, 0, 0};
+    A.outl = eb::MlpF16Layer{m->d_w16[m->cfg.n_hidden], m->d_b[m->cfg.n_hidden], m->units, 0};
+    EB_HIP(eb::launch_policy_rollout(h->cfg.task, A, (hipStream_t)stream));
     return EB_OK;
 }
 

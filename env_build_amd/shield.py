@@ -20,11 +20,18 @@ PENALTIES = {'veh2veh4real': 4, 'real_punish_term': 3}       # index into rollou
 SAFE_ACTION = (0., -1.)                                        # action_safe_set, hier_decision.py:100
 
 
-def is_safe(model, policy, obses, path_index=None, steps=5, penalty='veh2veh4real'):
+def is_safe(model, policy, obses, path_index=None, steps=5, penalty='veh2veh4real', fused=False):
     """-> (safe [B] bool DevArray, accumulated penalty [B] DevArray).  `path_index` selects the path for a model in
-    'selecting' mode (model.add_traj, hier_decision.py:91); a 'training'-mode model keeps its ref_indexes."""
+    'selecting' mode (model.add_traj, hier_decision.py:91); a 'training'-mode model keeps its ref_indexes.
+    `fused=True` takes the whole look-ahead through ONE launch where model and policy fit the kernel (an fp16 native policy;
+    env_build_amd/policy_rollout.py), the same bits; a pair that does not fit, and the default, take the paths below."""
     if penalty not in PENALTIES:
         raise ValueError('penalty must be one of %s' % sorted(PENALTIES))
+    if fused:
+        from .policy_rollout import fused_is_safe
+        out = fused_is_safe(model, policy, obses, int(steps), path_index, penalty)
+        if out is not None:
+            return out
     if path_index is not None:
         model.add_traj(obses, path_index)
     else:
@@ -70,11 +77,11 @@ def _is_safe_native(model, native, steps, penalty):
     return DevArray(safe.bool()), DevArray(punish)
 
 
-def safe_shield(model, policy, obses, path_index=None, steps=5, penalty='veh2veh4real'):
+def safe_shield(model, policy, obses, path_index=None, steps=5, penalty='veh2veh4real', fused=False):
     """-> (actions [B, 2] DevArray, shield_started [B] bool DevArray): the policy's action where the look-ahead is
     safe, the fallback action (0, -1) elsewhere (hier_decision.py:99-107)."""
     obs0 = model._obs(obses, model.state_dtype)                 # on the model's device, whatever the caller handed in
-    safe, _ = is_safe(model, policy, obs0, path_index, steps, penalty)
+    safe, _ = is_safe(model, policy, obs0, path_index, steps, penalty, fused)
     act = _unwrap(policy(DevArray(obs0))).to(device=obs0.device, dtype=torch.float32)
     fallback = torch.tensor(SAFE_ACTION, dtype=torch.float32, device=act.device).expand_as(act)
     started = ~_unwrap(safe)

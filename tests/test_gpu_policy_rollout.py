@@ -1,0 +1,338 @@
+"""GPU (-m gpu): the closed-loop rollout in one launch (env_build_amd/csrc/eb_policy_rollout.hip, include/envbuild_policy_rollout.h)
+through the C-ABI and the façade.  The yardstick everywhere is this file's own loop of single calls, eb_policy_run_batch ->
+eb_rollout_step through the same fp16 handle, and every comparison is bit for bit: (1) every output over networks, slot counts, batch
+sizes, horizons, penalties, action ranges, modes and scale, (2) row independence and repeatability, (3) eb_shield_is_safe, (4) the
+reference's G14 flags, (5) eb_policy_rollout_supported and the refusals, (6) the façade and the example."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from env_build_amd import _capi  # noqa: E402
+from env_build_amd.synthetic import assemble_obs, make_rollout_inputs  # noqa: E402
+from tests._helpers import DeviceModel, HostModel, golden, oracle_lib  # noqa: E402
+from tests._policy_cases import G14, make_layers  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+F32, F16 = 0, 1
+EVERYTHING = ('out5', 'actions', 'obs', 'punish', 'safe')
+
+
+def same(a, b):
+    return np.array_equal(a, b, equal_nan=True)
+
+
+def f16_mlp(dev, *args):
+    m = dev.make_mlp(*args)
+    dev.api.mlp_set_precision(m, F16)
+    return m
+
+
+def supported(dev, m):
+    ok = C.c_int32(-7)
+    dev.api.policy_rollout_supported(dev.h, m, C.byref(ok))
+    return ok.value, dev.api.lib.eb_last_error().decode()
+
+
+def entry(dev, m, obs, steps, ref_idx=None, path_id=0, ar=1.0, penalty=0, want=EVERYTHING):
+    """eb_policy_rollout -> dict; an output that is not in `want` is passed as NULL"""
+    ob, ri = dev._in(obs), dev._in(ref_idx, np.int32)
+    n, D = ob.shape
+    bufs = {'last': dev._out((n, D)),
+            'out5': dev._out((steps, 5, n)) if 'out5' in want else None,
+            'actions': dev._out((steps, n, 2)) if 'actions' in want else None,
+            'obs': dev._out((steps, n, D)) if 'obs' in want else None,
+            'punish': dev._out((n,)) if 'punish' in want else None,
+            'safe': dev._out((n,), np.uint8) if 'safe' in want else None}
+    p = dev._ptr
+    dev.api.policy_rollout(dev.h, m, n, int(steps), p(ob), p(ri), int(path_id), C.c_float(ar), int(penalty), p(bufs['last']),
+                           p(bufs['out5']), p(bufs['actions']), p(bufs['obs']), p(bufs['punish']), p(bufs['safe']), dev.stream)
+    return {k: dev._ret(v) for k, v in bufs.items() if v is not None}
+
+
+def loop(dev, m, obs0, steps, ref_idx=None, path_id=0, ar=1.0):
+    """the yardstick: `steps` x [eb_policy_run_batch -> eb_rollout_step], the per-step arrays kept (generic_loop of
+    tests/test_gpu_policy_f16.py, restated)"""
+    obs, out5s, acts, obss = obs0, [], [], []
+    for _ in range(steps):
+        a = dev.policy_run_batch(m, 2, obs, ar)
+        obs, out5, _ = dev.rollout_step(obs, a, ref_idx, path_id)
+        out5s.append(out5); acts.append(a); obss.append(obs)
+    return {'out5': np.stack(out5s), 'actions': np.stack(acts), 'obs': np.stack(obss)}
+
+
+def loop_view(ref, steps, penalty):
+    """what the entry must give for the first `steps` steps of a loop's record"""
+    row = 3 if penalty == 0 else 2
+    punish = ref['out5'][0, row].copy()
+    for t in range(1, steps):
+        punish = punish + ref['out5'][t, row]
+    return {'last': ref['obs'][steps - 1], 'out5': ref['out5'][:steps], 'actions': ref['actions'][:steps], 'obs': ref['obs'][:steps],
+            'punish': punish, 'safe': (~(punish > 0)).astype(np.uint8)}
+
+
+def assert_equal(got, want, what):
+    for k, g in got.items():
+        assert g.shape == want[k].shape and same(g, want[k]), '%s: %s differs in %d of %d values' % (
+            what, k, int((~((g == want[k]) | (np.isnan(g) & np.isnan(want[k])))).sum()), g.size)
+
+
+_SCENES = {}
+
+
+def scene(task, N, units, n_hidden, B=200):
+    """start states and a network, made once per case: make_rollout_inputs(task, B, N, 5, seed=21) + assemble_obs, make_layers(default_rng(N))"""
+    key = (task, N, units, n_hidden, B)
+    if key not in _SCENES:
+        host = HostModel(oracle_lib(), task, n_veh=N)
+        inp = make_rollout_inputs(task, B, N, 5, seed=21)
+        trk = host.tracking_error(inp['ego'][:, 3], inp['ego'][:, 4], inp['ego'][:, 5], inp['ego'][:, 0], 0, ref_idx=inp['ref_idx'])
+        obs0 = assemble_obs(inp['ego'], trk, inp['veh'])
+        rng = np.random.default_rng(N)
+        layers = make_layers(rng, host.D, n_hidden, units, 4)
+        scale = rng.uniform(0.02, 0.2, host.D).astype(np.float32)
+        _SCENES[key] = (obs0, inp['ref_idx'], (host.D, n_hidden, units, 4, 'elu', 'linear', layers), scale)
+    return _SCENES[key]
+
+
+# ---- 1: every output == the loop ----
+CASES = [('left', 8, 256, 2), ('right', 5, 64, 1), ('straight', 32, 256, 2), ('left', 32, 128, 3), ('left', 1, 100, 2)]
+PREMISE = {('left', 8), ('right', 5), ('straight', 32)}
+
+
+@pytest.mark.parametrize('case', CASES, ids=lambda c: '%s_N%d_%dx%d' % (c[0], c[1], c[3], c[2]))
+def test_every_output_equals_the_loop(case):
+    task, N, units, n_hidden = case
+    obs0, ref_idx, net, scale = scene(*case)
+    dev = DeviceModel(task, n_veh=N)
+    sel = DeviceModel(task, n_veh=N, mode='selecting')
+    m, m_plain = f16_mlp(dev, *net, scale), f16_mlp(dev, *net)
+    assert supported(dev, m)[0] == 1 and supported(sel, m_plain)[0] == 1
+    # training mode, scale on: every batch size (one tile, a tile edge, a partial tile), every horizon, both penalties, with every
+    # optional output and with none
+    for B in (1, 63, 64, 65, 200):
+        ref = loop(dev, m, obs0[:B], 20, ref_idx[:B])
+        if B == 200 and (task, N) in PREMISE:       # the loop's own outputs reach what the kernel has to get right
+            v2v, road, real = ref['out5'][:, 3], ref['out5'][:, 4], ref['out5'][:, 2]
+            hit = (v2v > 0).any(0)
+            assert hit.any() and (~hit).any() and (road > 0).any() and np.all(np.isfinite(ref['obs']))
+            assert len(set(loop_view(ref, 20, 0)['safe'])) == 2 and (real > 0).any()
+            print('%s N=%d: %d rows collide, %d hit a wall' % (task, N, int(hit.sum()), int((road > 0).any(0).sum())))
+        for steps, penalty in ((20, 0), (5, 1), (1, 0)):
+            want = loop_view(ref, steps, penalty)
+            what = '%s B=%d steps=%d penalty=%d' % (case, B, steps, penalty)
+            assert_equal(entry(dev, m, obs0[:B], steps, ref_idx[:B], penalty=penalty), want, what)
+            assert_equal(entry(dev, m, obs0[:B], steps, ref_idx[:B], penalty=penalty, want=()), want, what + ' (optional outputs NULL)')
+        assert_equal(entry(dev, m, obs0[:B], 5, ref_idx[:B], penalty=0, want=('punish', 'safe')), loop_view(ref, 5, 0), 'punish / safe only')
+    # the other heads, no scale, selecting mode
+    B = 200
+    for ar in (0.5, -1.0):
+        ref = loop(dev, m, obs0, 5, ref_idx, ar=ar)
+        assert_equal(entry(dev, m, obs0, 5, ref_idx, ar=ar, penalty=1), loop_view(ref, 5, 1), '%s action_range %g' % (case, ar))
+    ref = loop(dev, m_plain, obs0, 5, ref_idx)
+    assert_equal(entry(dev, m_plain, obs0, 5, ref_idx), loop_view(ref, 5, 0), '%s no scale' % (case,))
+    for path_id in (0, 2):
+        for mm in (m, m_plain):
+            ref = loop(sel, mm, obs0, 5, None, path_id)
+            assert_equal(entry(sel, mm, obs0, 5, None, path_id, penalty=1), loop_view(ref, 5, 1), '%s selecting path %d' % (case, path_id))
+    dev.api.mlp_destroy(m)
+    dev.api.mlp_destroy(m_plain)
+
+
+# ---- 2: rows, launches ----
+def test_rows_are_independent_and_launches_repeat():
+    case = ('left', 8, 256, 2)
+    obs0, ref_idx, net, scale = scene(*case)
+    dev = DeviceModel('left', n_veh=8)
+    m = f16_mlp(dev, *net, scale)
+    first = entry(dev, m, obs0, 5, ref_idx)
+    assert_equal(entry(dev, m, obs0, 5, ref_idx), first, 'second launch')
+    perm = np.random.default_rng(5).permutation(len(obs0))
+    rows = lambda d, idx: {k: (v[idx] if v.ndim == 1 or k == 'last' else v[:, idx] if k != 'out5' else v[:, :, idx]) for k, v in d.items()}
+    assert_equal(entry(dev, m, obs0[perm], 5, ref_idx[perm]), rows(first, perm), 'permuted batch')
+    sl = np.arange(100, 171)
+    assert_equal(entry(dev, m, obs0[sl], 5, ref_idx[sl]), rows(first, sl), 'slice')
+    # non-finite values in one row's ego and in one row's record: the loop's bits in those rows, every other row untouched
+    bad = obs0.copy()
+    bad[7, 3], bad[70, 4], bad[130, 9 + 4 * 2], bad[131, 9 + 4 * 3 + 3] = np.nan, np.inf, np.nan, -np.inf
+    got = entry(dev, m, bad, 5, ref_idx)
+    assert_equal(got, loop_view(loop(dev, m, bad, 5, ref_idx), 5, 0), 'non-finite rows')
+    keep = np.setdiff1d(np.arange(len(obs0)), [7, 70, 130, 131])
+    assert_equal(rows(got, keep), rows(first, keep), 'rows next to non-finite ones')
+    assert not np.all(np.isfinite(got['last'][[7, 70, 130, 131]]))
+    dev.api.mlp_destroy(m)
+
+
+# ---- 3: eb_shield_is_safe ----
+def test_agrees_with_the_shield_entry():
+    case = ('left', 8, 256, 2)
+    obs0, ref_idx, net, scale = scene(*case)
+    dev = DeviceModel('left', n_veh=8)
+    m = f16_mlp(dev, *net, scale)
+    for steps, penalty in ((5, 0), (20, 1)):
+        safe, punish, last, _ = dev.shield_is_safe(m, obs0, ref_idx=ref_idx, steps=steps, penalty=penalty)
+        got = entry(dev, m, obs0, steps, ref_idx, penalty=penalty, want=('punish', 'safe'))
+        assert same(got['safe'], safe) and same(got['punish'], punish) and same(got['last'], last), (steps, penalty)
+    dev.api.mlp_destroy(m)
+
+
+# ---- 4: G14 (three fixtures x 60 start states) ----
+@pytest.mark.parametrize('name', G14)
+def test_g14_safe_flags_with_the_fixture_weights_in_fp16(name):
+    g = golden(name)
+    task = name.split('_')[-1]
+    n = len([k for k in g.files if k.startswith('policy_w')])
+    layers = [(g['policy_w%d' % (2 * i)], g['policy_w%d' % (2 * i + 1)]) for i in range(n // 2)]
+    dev = DeviceModel(task, mode='selecting')
+    m = f16_mlp(dev, g['obs'].shape[1], n // 2 - 1, layers[0][0].shape[1], 4, 'elu', 'linear', layers, g['obs_scale'])
+    assert supported(dev, m)[0] == 1
+    got = entry(dev, m, g['obs'], 5, None, int(g['path_index']), penalty=0, want=('punish', 'safe'))
+    assert np.array_equal(got['safe'], g['safe']), 'safe flags differ from the reference at %s' % np.flatnonzero(got['safe'] != g['safe'])
+    assert np.array_equal(got['punish'] > 0, g['safe'] == 0)
+    dev.api.mlp_destroy(m)
+
+
+# ---- 5: what the kernel takes, and the refusals ----
+def refused(dev, m, obs, match, ref_idx=None, **kw):
+    """eb_policy_rollout is EB_EINVAL with `match` in the message and writes nothing"""
+    ob, ri = dev._in(obs), dev._in(ref_idx, np.int32)
+    n, D = ob.shape
+    steps = kw.get('steps', 5)
+    outs = [dev._out(s, d) for s, d in (((n, D), np.float32), ((max(steps, 1), 5, n), np.float32), ((max(steps, 1), n, 2), np.float32),
+                                        ((max(steps, 1), n, D), np.float32), ((n,), np.float32), ((n,), np.uint8))]
+    for o in outs:
+        o.fill_(77)
+    p = dev._ptr
+    with pytest.raises(ValueError, match=match):
+        dev.api.policy_rollout(dev.h, m, kw.get('n', n), steps, p(ob), p(ri), kw.get('path_id', 0), C.c_float(1.0), kw.get('penalty', 0),
+                               *[p(o) for o in outs], dev.stream)
+    for o in outs:
+        assert bool((dev._ret(o) == 77).all())
+
+
+def test_supported_says_what_the_kernel_takes_and_the_entry_refuses_the_rest():
+    rng = np.random.default_rng(0)
+    dev = DeviceModel('left', n_veh=8)
+    D = dev.D
+    obs = rng.standard_normal((70, D)).astype(np.float32)
+    ri = np.zeros(70, np.int32)
+
+    def net(d, units, out, precision=F16):
+        m = dev.make_mlp(d, 2, units, out, 'elu', 'linear', make_layers(rng, d, 2, units, out))
+        dev.api.mlp_set_precision(m, precision)
+        return m
+    good = net(D, 256, 4)
+    assert supported(dev, good)[0] == 1
+    cases = [(dev, net(D, 256, 4, F32), 'precision must be EB_MLP_PRECISION_F16'),
+             (dev, net(D, 300, 4), 'pads to 512'),
+             (dev, net(D + 4, 256, 4), 'obs_dim %d is not the model' % (D + 4)),
+             (dev, net(D, 256, 2), 'out_dim 2 is not 4')]
+    wide = DeviceModel('left', n_veh=64)
+    cases.append((wide, net(wide.D, 256, 4), 'n_veh 64 exceeds'))
+    fut = DeviceModel('left', n_veh=8, n_future=1)
+    cases.append((fut, net(fut.D, 256, 4), 'n_future 1 is not supported'))
+    for model, m, reason in cases:
+        ok, why = supported(model, m)
+        assert ok == 0 and reason in why, (reason, why)
+        x = rng.standard_normal((70, model.D)).astype(np.float32)
+        refused(model, m, x, reason, ref_idx=ri)
+        dev.api.mlp_destroy(m)
+    # the remaining bad arguments
+    with pytest.raises(ValueError, match='eb_policy_rollout_supported: null handle'):
+        dev.api.policy_rollout_supported(None, good, C.byref(C.c_int32()))
+    with pytest.raises(ValueError, match='eb_policy_rollout_supported: null policy'):
+        dev.api.policy_rollout_supported(dev.h, None, C.byref(C.c_int32()))
+    with pytest.raises(ValueError, match='null output pointer'):
+        dev.api.policy_rollout_supported(dev.h, good, None)
+    refused(dev, None, obs, 'eb_policy_rollout: null policy', ref_idx=ri)
+    refused(dev, good, obs, 'bad argument', ref_idx=ri, steps=0)
+    refused(dev, good, obs, 'bad argument', ref_idx=ri, n=-1)
+    refused(dev, good, obs, 'unknown penalty', ref_idx=ri, penalty=2)
+    refused(dev, good, obs, 'training mode needs ref_idx')
+    sel = DeviceModel('left', n_veh=8, mode='selecting')
+    refused(sel, good, obs, 'bad path_id', path_id=3)
+    refused(sel, good, obs, 'bad path_id', path_id=-1)
+    ob, out = dev._in(obs), dev._out(obs.shape)
+    for a, b in ((None, out), (ob, None), (ob, ob)):        # NULL obs_in, NULL obs_out, in place
+        with pytest.raises(ValueError, match='bad argument'):
+            dev.api.policy_rollout(dev.h, good, 70, 5, dev._ptr(a), dev._ptr(dev._in(ri, np.int32)), 0, C.c_float(1.0), 0, dev._ptr(b),
+                                   None, None, None, None, None, dev.stream)
+    with pytest.raises(ValueError, match='eb_policy_rollout: null handle'):
+        dev.api.policy_rollout(None, good, 70, 5, dev._ptr(ob), None, 0, C.c_float(1.0), 0, dev._ptr(out), None, None, None, None, None, dev.stream)
+    dev.api.policy_rollout(dev.h, good, 0, 5, None, None, 0, C.c_float(1.0), 0, None, None, None, None, None, None, dev.stream)   # n_env = 0: a no-op
+    # EB_ESTATE: a policy whose layers were never set (supported looks at the shapes only and says yes)
+    cfg = _capi.EbMlpConfig(_capi.EB_ABI_VERSION, D, 2, 256, 4, _capi.ACT_ID['elu'], _capi.ACT_ID['linear'], 0)
+    bare = C.c_void_p()
+    dev.api.check(dev.api.lib.eb_mlp_create(C.byref(cfg), C.byref(bare)))
+    dev.api.mlp_set_precision(bare, F16)
+    assert supported(dev, bare)[0] == 1
+    filled = dev._out(obs.shape)
+    filled.fill_(77)
+    with pytest.raises(_capi.EbError, match='eb_mlp_set_layer has not been called for every layer'):
+        dev.api.policy_rollout(dev.h, bare, 70, 5, dev._ptr(ob), dev._ptr(dev._in(ri, np.int32)), 0, C.c_float(1.0), 0, dev._ptr(filled),
+                               None, None, None, None, None, dev.stream)
+    assert bool((dev._ret(filled) == 77).all())
+    dev.api.mlp_destroy(bare)
+    assert dev.api.policy_rollout_fn('eb_policy_rollout_abi_version')() == _capi.EB_POLICY_ROLLOUT_ABI_VERSION == 1
+    dev.api.mlp_destroy(good)
+
+
+# ---- 6: façade ----
+def test_facade_fused_and_generic_equal_the_loop_and_the_example_runs(capsys):
+    import runpy
+    import torch
+    from types import SimpleNamespace
+    from env_build_amd.dynamics_and_models import EnvironmentModel
+    from env_build_amd.policy import LoadPolicy
+    from env_build_amd.policy_rollout import policy_rollout
+    from env_build_amd.shield import is_safe, safe_shield
+    task, N, B = 'left', 8, 200
+    model = EnvironmentModel(task, 0, mode='selecting', n_veh=N)
+    D = model.obs_dim
+    scale = [0.2] * 6 + [1., 1 / 30., 0.2] + [1 / 30., 1 / 30., 0.2, 1 / 180.] * N
+    args = dict(obs_dim=D, act_dim=2, num_hidden_layers=2, num_hidden_units=256, hidden_activation='elu', policy_out_activation='linear',
+                action_range=1.0, deterministic_policy=True, obs_preprocess_type='scale', obs_scale=scale)
+    pol16 = LoadPolicy(args=SimpleNamespace(policy_precision='fp16', **args))
+    pol32 = LoadPolicy(args=SimpleNamespace(**args))
+    obs0 = scene(task, N, 256, 2)[0]
+    dev = DeviceModel(task, n_veh=N, mode='selecting')
+    w = pol16.policy.policy.get_weights()
+    net = (D, 2, 256, 4, 'elu', 'linear', list(zip(w[0::2], w[1::2])), np.asarray(scale, np.float32))
+    for pol, m, fused in ((pol16, f16_mlp(dev, *net), True), (pol32, dev.make_mlp(*net), False)):
+        want = loop_view(loop(dev, m, obs0, 5, None, 1), 5, 1)
+        out = policy_rollout(model, pol, obs0, 5, path_index=1, penalty='real_punish_term', want=('out5', 'actions', 'obs'))
+        assert out['fused'] is fused
+        got = {'last': out['obs'], 'out5': out['out5_steps'], 'actions': out['actions_steps'], 'obs': out['obs_steps'],
+               'punish': out['punish']}
+        assert_equal({k: v.numpy() for k, v in got.items()}, want, 'facade, fused %s' % fused)
+        assert same(out['safe'].numpy(), want['safe'].astype(bool)) and same(model.obses.numpy(), want['last'])
+        short = policy_rollout(model, pol, obs0, 5, path_index=1, penalty='real_punish_term', want=())
+        assert sorted(short) == ['fused', 'obs', 'punish', 'safe'] and same(short['punish'].numpy(), want['punish'])
+        dev.api.mlp_destroy(m)
+    with pytest.raises(ValueError):
+        policy_rollout(model, pol16, obs0, 5, path_index=1, want=('rewards',))
+    # the shield through the fused kernel == the shield's two launches per step, with the fp16 policy
+    for steps, penalty in ((5, 'veh2veh4real'), (20, 'real_punish_term')):
+        s0, p0 = is_safe(model, pol16, obs0, path_index=1, steps=steps, penalty=penalty)
+        last0 = model.obses.numpy()
+        s1, p1 = is_safe(model, pol16, obs0, path_index=1, steps=steps, penalty=penalty, fused=True)
+        assert same(s1.numpy(), s0.numpy()) and same(p1.numpy(), p0.numpy()) and same(model.obses.numpy(), last0)
+    # fused=True with a policy the kernel does not take: the default's one C call, the default's bits
+    s0, p0 = is_safe(model, pol32, obs0, path_index=1, steps=5)
+    last0 = model.obses.numpy()
+    s1, p1 = is_safe(model, pol32, obs0, path_index=1, steps=5, fused=True)
+    assert same(s1.numpy(), s0.numpy()) and same(p1.numpy(), p0.numpy()) and same(model.obses.numpy(), last0)
+    a0, st0 = safe_shield(model, pol16, obs0, path_index=1)
+    a1, st1 = safe_shield(model, pol16, obs0, path_index=1, fused=True)
+    assert same(a1.numpy(), a0.numpy()) and same(st1.numpy(), st0.numpy())
+    torch.cuda.synchronize()
+    # the example: multi_ego's 20-step look-ahead for a batch, per-step penalties printed
+    capsys.readouterr()
+    mod = runpy.run_path(os.path.join(ROOT, 'examples', 'policy_lookahead.py'))
+    mod['main'](['--batch', '64', '--n-veh', '8'])
+    text = capsys.readouterr().out
+    assert 'fused: True' in text and text.count('step ') >= 20
