@@ -231,11 +231,28 @@ POLICY_FAMILIES = {
     'policy_rollout': ('envbuild_policy_rollout.h', 'closed-loop policy rollout', 'policy-rollout', 'eb_policy_rollout_abi_version',
                        EB_POLICY_ROLLOUT_ABI_VERSION, POLICY_ROLLOUT_PROTOTYPES),
 }
-_FAMILY_TABLES = (FAMILIES, MORE_FAMILIES, POLICY_FAMILIES)
+
+# include/envbuild_mlp_grad.h: the policy network's backward and the device-side weight set.  A table with a version of its own like the
+# others, kept in a FOURTH family table: the first three are the sets their tests enumerate.
+EB_MLP_GRAD_ABI_VERSION = 1
+MLP_GRAD_PROTOTYPES = {
+    'eb_mlp_grad_abi_version': (C.c_int, []),
+    'eb_mlp_grad_supported': (C.c_int, [_P, C.POINTER(_I)]),
+    'eb_mlp_param_count': (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    'eb_mlp_set_params_device': (C.c_int, [_P, _P, _P]),
+    'eb_mlp_backward_workspace_bytes': (C.c_int, [_P, _I, C.POINTER(C.c_size_t)]),
+    # (m, n, obs, g_out, head, action_range, workspace, workspace_bytes, out, g_obs, g_params, stream)
+    'eb_mlp_backward': (C.c_int, [_P, _I, _P, _P, _I, C.c_float, _P, C.c_size_t, _P, _P, _P, _P]),
+}
+TRAIN_FAMILIES = {
+    'mlp_grad': ('envbuild_mlp_grad.h', 'policy backward', 'policy-gradient', 'eb_mlp_grad_abi_version', EB_MLP_GRAD_ABI_VERSION,
+                 MLP_GRAD_PROTOTYPES),
+}
+_FAMILY_TABLES = (FAMILIES, MORE_FAMILIES, POLICY_FAMILIES, TRAIN_FAMILIES)
 
 
 def family_row(family):
-    """The six-tuple of one optional family: FAMILIES first, then MORE_FAMILIES, then POLICY_FAMILIES."""
+    """The six-tuple of one optional family: FAMILIES first, then MORE_FAMILIES, POLICY_FAMILIES and TRAIN_FAMILIES."""
     for table in _FAMILY_TABLES:
         if family in table:
             return table[family]
@@ -262,7 +279,7 @@ class CApi(object):
         self.backend = self.lib.eb_backend().decode()
 
     def family_fn(self, family, symbol):
-        """The raw ctypes function of one entry of an optional family (a key of FAMILIES, MORE_FAMILIES or POLICY_FAMILIES), the family bound on first use;
+        """The raw ctypes function of one entry of an optional family (a key of FAMILIES, MORE_FAMILIES, POLICY_FAMILIES or TRAIN_FAMILIES), the family bound on first use;
         EbError when this library does not export it or speaks another version of it."""
         header, label, abi, version_symbol, version, prototypes = family_row(family)
         fns = self.__dict__.setdefault('_%s_fns' % family, {})
@@ -301,6 +318,9 @@ class CApi(object):
 
     def policy_rollout_fn(self, symbol):
         return self.family_fn('policy_rollout', symbol)
+
+    def mlp_grad_fn(self, symbol):
+        return self.family_fn('mlp_grad', symbol)
 
     def check(self, rc):
         if rc != 0:

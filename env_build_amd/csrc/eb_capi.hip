@@ -31,6 +31,8 @@
 #include "eb_policy_f16.h"
 #include "../../include/envbuild_policy_rollout.h"
 #include "eb_policy_rollout.h"
+#include "../../include/envbuild_mlp_grad.h"
+#include "eb_policy_grad.h"
 #include "eb_grad.h"
 #include "eb_kernels.h"
 
@@ -1562,6 +1564,7 @@ struct eb_mlp_s {
     unsigned layers_set;
     int precision;                   // EB_MLP_PRECISION_* (include/envbuild_mlp_f16.h); both packings are kept, this picks the kernel
     uint16_t* d_w16[EB_MLP_MAX_HIDDEN + 1];   // the binary16 packing of every layer (eb_policy_f16.hip)
+    float* d_wt[EB_MLP_MAX_HIDDEN + 1];       // pack_weights of every layer's TRANSPOSED kernel: the backward's B operand (eb_policy_grad.hip)
 };
 
 static int mlp_layer_dims(const eb_mlp_s* m, int layer, int* k_real, int* cols_real, int* k_pad, int* col_tiles) {
@@ -1571,6 +1574,13 @@ static int mlp_layer_dims(const eb_mlp_s* m, int layer, int* k_real, int* cols_r
     *k_pad = layer == 0 ? m->k_pad0 : m->units;
     *col_tiles = out ? 1 : m->units / 32;
     return 0;
+}
+
+// the transposed packing of a layer (include/envbuild_mlp_grad.h): its inputs are this layer's columns (padded: the hidden width, or
+// out_dim rounded up to 8), its columns this layer's inputs in tiles of 32
+static void mlp_t_dims(const eb_mlp_s* m, int layer, int* kt_pad, int* colt_tiles) {
+    *kt_pad = layer == m->cfg.n_hidden ? (m->cfg.out_dim + 7) / 8 * 8 : m->units;
+    *colt_tiles = layer == 0 ? (m->cfg.obs_dim + 31) / 32 : m->units / 32;
 }
 
 // halves of a layer's binary16 packing: k padded to 16 (layer 0) or the padded width, times the tile columns
@@ -1689,6 +1699,9 @@ int eb_mlp_create(const eb_mlp_config* cfg, eb_mlp* out) {
         hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->d_w[L]), sizeof(float) * (size_t)kp * ct * 32);
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_b[L]), sizeof(float) * ct * 32);
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_w16[L]), sizeof(uint16_t) * mlp_f16_elems(m, L));
+        int ktp, ctt;
+        mlp_t_dims(m, L, &ktp, &ctt);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_wt[L]), sizeof(float) * (size_t)ktp * ctt * 32);
         if (e != hipSuccess) { eb_mlp_destroy(m); return fail_hip("hipMalloc(mlp layer)", e); }
     }
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->d_scale), sizeof(float) * cfg->obs_dim);
@@ -1703,6 +1716,7 @@ int eb_mlp_destroy(eb_mlp m) {
         if (m->d_w[L]) (void)hipFree(m->d_w[L]);
         if (m->d_b[L]) (void)hipFree(m->d_b[L]);
         if (m->d_w16[L]) (void)hipFree(m->d_w16[L]);
+        if (m->d_wt[L]) (void)hipFree(m->d_wt[L]);
     }
     if (m->d_scale) (void)hipFree(m->d_scale);
     delete m;
@@ -1721,7 +1735,15 @@ int eb_mlp_set_layer(eb_mlp m, int32_t layer, const float* kernel, const float* 
     std::vector<uint16_t> hp(mlp_f16_elems(m, layer), 0);
     if (layer == m->cfg.n_hidden) eb::pack_weights16_f16(kernel, kr, cr, m->units, hp.data());
     else eb::pack_weights_f16(kernel, kr, cr, layer == 0 ? eb::mlp_f16_k_pad0(m->cfg.obs_dim) : m->units, ct, hp.data());
+    // and the transposed one the backward reads (envbuild_mlp_grad.h): pack_weights of the [cols, inputs] matrix
+    int ktp, ctt;
+    mlp_t_dims(m, layer, &ktp, &ctt);
+    std::vector<float> tr((size_t)kr * cr), tp((size_t)ktp * ctt * 32);
+    for (int k = 0; k < kr; ++k)
+        for (int j = 0; j < cr; ++j) tr[(size_t)j * kr + k] = kernel[(size_t)k * cr + j];
+    eb::pack_weights(tr.data(), cr, kr, ktp, ctt, tp.data());
     EB_HIP(hipSetDevice(m->cfg.device));
+    EB_HIP(hipMemcpy(m->d_wt[layer], tp.data(), tp.size() * sizeof(float), hipMemcpyHostToDevice));
     EB_HIP(hipMemcpy(m->d_w[layer], wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
     EB_HIP(hipMemcpy(m->d_w16[layer], hp.data(), hp.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     EB_HIP(hipMemcpy(m->d_b[layer], bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -2222,6 +2244,119 @@ int eb_policy_rollout(eb_handle h, eb_mlp policy, int32_t n_env, int32_t steps, 
                                        : eb::MlpF16Layer{nullptr, nullptr, 0, 0};
     A.outl = eb::MlpF16Layer{m->d_w16[m->cfg.n_hidden], m->d_b[m->cfg.n_hidden], m->units, 0};
     EB_HIP(eb::launch_policy_rollout(h->cfg.task, A, (hipStream_t)stream));
+    return EB_OK;
+}
+
+}  // extern "C"
+
+// ---- include/envbuild_mlp_grad.h: the policy network's backward and the device-side weight set (eb_policy_grad.hip) ----
+// the first condition of eb_mlp_backward's list this handle does not meet, in g_err, as the code to return; EB_OK when there is none
+static int mlp_grad_fits(eb_mlp m) {
+    if (m->precision != EB_MLP_PRECISION_F32)
+        return fail(EB_EINVAL, "eb_mlp_backward: the handle's precision must be EB_MLP_PRECISION_F32 (the gradient is that of the fp32 forward; "
+                               "eb_mlp_set_precision)");
+    if (m->units > eb::MLP_GRAD_MAX_UNITS)
+        return fail_limit("eb_mlp_backward: hidden width %d pads to %d, beyond the kernels' limit of %d", (int)m->cfg.n_units, m->units,
+                          eb::MLP_GRAD_MAX_UNITS);
+    if (m->layers_set != (1u << (m->cfg.n_hidden + 1)) - 1u)
+        return fail(EB_ESTATE, "eb_mlp_backward: a layer was never set (eb_mlp_set_layer for every layer, or eb_mlp_set_params_device)");
+    return EB_OK;
+}
+
+static void mlp_grad_args(eb_mlp m, int32_t n, int head, float action_range, eb::MlpGradArgs* G) {
+    std::memset(G, 0, sizeof *G);
+    mlp_args(m, 0, nullptr, nullptr, eb::MLP_HEAD_LOGITS, action_range, &G->fwd, "");   // n = 0 for its checks: n and the pointers follow
+    G->fwd.n = n;
+    G->fwd.head = head;
+    for (int L = 0; L <= m->cfg.n_hidden; ++L) G->wt[L] = m->d_wt[L];
+    G->kt_out = (m->cfg.out_dim + 7) / 8 * 8;
+    G->n_units = m->cfg.n_units;
+}
+
+extern "C" {
+
+int eb_mlp_grad_abi_version(void) { return EB_MLP_GRAD_ABI_VERSION; }
+
+int eb_mlp_grad_supported(eb_mlp m, int32_t* ok) {
+    if (!m) return fail(EB_EINVAL, "eb_mlp_grad_supported: null handle");
+    if (!ok) return fail(EB_EINVAL, "eb_mlp_grad_supported: null output pointer");
+    *ok = mlp_grad_fits(m) == EB_OK ? 1 : 0;
+    return EB_OK;
+}
+
+int eb_mlp_param_count(eb_mlp m, int64_t* count) {
+    if (!m) return fail(EB_EINVAL, "eb_mlp_param_count: null handle");
+    if (!count) return fail(EB_EINVAL, "eb_mlp_param_count: null output pointer");
+    int64_t total = 0;
+    for (int L = 0; L <= m->cfg.n_hidden; ++L) {
+        int kr, cr, kp, ct;
+        mlp_layer_dims(m, L, &kr, &cr, &kp, &ct);
+        total += (int64_t)kr * cr + cr;
+    }
+    *count = total;
+    return EB_OK;
+}
+
+int eb_mlp_set_params_device(eb_mlp m, const float* params, void* stream) {
+    if (!m) return fail(EB_EINVAL, "eb_mlp_set_params_device: null handle");
+    if (!params) return fail(EB_EINVAL, "eb_mlp_set_params_device: null params");
+    eb::MlpPackArgs P;
+    std::memset(&P, 0, sizeof P);
+    P.params = params;
+    P.n_layers = m->cfg.n_hidden + 1;
+    P.units = m->units;
+    long long at = 0;
+    for (int L = 0; L <= m->cfg.n_hidden; ++L) {
+        eb::MlpPackLayer& Y = P.layer[L];
+        mlp_layer_dims(m, L, &Y.k_real, &Y.cols_real, &Y.k_pad, &Y.col_tiles);
+        mlp_t_dims(m, L, &Y.kt_pad, &Y.colt_tiles);
+        Y.k_pad16 = L == 0 ? eb::mlp_f16_k_pad0(m->cfg.obs_dim) : m->units;
+        Y.is_out = L == m->cfg.n_hidden;
+        Y.w = m->d_w[L]; Y.b = m->d_b[L]; Y.w16 = m->d_w16[L]; Y.wt = m->d_wt[L];
+        Y.w_off = at;
+        Y.b_off = at + (long long)Y.k_real * Y.cols_real;
+        at = Y.b_off + Y.cols_real;
+    }
+    EB_HIP(hipSetDevice(m->cfg.device));
+    EB_HIP(eb::launch_mlp_pack(P, (hipStream_t)stream));
+    m->layers_set = (1u << (m->cfg.n_hidden + 1)) - 1u;
+    return EB_OK;
+}
+
+int eb_mlp_backward_workspace_bytes(eb_mlp m, int32_t n, size_t* bytes) {
+    if (!m) return fail(EB_EINVAL, "eb_mlp_backward_workspace_bytes: null handle");
+    if (!bytes) return fail(EB_EINVAL, "eb_mlp_backward_workspace_bytes: null output pointer");
+    if (n < 0) return fail(EB_EINVAL, "eb_mlp_backward_workspace_bytes: n < 0");
+    const int rc = mlp_grad_fits(m);
+    if (rc) return rc;
+    eb::MlpGradArgs G;
+    mlp_grad_args(m, n, eb::MLP_HEAD_LOGITS, 0.0f, &G);
+    *bytes = n == 0 ? 0 : eb::mlp_grad_layout(G);
+    return EB_OK;
+}
+
+int eb_mlp_backward(eb_mlp m, int32_t n, const float* obs, const float* g_out, int32_t head, float action_range,
+                    void* workspace, size_t workspace_bytes, float* out, float* g_obs, float* g_params, void* stream) {
+    if (!m) return fail(EB_EINVAL, "eb_mlp_backward: null handle");
+    const int rc = mlp_grad_fits(m);
+    if (rc) return rc;
+    if (n < 0) return fail(EB_EINVAL, "eb_mlp_backward: n < 0");
+    if (head != eb::MLP_HEAD_LOGITS && head != eb::MLP_HEAD_ACTION) return fail(EB_EINVAL, "eb_mlp_backward: head must be 0 (logits) or 1 (actions)");
+    if (head == eb::MLP_HEAD_ACTION && (m->cfg.out_dim < 2 || (m->cfg.out_dim & 1)))
+        return fail(EB_EINVAL, "eb_mlp_backward: head 1 needs out_dim = 2 * act_dim");
+    if (n > 0 && (!obs || !g_out || !workspace)) return fail(EB_EINVAL, "eb_mlp_backward: null obs, g_out or workspace");
+    eb::MlpGradArgs G;
+    mlp_grad_args(m, n, head, action_range, &G);
+    const size_t need = eb::mlp_grad_layout(G);
+    if (n > 0 && workspace_bytes < need)
+        return fail_limit("eb_mlp_backward: the workspace holds %zu bytes, %d rows need %zu (eb_mlp_backward_workspace_bytes)", workspace_bytes,
+                          (int)n, need);
+    if (n == 0 && !g_params) return EB_OK;
+    G.fwd.obs = obs; G.fwd.out = out;
+    G.g_out = g_out; G.g_obs = g_obs; G.g_params = g_params;
+    G.ws = static_cast<float*>(workspace);
+    EB_HIP(hipSetDevice(m->cfg.device));
+    EB_HIP(eb::launch_mlp_backward(G, (hipStream_t)stream));
     return EB_OK;
 }
 

@@ -4,9 +4,10 @@ the 'scale' observation preprocessor (utils/preprocessor.py:116-123).
 
 Same names, constructor arguments and methods as the reference; the arithmetic is one fused HIP kernel per call
 (env_build_amd/csrc/eb_policy.hip: fp32 matrix cores, the whole network in one launch; with precision='fp16' the opt-in
-binary16 kernel of env_build_amd/csrc/eb_policy_f16.hip, include/envbuild_mlp_f16.h).  Training (optimisers,
-stochastic sampling, log-probabilities) is out of scope — the shield and the path selection only ever call
-`run_batch` / `obj_value_batch`.
+binary16 kernel of env_build_amd/csrc/eb_policy_f16.hip, include/envbuild_mlp_f16.h).  The shield and the path selection
+only ever call `run_batch` / `obj_value_batch`; the network's backward and a trainable `MLPNet` whose weights stay on the
+device are env_build_amd.policy_grad (`TrainableMLPNet`, include/envbuild_mlp_grad.h).  Optimisers, stochastic sampling
+and log-probabilities are out of scope.
 
 TensorFlow checkpoints cannot be read here (no TF, and the reference's checkpoints are git-ignored): weights are
 exchanged as the list `Model.get_weights()` returns — [kernel0, bias0, kernel1, bias1, ...], kernels [in, out] —

@@ -1,0 +1,257 @@
+"""A trainable `MLPNet`: the policy network's backward on the GPU (include/envbuild_mlp_grad.h, env_build_amd/csrc/eb_policy_grad.hip)
+behind torch autograd, with the weights living in ONE flat device tensor that any torch optimiser steps.
+
+`TrainableMLPNet` takes `MLPNet`'s constructor arguments.  `call(x)` / `mode(x, action_range)` return torch tensors on the autograd
+graph: forward is eb_mlp_forward / eb_policy_run_batch, backward one eb_mlp_backward — the gradient of exactly the function the
+inference handle evaluates.  The handle is brought up to date with eb_mlp_set_params_device whenever the flat tensor has been written
+since the last upload (its `_version`): no host copy, no synchronisation, one policy.  The same handle serves the shield,
+`policy_rollout` and `HierarchicalDecision`, at either precision; differentiating needs precision 'fp32'.
+
+`mlp_backward_reference` restates the header's contract in NumPy.  There is no CPU path for the network itself.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _capi
+from .dynamics_and_models import _dev
+from .policy import MLPNet, _act_det, _tanh_det
+
+__all__ = ['TrainableMLPNet', 'mlp_backward_reference']
+
+
+def _act(act, x, dtype):
+    if dtype == np.float32:
+        return _act_det(act, x)
+    with np.errstate(all='ignore'):
+        if act == 'relu':
+            return np.where(x > 0, x, 0.0)
+        if act == 'elu':
+            return np.where(x > 0, x, np.expm1(np.minimum(x, 0.0)))
+        if act == 'tanh':
+            return np.tanh(x)
+    return x
+
+
+def _derivative(act, y):
+    """the derivative of an activation from its OUTPUT y, one operation each"""
+    one = y.dtype.type(1)
+    if act == 'relu':
+        return np.where(y > 0, one, y.dtype.type(0))
+    if act == 'elu':
+        return np.where(y > 0, one, y + one)
+    if act == 'tanh':
+        return one - y * y
+    return np.ones_like(y)
+
+
+def _product(a, b, dtype, start=None):
+    """start + a @ b: in float64 as one matrix product; in float32 with float32 products added one by one in ascending order of the
+    reduction index (with `start`, the forward's chain: every step one fused multiply-add, through float64)."""
+    if dtype == np.float64:
+        out = a @ b
+        return out if start is None else out + start
+    acc = np.zeros((a.shape[0], b.shape[1]), np.float32) if start is None else np.broadcast_to(start, (a.shape[0], b.shape[1])).astype(np.float32)
+    with np.errstate(all='ignore'):
+        for k in range(a.shape[1]):
+            if start is None:
+                acc = acc + a[:, k:k + 1] * b[k:k + 1, :]
+            else:
+                acc = (a[:, k:k + 1].astype(np.float64) * b[k:k + 1, :].astype(np.float64) + acc.astype(np.float64)).astype(np.float32)
+    return acc
+
+
+def mlp_backward_reference(layers, obs, g, hidden_act, out_act, obs_scale=None, head=0, action_range=1.0, dtype=np.float32):
+    """The contract of include/envbuild_mlp_grad.h in NumPy: -> (out, g_obs, g_params), what eb_mlp_backward writes up to the order of
+    each backward sum.
+
+    layers: [(kernel [in, out], bias [out]), ...]; obs [n, in]; g: the cotangent of `out` — [n, out_dim] with head 0 (logits),
+    [n, out_dim // 2] with head 1 (actions = action_range * tanh(mean), or the mean itself with action_range <= 0 or None).
+    g_params is the list Model.get_weights() would have: [d kernel0, d bias0, d kernel1, ...].
+
+    dtype float32: the forward is the kernel's chain (bias, then one fused multiply-add per input in ascending k; the deterministic
+    float32 activations), every backward product is float32 and every backward sum float32 in ascending order of its index.
+    dtype float64: the same formulas in float64 with the library activations — the yardstick the float32 run and the kernel are measured
+    against."""
+    dtype = np.dtype(dtype).type
+    layers = [(np.asarray(w, np.float32).astype(dtype), np.asarray(b, np.float32).astype(dtype)) for w, b in layers]
+    x = np.asarray(obs, np.float32).astype(dtype)
+    g = np.asarray(g, np.float32).astype(dtype)
+    scale = None if obs_scale is None else np.asarray(obs_scale, np.float32).astype(dtype)
+    ar = -1.0 if action_range is None else float(action_range)
+    with np.errstate(all='ignore'):
+        if scale is not None:
+            x = x * scale
+        xs = [x]
+        for L, (w, b) in enumerate(layers):
+            pre = _product(xs[-1], w, dtype, start=b)
+            xs.append(_act(out_act if L == len(layers) - 1 else hidden_act, pre, dtype))
+        y = xs.pop()
+        if head == 0:
+            out, d = y, g * _derivative(out_act, y)
+        else:
+            act_dim = y.shape[1] // 2
+            mean = y[:, :act_dim]
+            d = np.zeros_like(y)
+            if ar > 0:
+                t = _tanh_det(mean) if dtype == np.float32 else np.tanh(mean)
+                out = dtype(ar) * t
+                d[:, :act_dim] = (g * dtype(ar)) * (dtype(1) - t * t) * _derivative(out_act, mean)
+            else:
+                out = mean.copy()
+                d[:, :act_dim] = g * _derivative(out_act, mean)
+        g_params = [None] * (2 * len(layers))
+        for L in range(len(layers) - 1, -1, -1):
+            g_params[2 * L] = _product(xs[L].T, d, dtype)
+            g_params[2 * L + 1] = _product(np.ones((1, len(d)), dtype), d, dtype)[0]
+            d = _product(d, layers[L][0].T, dtype)
+            d = d * _derivative(hidden_act, xs[L]) if L > 0 else (d if scale is None else d * scale)
+    return out.astype(dtype), d.astype(dtype), [a.astype(dtype) for a in g_params]
+
+
+class _Evaluate(torch.autograd.Function):
+    """call / mode of a TrainableMLPNet: forward through the inference entry, backward through eb_mlp_backward"""
+
+    @staticmethod
+    def forward(ctx, net, head, action_range, x, *params):
+        net._sync()
+        n = x.shape[0]
+        out = torch.empty((n, net.output_dim if head == 0 else net.output_dim // 2), dtype=torch.float32, device=net.device)
+        if head == 0:
+            net.api.mlp_forward(net._h, n, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), net._stream())
+        else:
+            net.api.policy_run_batch(net._h, n, C.c_void_p(x.data_ptr()), C.c_float(action_range), C.c_void_p(out.data_ptr()), net._stream())
+        ctx.net, ctx.head, ctx.action_range, ctx.version = net, head, action_range, net._flat._version
+        ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        net, (x,) = ctx.net, ctx.saved_tensors
+        if net._flat._version != ctx.version:
+            raise RuntimeError('the weights of %s were modified in place between this forward and its backward (version %d, expected %d): '
+                               'the gradient would be that of another network' % (net.name, net._flat._version, ctx.version))
+        net._sync()
+        n = x.shape[0]
+        g = g.to(dtype=torch.float32).contiguous()
+        need = C.c_size_t(0)
+        net.api.mlp_backward_workspace_bytes(net._h, n, C.byref(need))       # refuses an fp16 handle with the C reason
+        ws = torch.empty((max(need.value, 16),), dtype=torch.uint8, device=net.device)
+        g_obs = torch.empty_like(x) if ctx.needs_input_grad[3] else None
+        g_flat = torch.empty_like(net._flat) if any(ctx.needs_input_grad[4:]) else None
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        net.api.mlp_backward(net._h, n, p(x), p(g), ctx.head, C.c_float(ctx.action_range), p(ws), need.value, None, p(g_obs), p(g_flat),
+                             net._stream())
+        grads = [None] * len(net._params) if g_flat is None else [g_flat[a:b].view(shape) for a, b, shape in net._slices]
+        return (None, None, None, g_obs) + tuple(grads)
+
+
+class TrainableMLPNet(MLPNet):
+    """`MLPNet` with a backward.  The parameters are views of one flat device tensor in Keras order (kernel0 [in, out], bias0, ...), each a
+    leaf that requires grad: `parameters()` goes to any torch optimiser.  `call` / `mode` return torch tensors on the autograd graph."""
+
+    def __init__(self, input_dim, num_hidden_layers, num_hidden_units, hidden_activation, output_dim, **kwargs):
+        self._h = None
+        self._flat = None
+        MLPNet.__init__(self, input_dim, num_hidden_layers, num_hidden_units, hidden_activation, output_dim, **kwargs)
+
+    # the inference handle, current: whoever launches on it (the shield, policy_rollout, HierarchicalDecision) sees the latest weights
+    @property
+    def _handle(self):
+        if self._h is not None:
+            self._sync()
+        return self._h
+
+    @_handle.setter
+    def _handle(self, value):
+        self._h = value
+
+    def __del__(self):
+        try:
+            if self._h is not None:
+                self.api.lib.eb_mlp_destroy(self._h)
+        except Exception:
+            pass
+
+    def _shapes(self):
+        dims = [self.input_dim] + [self.num_hidden_units] * self.num_hidden_layers + [self.output_dim]
+        return [s for L in range(self.num_hidden_layers + 1) for s in ((dims[L], dims[L + 1]), (dims[L + 1],))]
+
+    def _create(self):
+        index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        cfg = _capi.EbMlpConfig(_capi.EB_ABI_VERSION, self.input_dim, self.num_hidden_layers, self.num_hidden_units, self.output_dim,
+                                _capi.ACT_ID[self.hidden_activation], _capi.ACT_ID[self.output_activation], index)
+        m = C.c_void_p()
+        self.api.check(self.api.lib.eb_mlp_create(C.byref(cfg), C.byref(m)))
+        self._h = m
+        if self.precision != 'fp32':
+            self.api.mlp_set_precision(m, _capi.MLP_PRECISION_ID[self.precision])
+        count = C.c_int64(0)
+        self.api.mlp_param_count(m, C.byref(count))
+        self._flat = torch.zeros((count.value,), dtype=torch.float32, device=self.device)
+        self._slices, at = [], 0
+        for shape in self._shapes():
+            size = int(np.prod(shape))
+            self._slices.append((at, at + size, shape))
+            at += size
+        assert at == count.value
+        with torch.no_grad():
+            self._params = [self._flat[a:b].view(shape) for a, b, shape in self._slices]
+        for t in self._params:
+            t.requires_grad_(True)
+        self._uploaded = None
+
+    def parameters(self):
+        return list(self._params)
+
+    def _sync(self):
+        """eb_mlp_set_params_device when the flat tensor has been written since the last upload; stream-ordered, nothing waits"""
+        if self._uploaded != self._flat._version:
+            self.api.mlp_set_params_device(self._h, C.c_void_p(self._flat.data_ptr()), self._stream())
+            self._uploaded = self._flat._version
+
+    # -- weights ------------------------------------------------------------------------------
+    def get_weights(self):
+        flat = self._flat.detach().cpu().numpy()
+        return [flat[a:b].reshape(shape).copy() for a, b, shape in self._slices]
+
+    def set_weights(self, weights):
+        weights = [np.ascontiguousarray(a, np.float32) for a in weights]
+        shapes = self._shapes()
+        if len(weights) != len(shapes):
+            raise ValueError('expected %d arrays (kernel, bias per Dense layer)' % len(shapes))
+        for a, shape in zip(weights, shapes):
+            if a.shape != tuple(shape):
+                raise ValueError('expected shapes %s, got %s' % (shapes, [w.shape for w in weights]))
+        if self._flat is None:
+            self._create()
+        with torch.no_grad():
+            self._flat.copy_(torch.from_numpy(np.concatenate([a.ravel() for a in weights])))
+
+    def set_obs_scale(self, obs_scale):
+        self._obs_scale = None if obs_scale is None else np.ascontiguousarray(obs_scale, np.float32)
+        if self._obs_scale is not None and self._obs_scale.shape != (self.input_dim,):
+            raise ValueError('obs_scale must have %d entries' % self.input_dim)
+        self.api.mlp_set_obs_scale(self._h, None if self._obs_scale is None else self._obs_scale.ctypes.data)
+
+    def _rebuild(self):        # MLPNet's host path: this class never rebuilds its handle
+        raise NotImplementedError
+
+    # -- forward ------------------------------------------------------------------------------
+    def _graph_in(self, x):
+        t = x if isinstance(x, torch.Tensor) else _dev(x, self.device)
+        t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        if t.dim() != 2 or t.shape[1] != self.input_dim:
+            raise ValueError('input must be [B, %d], got %s' % (self.input_dim, tuple(t.shape)))
+        return t
+
+    def call(self, x, **kwargs):
+        return _Evaluate.apply(self, 0, 0.0, self._graph_in(x), *self._params)
+
+    __call__ = call
+
+    def mode(self, x, action_range):
+        return _Evaluate.apply(self, 1, -1.0 if action_range is None else float(action_range), self._graph_in(x), *self._params)
