@@ -1,6 +1,7 @@
 """GPU (-m gpu): the policy network's backward (env_build_amd/csrc/eb_policy_grad.hip, include/envbuild_mlp_grad.h) through the C-ABI and
 the façade.  The backward sums take the kernels' own order, so the entry is held to (1) the bits of the float64 restatement where every
-partial sum is exact, (2) a bound from the restatement's own float32 / float64 runs on random networks, (3) the forward's bits in `out`
+partial sum is exact, (2) a bound from the restatement's own float32 / float64 runs on random networks, (2b) the bits of the float32
+restatement where every backward sum has one non-zero term at most, for every activation and head, (3) the forward's bits in `out`
 and untouched forwards, (4) repeatability and row independence, (5) the device-side weight set against the host one bit for bit,
 (6) clean refusals, (7) the façade and the example."""
 import ctypes as C
@@ -13,7 +14,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from env_build_amd import _capi  # noqa: E402
-from env_build_amd.policy_grad import mlp_backward_reference  # noqa: E402
+from env_build_amd import policy_grad  # noqa: E402
+from env_build_amd.policy_grad import _act, mlp_backward_reference  # noqa: E402
 from tests._helpers import DeviceModel, HostModel, oracle_lib  # noqa: E402
 from tests._policy_cases import make_layers  # noqa: E402
 
@@ -78,8 +80,18 @@ def flat_of(layers):
 
 # ---- 1: exact ----
 EXACT_SHAPES = [(9, 1, 64, 2), (29, 1, 64, 4), (41, 2, 256, 4), (137, 2, 256, 4), (45, 3, 128, 4), (33, 4, 100, 4), (8, 8, 32, 2),
-                (137, 2, 200, 1), (137, 1, 64, 4)]
+                (137, 2, 200, 1), (137, 1, 64, 4),
+                # out_dim 8 .. 32: the output layer's transposed product with 1 .. 4 steps, its second 16-column tile, head 1 with
+                # act_dim 9 / 12 / 16; obs_dim 192 / 193 / 300: the second trip of the x_0 staging loop, 7 / 10 column tiles of g_obs
+                (16, 2, 64, 8), (193, 2, 64, 9), (192, 1, 256, 16), (137, 1, 64, 17), (41, 2, 256, 18), (45, 3, 128, 24), (29, 1, 64, 32),
+                (300, 1, 128, 4)]
 EXACT_SIZES = (1, 63, 64, 65, 200, 1100)      # 1100 rows: three row splits of the parameter gradients (512, 512, 76)
+# 2048: four full splits; 2049: a fifth split of one row in a second y block of mlp_wgrad_kernel, three idle waves; 4160: nine splits
+# in three y blocks and 65 full row blocks.  One shape per width.
+MANY_ROWS_SIZES = (2048, 2049, 4160)
+MANY_ROWS_SHAPES = [(29, 1, 64, 32), (45, 3, 128, 24), (41, 2, 256, 4)]
+EXACT_CASES = [(s, EXACT_SIZES) for s in EXACT_SHAPES] + [(s, MANY_ROWS_SIZES) for s in MANY_ROWS_SHAPES]
+EXACT_IDS = ['%dx%dx%dx%d' % s for s in EXACT_SHAPES] + ['%dx%dx%dx%d-2048+' % s for s in MANY_ROWS_SHAPES]
 GRAN = 2.0 ** -4
 
 
@@ -122,8 +134,8 @@ def exact_premise(layers, obs, g, scale, relu, head):
     return ok
 
 
-@pytest.mark.parametrize('shape', EXACT_SHAPES, ids=lambda s: '%dx%dx%dx%d' % s)
-def test_exact_inputs_give_the_restatement_bits(shape):
+@pytest.mark.parametrize('shape,sizes', EXACT_CASES, ids=EXACT_IDS)
+def test_exact_inputs_give_the_restatement_bits(shape, sizes):
     obs_dim, n_hidden, n_units, out_dim = shape
     relu = EXACT_SHAPES.index(shape) % 2 == 0
     act = 'relu' if relu else 'linear'
@@ -135,15 +147,15 @@ def test_exact_inputs_give_the_restatement_bits(shape):
     for attempt in range(20):     # redraw until the premise holds
         layers = [(sparse_signs(rng, dims[L], dims[L + 1], 6 if L == 0 else 3), rng.integers(-4, 5, dims[L + 1]).astype(np.float32) / 4)
                   for L in range(n_hidden + 1)]
-        obs = {n: rng.integers(-8, 9, (n, obs_dim)).astype(np.float32) / 4 for n in EXACT_SIZES}
-        g = {(n, h): rng.integers(-4, 5, (n, out_dim if h == 0 else out_dim // 2)).astype(np.float32) / 4 for n in EXACT_SIZES for h in heads}
-        if all(exact_premise(layers, obs[n], g[(n, h)], sc, relu, h) for n in EXACT_SIZES for h in heads for sc in (None, scale)):
+        obs = {n: rng.integers(-8, 9, (n, obs_dim)).astype(np.float32) / 4 for n in sizes}
+        g = {(n, h): rng.integers(-4, 5, (n, out_dim if h == 0 else out_dim // 2)).astype(np.float32) / 4 for n in sizes for h in heads}
+        if all(exact_premise(layers, obs[n], g[(n, h)], sc, relu, h) for n in sizes for h in heads for sc in (None, scale)):
             break
     else:
         raise AssertionError('no draw satisfied the premise')
     for sc in (None, scale):
         m = dev.make_mlp(obs_dim, n_hidden, n_units, out_dim, act, 'linear', layers, sc)
-        for n in EXACT_SIZES:
+        for n in sizes:
             for h in heads:
                 want = mlp_backward_reference(layers, obs[n], g[(n, h)], act, 'linear', sc, h, -1.0, dtype=np.float64)
                 got = backward(dev, m, shape, obs[n], g[(n, h)], h, -1.0)
@@ -161,17 +173,28 @@ def test_exact_inputs_give_the_restatement_bits(shape):
 RANDOM_CONFIGS = [(41, 2, 256, 4, 'elu', 'linear'), (137, 2, 256, 4, 'elu', 'linear'), (29, 1, 64, 4, 'relu', 'linear'),
                   (45, 3, 128, 4, 'relu', 'linear'), (45, 3, 128, 1, 'tanh', 'linear'), (33, 4, 100, 6, 'elu', 'tanh'),
                   (8, 8, 32, 2, 'tanh', 'linear'), (137, 2, 200, 4, 'relu', 'linear'), (17, 1, 1, 1, 'elu', 'linear')]
+# the project's critic (a relu output); both tiles of the output layer with random weights; obs_dim 300 at width 256, elu output
+WIDE_CONFIGS = [(45, 3, 100, 1, 'tanh', 'relu'), (29, 1, 64, 32, 'elu', 'linear'), (137, 2, 128, 17, 'relu', 'tanh'),
+                (300, 1, 256, 18, 'elu', 'elu'), (41, 2, 128, 8, 'elu', 'linear')]
+# 2049 rows: five row splits, the last of one row in a second y block (the float32 restatement loops over the rows in Python: two small ones)
+MANY_ROWS_CONFIGS = [(29, 1, 64, 4, 'relu', 'linear'), (41, 2, 128, 8, 'elu', 'linear')]
+RANDOM_CASES = [(c, 200) for c in RANDOM_CONFIGS + WIDE_CONFIGS] + [(c, 2049) for c in MANY_ROWS_CONFIGS]
+RANDOM_IDS = ['%dx%dx%d_%s' % (c[0], c[1], c[2], c[4]) for c in RANDOM_CONFIGS] + \
+             ['%dx%dx%dx%d_%s_%s' % c for c in WIDE_CONFIGS] + ['%dx%dx%dx%d_%s_%s-2049' % c for c in MANY_ROWS_CONFIGS]
 
 
-def rows_off_the_relu_kink(layers, obs, scale):
-    """rows none of whose hidden pre-activations (float64) lies within 2^-16 (|b| + sum |x w|) of zero"""
+def rows_off_the_relu_kink(layers, obs, scale, hact='relu', oact='linear'):
+    """rows none of whose relu pre-activations (float64) lies within 2^-16 (|b| + sum |x w|) of zero: the hidden layers' when the hidden
+    activation is relu, the output layer's when the output activation is"""
     x = obs.astype(np.float64) * (1.0 if scale is None else scale.astype(np.float64))
     keep = np.ones(len(obs), bool)
-    for w, b in layers[:-1]:
+    for L, (w, b) in enumerate(layers):
+        act = oact if L == len(layers) - 1 else hact
         w64, b64 = w.astype(np.float64), b.astype(np.float64)
         pre, mass = x @ w64 + b64, np.abs(x) @ np.abs(w64) + np.abs(b64)
-        keep &= ~np.any(np.abs(pre) < 2.0 ** -16 * mass, 1)
-        x = np.maximum(pre, 0.0)
+        if act == 'relu':
+            keep &= ~np.any(np.abs(pre) < 2.0 ** -16 * mass, 1)
+        x = _act(act, pre, np.float64)
     return keep
 
 
@@ -190,22 +213,22 @@ def bound_check(got, r32, r64, what, failures):
     return worst
 
 
-@pytest.mark.parametrize('cfg', RANDOM_CONFIGS, ids=lambda c: '%dx%dx%d_%s' % (c[0], c[1], c[2], c[4]))
-def test_random_networks_within_the_bound(cfg):
+@pytest.mark.parametrize('cfg,n', RANDOM_CASES, ids=RANDOM_IDS)
+def test_random_networks_within_the_bound(cfg, n):
     """Measured worst error / tolerance per config (MI355X): see DESIGN §17."""
     obs_dim, n_hidden, n_units, out_dim, hact, oact = cfg
     dims = (obs_dim, n_hidden, n_units, out_dim)
     rng = np.random.default_rng(0)
     layers = make_layers(rng, obs_dim, n_hidden, n_units, out_dim)
-    obs = rng.standard_normal((200, obs_dim)).astype(np.float32)
+    obs = rng.standard_normal((n, obs_dim)).astype(np.float32)
     scale = rng.uniform(0.25, 1.0, obs_dim).astype(np.float32)
     dev = DeviceModel('left')
     worst, failures = 0.0, []
     cases = [(0, 1.0)] + ([(1, 1.0), (1, 0.5), (1, -1.0)] if out_dim % 2 == 0 else [])
     for sc in (None, scale):
         rows = obs
-        if hact == 'relu':        # rows on the kink leave the batch BEFORE the kernel runs: the parameter sums cover the same rows
-            keep = rows_off_the_relu_kink(layers, obs, sc)
+        if 'relu' in (hact, oact):        # rows on a kink leave the batch BEFORE the kernel runs: the parameter sums cover the same rows
+            keep = rows_off_the_relu_kink(layers, obs, sc, hact, oact)
             assert keep.sum() >= 0.9 * len(obs), 'more than 10 %% of the rows removed: %d' % int((~keep).sum())
             rows = obs[keep]
         m = dev.make_mlp(obs_dim, n_hidden, n_units, out_dim, hact, oact, layers, sc)
@@ -216,17 +239,163 @@ def test_random_networks_within_the_bound(cfg):
             got = backward(dev, m, dims, rows, g, head, ar)
             worst = max(worst, bound_check(got, r32, r64, 'head %d range %g scale %s' % (head, ar, sc is not None), failures))
         dev.api.mlp_destroy(m)
-    print('%s: worst error / tolerance %.3f' % (cfg, worst))
+    print('%s, %d rows: worst error / tolerance %.3f' % (cfg, n, worst))
     assert not failures, failures
 
 
 def test_the_relu_rule_removes_what_the_issue_counted():
-    """the rule itself, on the CPU side of this module: seed 0 removes 2 of 200 rows at 29x1x64 and 3 of 200 at 45x3x128"""
-    for dims, n_removed in (((29, 1, 64, 4), 2), ((45, 3, 128, 4), 3)):
+    """the rule itself, on the CPU side of this module: seed 0 removes 2 of 200 rows at 29x1x64 and 3 of 200 at 45x3x128; of the later
+    configs, none of 200 at the critic's relu output (45x3x100 -> 1, tanh hidden), 2 of 200 at 137x2x128 -> 17 and 6 of 2049 at 29x1x64
+    (with the scale on: 0, 5 and 7) — all far inside the 10 % cap"""
+    for dims, hact, oact, n, n_removed, n_removed_scaled in (((29, 1, 64, 4), 'relu', 'linear', 200, 2, 0),
+                                                             ((45, 3, 128, 4), 'relu', 'linear', 200, 3, 5),
+                                                             ((45, 3, 100, 1), 'tanh', 'relu', 200, 0, 0),
+                                                             ((137, 2, 128, 17), 'relu', 'tanh', 200, 2, 5),
+                                                             ((29, 1, 64, 4), 'relu', 'linear', 2049, 6, 7)):
         rng = np.random.default_rng(0)
         layers = make_layers(rng, *dims)
-        obs = rng.standard_normal((200, dims[0])).astype(np.float32)
-        assert int((~rows_off_the_relu_kink(layers, obs, None)).sum()) == n_removed, dims
+        obs = rng.standard_normal((n, dims[0])).astype(np.float32)
+        scale = rng.uniform(0.25, 1.0, dims[0]).astype(np.float32)
+        if oact == 'linear':
+            assert int((~rows_off_the_relu_kink(layers, obs, None)).sum()) == n_removed, dims       # the defaults: a relu / linear network
+        assert int((~rows_off_the_relu_kink(layers, obs, None, hact, oact)).sum()) == n_removed, dims
+        assert int((~rows_off_the_relu_kink(layers, obs, scale, hact, oact)).sum()) == n_removed_scaled, dims
+
+
+# ---- 2b: one term per sum ----
+ONE_TERM_SHAPES = [(41, 2, 64, 32), (137, 2, 256, 4), (45, 3, 100, 6)]
+ONE_TERM_ROWS = (0, 63, 64, 511, 512, 599)       # of 600: the ends of a row block and of a row split
+ONE_TERM_N = 600
+
+
+def permutation_layers(rng, dims):
+    """Kernels with at most one non-zero per row and per column, magnitudes in [0.5, 2], random signs, and random biases; every output
+    column is tied back to an input through one unit per layer.  -> (layers, paths): paths[c] = the input and the units column c hangs on."""
+    obs_dim, n_hidden, n_units, out_dim = dims
+    d = [obs_dim] + [n_units] * n_hidden + [out_dim]
+    assert out_dim <= obs_dim <= n_units
+    value = lambda size: (rng.uniform(0.5, 2.0, size) * rng.choice([-1.0, 1.0], size)).astype(np.float32)
+    layers, ends = [None] * (n_hidden + 1), np.arange(out_dim)           # ends: the column of layer L each path leaves through
+    paths = [[c] for c in range(out_dim)]
+    for L in range(n_hidden, -1, -1):
+        k, cols = d[L], d[L + 1]
+        m = min(k, cols)
+        others = np.setdiff1d(np.arange(cols), ends)
+        used_cols = np.concatenate([ends, rng.permutation(others)[:m - len(ends)]])
+        keep = np.concatenate([np.ones(len(ends), bool), rng.random(m - len(ends)) < 0.9])       # partial: a tenth of the rest stays empty
+        used_rows = rng.permutation(k)[:m]
+        w = np.zeros((k, cols), np.float32)
+        w[used_rows[keep], used_cols[keep]] = value(int(keep.sum()))
+        layers[L] = (w, rng.uniform(-1.0, 1.0, cols).astype(np.float32))
+        ends = used_rows[:len(ends)]
+        for c in range(out_dim):
+            paths[c].insert(0, int(ends[c]))
+    return layers, paths
+
+
+def path_is_live(layers, path, hact, oact, z, head_tanh):
+    """float64, elementwise in z (the scaled input the path starts from): no relu on the path within 0.05 of its kink or below it, no
+    tanh beyond 4 — the derivative along the path is then far from zero in float32 too"""
+    ok = np.ones(z.shape, bool)
+    for L, (w, b) in enumerate(layers):
+        act = oact if L == len(layers) - 1 else hact
+        pre = float(b[path[L + 1]]) + float(w[path[L], path[L + 1]]) * z
+        ok &= (pre > 0.05) if act == 'relu' else (np.abs(pre) < 4.0) if act == 'tanh' else (pre > -4.0)
+        z = _act(act, pre, np.float64)
+    return ok & (np.abs(z) < 4.0 if head_tanh else True)
+
+
+def one_term_case(rng, dims, hact, oact):
+    """-> (layers, paths) in which every output column's path is live over a good part of the inputs: the biases on a path are redrawn
+    until a twentieth of a standard normal sample passes path_is_live at scale 1 and at scale 1/4"""
+    layers, paths = permutation_layers(rng, dims)
+    z = rng.standard_normal(1024)
+    for path in paths:
+        for attempt in range(2000):
+            if all(path_is_live(layers, path, hact, oact, z * s, True).mean() >= 0.05 for s in (1.0, 0.25)):
+                break
+            for L in range(len(layers)):
+                layers[L][1][path[L + 1]] = rng.uniform(-1.0, 1.0)
+        else:
+            raise AssertionError('no biases keep the path of a column alive')
+    return layers, paths
+
+
+def one_term_inputs(rng, layers, paths, hact, oact, scale, gcols, head_tanh, turn):
+    """obs and g_out of ONE_TERM_N rows: min(gcols, n) live rows, ONE_TERM_ROWS first (rotated by `turn`), each with one non-zero cotangent in
+    a column of its own and with the input its path starts from drawn until path_is_live"""
+    n, obs_dim = ONE_TERM_N, layers[0][0].shape[0]
+    obs = rng.standard_normal((n, obs_dim)).astype(np.float32)
+    first = list(np.roll(ONE_TERM_ROWS, -turn))
+    rest = rng.permutation(np.setdiff1d(np.arange(n), ONE_TERM_ROWS))
+    rows = np.array(first + list(rest))[:gcols]
+    cols = rng.permutation(gcols)
+    g = np.zeros((n, gcols), np.float32)
+    for r, c in zip(rows, cols):
+        k = paths[c][0]
+        sc = 1.0 if scale is None else float(scale[k])
+        draws = rng.standard_normal(4096).astype(np.float32)
+        live = path_is_live(layers, paths[c], hact, oact, draws.astype(np.float64) * sc, head_tanh)
+        assert live.any(), (r, c)
+        obs[r, k] = draws[np.argmax(live)]
+        g[r, c] = rng.uniform(0.5, 2.0) * rng.choice([-1.0, 1.0])
+    return obs, g, rows
+
+
+def one_term_reference(layers, obs, g, hact, oact, scale, head, ar):
+    """mlp_backward_reference in float32, with the premise asserted on every backward product it forms (those without a start): no sum of
+    non-zero terms has more than one — so the float32 restatement is the kernel's bits whatever the kernel's order"""
+    inner, products = policy_grad._product, []
+
+    def watched(a, b, dtype, start=None):
+        if start is None:         # ((a != 0) @ (b != 0)).max(): a column of b with one non-zero gives one term at most, the others are counted
+            per_col = np.count_nonzero(b, 0)
+            many = (a != 0).astype(np.int64) @ (b[:, per_col > 1] != 0).astype(np.int64)
+            products.append(max(int(per_col.clip(0, 1).max()), int(many.max()) if many.size else 0))
+        return inner(a, b, dtype, start)
+
+    policy_grad._product = watched
+    try:
+        ref = mlp_backward_reference(layers, obs, g, hact, oact, scale, head, ar, dtype=np.float32)
+    finally:
+        policy_grad._product = inner
+    assert len(products) == 3 * len(layers) and max(products) <= 1, products
+    return ref
+
+
+@pytest.mark.parametrize('oact', ['linear', 'tanh', 'relu', 'elu'])
+@pytest.mark.parametrize('hact', ['elu', 'tanh', 'relu'])
+@pytest.mark.parametrize('shape', ONE_TERM_SHAPES, ids=lambda s: '%dx%dx%dx%d' % s)
+def test_one_term_per_sum_gives_the_restatement_bits(shape, hact, oact):
+    """Every activation's derivative, the tanh head, action_range and the output activation's derivative held to bits: each backward sum
+    has at most one non-zero term, adding zeros is exact, so the order of the kernels' sums does not matter."""
+    obs_dim, n_hidden, n_units, out_dim = shape
+    rng = np.random.default_rng(1000 * ONE_TERM_SHAPES.index(shape) + 10 * len(hact) + len(oact) + obs_dim)
+    dev = DeviceModel('left')
+    scale = rng.uniform(0.25, 1.0, obs_dim).astype(np.float32)
+    layers, paths = one_term_case(rng, shape, hact, oact)
+    handles = {False: dev.make_mlp(obs_dim, n_hidden, n_units, out_dim, hact, oact, layers, None),
+               True: dev.make_mlp(obs_dim, n_hidden, n_units, out_dim, hact, oact, layers, scale)}
+    turn = 0
+    # action_range 0.3: multiplying by 1.0 or 0.5 is exact, so only a range that is no power of two pins the grouping (g * range) * (1 - t * t)
+    for head, ar, scaled in [(h, r, sc) for sc in (False, True) for h, r in ((0, 1.0), (1, 1.0), (1, 0.5), (1, 0.3), (1, -1.0))]:
+        m, sc = handles[scaled], scale if scaled else None
+        gcols = out_dim if head == 0 else out_dim // 2
+        obs, g, rows = one_term_inputs(rng, layers, paths, hact, oact, sc, gcols, head == 1 and ar > 0, turn)
+        turn += gcols
+        want = one_term_reference(layers, obs, g, hact, oact, sc, head, ar)
+        got = backward(dev, m, shape, obs, g, head, ar)
+        what = '%s -> %s, head %d range %g scale %s' % (hact, oact, head, ar, scaled)
+        forward = dev.mlp_forward(m, out_dim, obs) if head == 0 else dev.policy_run_batch(m, gcols, obs, ar)
+        assert same(got[0], forward), 'out, ' + what
+        assert same(got[1], want[1]), 'g_obs, %s: %d of %d differ' % (what, int((got[1] != want[1]).sum()), want[1].size)
+        for k, (a, b) in enumerate(zip(got[2], want[2])):
+            assert same(a, b), 'g_params[%d], %s: %d of %d differ' % (k, what, int((a != b).sum()), b.size)
+        # the case says something: every live row reaches the observations and no other does, every kernel has a gradient
+        assert np.all(np.any(want[1][rows] != 0, 1)) and not np.any(np.delete(want[1], rows, 0)), what
+        assert all(np.any(want[2][2 * L] != 0) for L in range(n_hidden + 1)), what
+    for m in handles.values():
+        dev.api.mlp_destroy(m)
 
 
 # ---- shared by 3, 4: a random elu network ----
@@ -506,6 +675,41 @@ def test_trainable_mlpnet_gradients_optimiser_step_and_fp16():
     net.set_precision('fp32')
     net.call(obs).sum().backward()
     torch.cuda.synchronize()
+
+
+def test_trainable_mlpnet_critic_with_a_relu_output():
+    """the project's critic, MLPNet(D, 3, 100, 'tanh', 1, output_activation='relu'), as an ADP trainer differentiates it:
+    call(x).sum().backward() against the torch twin under the rule of (2), rows on the output's kink leaving first"""
+    import torch
+    from env_build_amd.policy_grad import TrainableMLPNet
+    from tests.test_policy_grad_host import torch_twin
+    dims = (41, 3, 100, 1)
+    rng = np.random.default_rng(12)
+    net = TrainableMLPNet(dims[0], dims[1], dims[2], 'tanh', dims[3], name='obj_v', output_activation='relu', seed=5)
+    layers = make_layers(rng, *dims, bias_scale=0.3)
+    net.set_weights([a for pair in layers for a in pair])
+    scale = rng.uniform(0.25, 1.0, dims[0]).astype(np.float32)
+    net.set_obs_scale(scale)
+    params = net.parameters()
+    obs = rng.standard_normal((200, dims[0])).astype(np.float32)
+    keep = rows_off_the_relu_kink(layers, obs, scale, 'tanh', 'relu')
+    assert keep.sum() >= 0.9 * len(obs)
+    obs = obs[keep]
+    x = torch.from_numpy(obs).cuda().requires_grad_(True)
+    out = net.call(x)
+    out.sum().backward()
+    got = (out.detach().cpu().numpy(), x.grad.cpu().numpy(), [p.grad.cpu().numpy() for p in params])
+    g = np.ones((len(obs), 1), np.float32)
+    want = torch_twin(layers, obs, g, 'tanh', 'relu', scale, 0, 1.0)
+    r32 = mlp_backward_reference(layers, obs, g, 'tanh', 'relu', scale, 0, 1.0, dtype=np.float32)
+    failures = []
+    worst = bound_check(got, r32, want, 'critic', failures)
+    print('critic façade: worst error / tolerance %.3f' % worst)
+    assert not failures, failures
+    # both sides of the kink are in the batch, and the rows below it give exact zeros
+    dead = want[0][:, 0] == 0
+    assert dead.sum() >= 10 and (~dead).sum() >= 10 and not np.any(got[1][dead]) and np.all(np.any(got[1][~dead] != 0, 1))
+    assert all(np.any(t != 0) for t in got[2])
 
 
 def test_example_trains_the_project_network_and_rolls_it_out_in_fp16():

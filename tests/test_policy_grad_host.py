@@ -121,12 +121,26 @@ def torch_twin(layers, obs, g, hidden_act, out_act, scale, head, action_range):
     return x.detach().numpy(), x0.grad.numpy(), [p.grad.numpy() for p in params]
 
 
-@pytest.mark.parametrize('cfg', CONFIGS, ids=lambda c: '%dx%dx%d_%s' % (c[0], c[1], c[2], c[4]))
+# what tests/test_gpu_policy_grad.py rests on the restatement for, beyond CONFIGS (that module is GPU-marked as a whole; restated here):
+# its exact shapes with out_dim 8 .. 32 and obs_dim 192 / 193 / 300 (relu / linear alternating), its wide random configs, and the
+# one-term shapes with every hidden activation times every output activation — relu and elu outputs, out_dim 17 / 18 / 32, obs_dim 300
+GRAD_CONFIGS = [(16, 2, 64, 8, 'linear', 'linear'), (193, 2, 64, 9, 'relu', 'linear'), (192, 1, 256, 16, 'linear', 'linear'),
+                (137, 1, 64, 17, 'relu', 'linear'), (41, 2, 256, 18, 'linear', 'linear'), (45, 3, 128, 24, 'relu', 'linear'),
+                (29, 1, 64, 32, 'linear', 'linear'), (300, 1, 128, 4, 'relu', 'linear'),
+                (45, 3, 100, 1, 'tanh', 'relu'), (29, 1, 64, 32, 'elu', 'linear'), (137, 2, 128, 17, 'relu', 'tanh'),
+                (300, 1, 256, 18, 'elu', 'elu'), (41, 2, 128, 8, 'elu', 'linear'), (41, 3, 100, 1, 'tanh', 'relu')]
+GRAD_CONFIGS += [shape + (hact, oact) for shape in ((41, 2, 64, 32), (137, 2, 256, 4), (45, 3, 100, 6))
+                 for hact in ('elu', 'tanh', 'relu') for oact in ('linear', 'tanh', 'relu', 'elu')]
+ALL_CONFIGS = CONFIGS + GRAD_CONFIGS
+ALL_IDS = ['%dx%dx%d_%s' % (c[0], c[1], c[2], c[4]) for c in CONFIGS] + ['%dx%dx%dx%d_%s_%s' % c for c in GRAD_CONFIGS]
+
+
+@pytest.mark.parametrize('cfg', ALL_CONFIGS, ids=ALL_IDS)
 def test_float64_restatement_is_torch_autograd(cfg):
     """both heads, action_range 1.0 / 0.5 / -1.0, scale on and off: every tensor within 1e-12 of its own maximum.  The derivative taken
     from the activation's output is what torch computes for all four activations away from the relu kink."""
     obs_dim, n_hidden, n_units, out_dim, hact, oact = cfg
-    assert len(CONFIGS) == 10 and CONFIGS[-1][:4] == (17, 1, 1, 1)
+    assert len(CONFIGS) == 10 and CONFIGS[-1][:4] == (17, 1, 1, 1) and len(set(ALL_IDS)) == len(ALL_IDS) == 60
     rng = np.random.default_rng(obs_dim * 11 + n_units)
     layers = make_layers(rng, obs_dim, n_hidden, n_units, out_dim)
     scale = rng.uniform(0.05, 1.0, obs_dim).astype(np.float32)
