@@ -92,9 +92,123 @@ def composite_case(make, task, B, M, NV, nf, tile=None):
     return got
 
 
-def auto_reset_case(make, task, B, M, NV=None, nf=0, tile=None, close_p=0.02, seed=5, v_light_none=False, strict=True):
+def g20_parked_scene(task, widened=False):
+    """Families A-D of fixture G20 (native or 16-slot file), parked: the ego's v_x = v_y = r = 0 and every candidate's v = 0, so a step
+    leaves every position where it is and the step's own observation pass decides on the fixture's inputs -> (scene, the fixture's
+    vehicle block with its v column cleared, labels, slot count or None).  That the reference's block of the parked scene IS this
+    block is asserted by the generator on every scene (oracle/gen_golden_env_edges.py: emit)."""
+    from tests._golden_checks import g20_arrays
+    g = g20_arrays(('g20w_env_edges_%s_N16' if widened else 'g20_env_edges_%s') % task)
+    rows = np.array([str(l)[0] in 'ABCD' for l in g['label']])
+    ego, cand = g['ego'][rows].copy(), g['cand'][rows].copy()
+    ego[:, :3] = 0
+    cand[:, :, 2] = 0
+    block = g['obs'][rows][:, 9:].copy()
+    block[:, 2::4] = 0
+    scene = dict(ego=ego, cand=cand, cmode=g['cand_mode'][rows], lw=g['cand_lw'][rows], v_light=g['v_light'][rows], virtual=g['virtual'][rows],
+                 ref=g['ref_index'][rows])
+    return scene, block, g['label'][rows], (len(g['slot_modes']) if widened else None)
+
+
+def _g20_parked_asserts(ego_in, cand_in, ego_out, cand_out, obs_out, block, labels, rows, what):
+    """the condition first, with no allowance: the ego's (x, y) and the candidates' (x, y, v) came through the step with their input
+    bits; then the x, y and v columns of the step's vehicle block against the fixture's, bit for bit (the headings drift by an ulp of
+    the degree-radian round trip on some rows: they are compared with the oracle's step only)"""
+    from tests._golden_checks import rows_bit_equal
+    B = len(ego_in)
+    rows_bit_equal(np.asarray(ego_out).reshape(B, 6)[rows][:, 3:5], ego_in[rows][:, 3:5], labels[rows], what + ': ego (x, y) through the step')
+    rows_bit_equal(np.asarray(cand_out).reshape(cand_in.shape)[rows][:, :, :3], cand_in[rows][:, :, :3], labels[rows], what + ': candidates (x, y, v) through the step')
+    got = np.asarray(obs_out)[rows][:, 9:].reshape(int(rows.sum()), -1, 4)[:, :, :3]
+    rows_bit_equal(got, block[rows].reshape(int(rows.sum()), -1, 4)[:, :, :3], labels[rows], what + ': vehicle block (x, y, v) against G20')
+
+
+def g20_parked_case(make, task, tile=None, widened=False):
+    """eb_env_step on the parked G20 scenes: (1) its eight outputs equal the six single calls bit for bit, as composite_case checks on
+    drawn scenes; (2) the x, y, v columns of its vehicle block equal the fixture's.  -> the eight outputs"""
+    from tests._golden_checks import rows_bit_equal
+    sc, block, labels, NV = g20_parked_scene(task, widened)
+    ego, cand, cmode, lw, v_light, virtual, ref = (sc[k] for k in ('ego', 'cand', 'cmode', 'lw', 'v_light', 'virtual', 'ref'))
+    B, M = cand.shape[:2]
+    native = VEHICLE_MODE_LIST[task]
+    modes = [native[i % len(native)] for i in range(M)]          # the traffic model's per-column modes: with v = 0 no mode moves a record
+    raw = np.random.default_rng(20).uniform(-1.2, 1.2, (B, 2)).astype(np.float32)
+    m, tr = make(task, mode='training', **({} if NV is None else dict(n_veh=NV))), make(task, n_veh=M, modes=modes)
+    if tile is not None:
+        m.set_tile(tile)
+    obs0 = m.get_obs(ego, cand, cmode, v_light, ref_idx=ref, virtual=virtual)
+    act = m.action_transform(raw)
+    o5, d16 = m.compute_rewards(obs0, act)
+    ego1, par1 = m.env_ego_step(ego, act)
+    cand1 = tr.veh_predict(cand.reshape(B, -1)).reshape(B, M, 4)
+    obs1 = m.get_obs(ego1, cand1, cmode, v_light, ref_idx=ref, virtual=virtual)
+    done1 = m.judge_done(ego1, par1, obs1, cand1, cmode, lw, v_light)
+    got = m.env_step(tr, obs0, raw, ego, cand, cmode, ref_idx=ref, cand_lw=lw, v_light=v_light, virtual=virtual)
+    every = np.ones(B, bool)
+    what = 'G20 parked, %s%s, tile %s' % (task, ' N16' if widened else '', tile)
+    _g20_parked_asserts(ego, cand, got[3], got[5], got[6], block, labels, every, what)
+    names = ['scaled', 'out5', 'dict16', 'ego', 'params', 'cand', 'obs', 'done']
+    for k, (g, w) in enumerate(zip(got, [act, o5, d16, ego1, par1, cand1, obs1, done1])):
+        g, w = np.asarray(g).reshape(np.asarray(w).shape), np.asarray(w)
+        if k in (1, 2):
+            assert np.array_equal(g, w), names[k]
+        else:
+            rows_bit_equal(g, w, labels, what + ': %s against the single calls' % names[k])
+    return got
+
+
+def g20_parked_auto_reset_case(make, task, tile=None, widened=False):
+    """eb_env_step(auto_reset) on the parked G20 scenes against its stepwise composition (auto_reset_case, the scene swapped in); the
+    rows the step did not finish keep the step's observation: their block against the fixture's"""
+    sc, block, labels, NV = g20_parked_scene(task, widened)
+    B, M = sc['cand'].shape[:2]
+    got = auto_reset_case(make, task, B, M, NV=NV, tile=tile, strict=False, scene=sc)
+    live = np.asarray(got[7]) == 0
+    assert live.sum() > B // 2
+    _g20_parked_asserts(sc['ego'], sc['cand'], got[3], got[5], got[6], block, labels, live, 'G20 parked + auto reset, %s' % task)
+    return got
+
+
+def g20_parked_flow_scene(task, widened=False, K=2):
+    """The parked G20 scenes the flow source's layout admits: its 12 K slots carry one route each (K per route, fixed), so a scene
+    fits when no mode has more than K candidates; they go to their route's slots in insertion order, which keeps every mode's own
+    order — the order the filter and the sort see — and with it the fixture's block."""
+    sc, block, labels, NV = g20_parked_scene(task, widened)
+    B, M = sc['cand'].shape[:2]
+    assert M == 12 * K
+    keep, cand, active = [], np.zeros((B, M, 4), np.float32), np.zeros((B, M), np.uint8)
+    for i in range(B):
+        live = np.flatnonzero(sc['cmode'][i] != _capi.VMODE_EMPTY)
+        per = {r: [c for c in live if sc['cmode'][i, c] == r] for r in range(12)}
+        if max(len(v) for v in per.values()) > K:
+            continue
+        keep.append(i)
+        for r, cs in per.items():
+            for j, c in enumerate(cs):
+                cand[i, r * K + j], active[i, r * K + j] = sc['cand'][i, c], 1
+    keep = np.array(keep)
+    scene = dict(ego=sc['ego'][keep], ref=sc['ref'][keep], active=active[keep], cand=cand[keep], v_light=sc['v_light'][keep], virtual=sc['virtual'][keep])
+    return scene, block[keep], labels[keep], NV
+
+
+def g20_parked_flow_case(make, task, tile=None, widened=False):
+    """eb_env_step(flow) at per_route = 2 (24 slots) on the parked G20 scenes that fit its layout, against eb_env_step +
+    eb_traffic_flow_step (flow_rule_case, the scene swapped in, one step); the step's block against the fixture's"""
+    scene, block, labels, NV = g20_parked_flow_scene(task, widened)
+    B = len(scene['ego'])
+    assert B >= 60 and {str(l)[0] for l in labels} >= set('ACD')
+    trace = flow_rule_case(make, task, B=B, K=2, steps=1, tile=tile, strict=False, scene=scene, NV=NV)
+    g = trace[0]
+    from tests._golden_checks import rows_bit_equal
+    rows_bit_equal(np.asarray(g[3])[:, 3:5], scene['ego'][:, 3:5], labels, 'G20 parked + flow rule: ego (x, y) through the step')
+    got = np.asarray(g[6])[:, 9:].reshape(B, -1, 4)[:, :, :3]
+    rows_bit_equal(got, block.reshape(B, -1, 4)[:, :, :3], labels, 'G20 parked + flow rule, %s: vehicle block (x, y, v) against G20' % task)
+    return trace
+
+
+def auto_reset_case(make, task, B, M, NV=None, nf=0, tile=None, close_p=0.02, seed=5, v_light_none=False, strict=True, scene=None):
     """eb_env_step(auto_reset) == eb_env_step, then the terminal rows -> final_obs, then eb_env_reset_pool(mask = done != 0) in place —
-    every output and every piece of state, bit for bit; done_code keeps the step's codes."""
+    every output and every piece of state, bit for bit; done_code keeps the step's codes.
+    scene: dict(ego, cand, cmode, virtual, v_light, ref) of B envs and M candidates in place of the drawn one (g20_parked_scene)."""
     from env_build_amd.endtoend import _lane_entry
     native = VEHICLE_MODE_LIST[task]
     modes = [native[i % len(native)] for i in range(M)]
@@ -113,6 +227,9 @@ def auto_reset_case(make, task, B, M, NV=None, nf=0, tile=None, close_p=0.02, se
     cand[:, :, 0] = np.where(gone, rng.choice([-70.0, 66.0, 64.9], (B, M)), cand[:, :, 0]).astype(np.float32)
     virtual = (rng.random(B) < 0.4).astype(np.uint8)
     v_light = None if v_light_none else rng.integers(0, 3, B).astype(np.uint8)
+    if scene is not None:
+        ego, cand, cmode, virtual, v_light, ref = (scene[k] for k in ('ego', 'cand', 'cmode', 'virtual', 'v_light', 'ref'))
+        assert ego.shape == (B, 6) and cand.shape == (B, M, 4)
     rule = dict(entry=entry, limit=65.0, span=5.0, v_max=8.0, seed=0x1234567, counter=9)
     pool = dict(entry=entry, span=60.0, v_max=8.0, seed=4242, counter=17, edge_span=5.0)
     kw = dict(mode='training', n_future=nf)
@@ -177,10 +294,12 @@ def auto_reset_bad_args_case(make, task='left', B=40, M=8):
                    auto_reset=dict(seed=1, counter=1, training=1, pool=pool))
 
 
-def flow_rule_case(make, task, B=300, K=5, steps=40, tile=None, light_cycle=1, seed=3, strict=True, hostile=False):
+def flow_rule_case(make, task, B=300, K=5, steps=40, tile=None, light_cycle=1, seed=3, strict=True, hostile=False, scene=None, NV=None):
     """eb_env_step(flow) == eb_env_step, then eb_traffic_flow_step on what it left — every output and every piece of the flow
     source's state, bit for bit, over a closed loop that starts from an empty junction (emissions, exits, accelerations, the
-    light programme all occur on the way); -> the trace of the fused path (for cross-library comparison)."""
+    light programme all occur on the way); -> the trace of the fused path (for cross-library comparison).
+    scene: dict(ego, ref, active, cand, v_light, virtual) of B envs and 12 K slots in place of the drawn junction (g20_parked_flow_scene);
+    NV: the ego model's slot count (None = native)."""
     from env_build_amd.traffic import ACCEL, EXIT_RANGE, FLOWS, LANE_START, ROUTES, VTYPES, approach_lane
     M = 12 * K
     slot_modes = [r for r in ROUTES for _ in range(K)]
@@ -191,7 +310,7 @@ def flow_rule_case(make, task, B=300, K=5, steps=40, tile=None, light_cycle=1, s
     rng = np.random.default_rng(seed)
     inp = make_rollout_inputs(task, B, 8, 1, seed=seed)
     ego, ref = inp['ego'].copy(), inp['ref_idx']
-    m, tr = make(task, mode='training'), make(task, n_veh=M, modes=slot_modes)
+    m, tr = make(task, mode='training', **({} if NV is None else dict(n_veh=NV))), make(task, n_veh=M, modes=slot_modes)
     if tile is not None:
         m.set_tile(tile)
     # a junction in mid-traffic: some slots occupied along their lanes (a few of them far out and heading away: they leave)
@@ -220,11 +339,16 @@ def flow_rule_case(make, task, B=300, K=5, steps=40, tile=None, light_cycle=1, s
         cand = np.stack([x, y, v, phi], 2).astype(np.float32)
         cand[::7, 3, 0] = np.nan; cand[3::11, 5, 3] = np.inf; cand[5::13, 2, 2] = np.inf; cand[1::17, 4, 1] = -np.inf
         cand[2::5, 1] = (70.0, 0.0, 3.0, 90.0); cand[4::5, 1] = (0.0, -80.0, 3.0, 180.0)  # exactly at a right angle, on the axes
+    if scene is not None:
+        ego, ref, active, cand = scene['ego'], scene['ref'], scene['active'], scene['cand']
+        assert ego.shape == (B, 6) and cand.shape == (B, M, 4)
     mode = np.where(active != 0, np.array([_capi.VMODE_ID[x] for x in slot_modes], np.uint8)[None, :], _capi.VMODE_EMPTY).astype(np.uint8)
     timer = (rng.random((B, 12)) * period).astype(np.float32)
     emitted, sim_step = np.zeros((B, 12), np.int32), rng.integers(0, 600, B).astype(np.int32)
     light = rng.integers(0, 4, B).astype(np.uint8)
     virtual = (rng.random(B) < 0.3).astype(np.uint8)
+    if scene is not None:
+        light, virtual = scene['v_light'], scene['virtual']
     obs = m.get_obs(ego, cand, mode, light, ref_idx=ref, virtual=virtual)
     const = dict(per_route=K, lane=lane, period=period, v_max=vmax, dt=0.1, exit_range=EXIT_RANGE, accel=ACCEL, lane_len=LANE_START - 25.0,
                  light_cycle=light_cycle, seed=99)

@@ -117,6 +117,78 @@ def check_g12_exit_frames(make, tag=''):
     close(back[:, 3:5], ego[:, 3:5], RTOL, ATOL['g12'], tag + 'G12 exit frame: there and back')
 
 
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def rows_bit_equal(got, want, labels, what):
+    """bit for bit, row by row; a mismatch names the scenes (G20's `label`)"""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, '%s: shape %s vs %s' % (what, got.shape, want.shape)
+    a, b = (_bits(got), _bits(want)) if got.dtype.kind == 'f' else (got, want)
+    bad = np.flatnonzero((a != b).reshape(len(a), -1).any(axis=1))
+    assert not len(bad), '%s: %d of %d scenes differ: %s' % (what, len(bad), len(a), ', '.join('%s [row %d]' % (labels[i], i) for i in bad[:6]))
+
+
+def g20_arrays(name):
+    z = golden(name)
+    return {k: z[k] for k in z.files}          # decompressed once
+
+
+def _g20_slots(g, task):
+    from tests._env_edges import MODES12
+    return [MODES12[i] for i in g['slot_modes']] if 'slot_modes' in g else None
+
+
+def _check_g20(g, make, task, tag, form, what):
+    """G6's rules on a G20 file: ego columns and the vehicle block bit-exact, tracking columns within RTOL / ATOL['g4'], the done
+    code bit-exact, done == 1 exactly where the reference's collision check hit.  form: 'single' = eb_get_obs as it is, 'exit0' = its
+    exit-frame form with exit D, whose frame is the identity (rotation by 0: x * 1 + y * 0, heading - 0; the scenes' headings lie inside
+    (-180, 180)), so the expectation is the same block; 'masked' = two calls with complementary row masks into one buffer;
+    'separate_staged' / 'separate_unstaged' = the ego / the candidates handed over 4 bytes off a 16-byte boundary, which the HIP library's
+    one-launch form of eb_get_obs does not take: the call runs get_obs_kernel (veh_in_range / veh_cmp), with the candidates staged in LDS
+    (misaligned ego) or read per thread (misaligned candidates)."""
+    slots, labels = _g20_slots(g, task), g['label']
+    m = make(task, mode='training') if slots is None else make(task, n_veh=len(slots), mode='training', modes=slots)
+    n = len(g['ego'])
+    args = (g['ego'], g['cand'], g['cand_mode'], g['v_light'])
+    kw = dict(ref_idx=g['ref_index'], virtual=g['virtual'])
+    if form == 'single':
+        obs = m.get_obs(*args, **kw)
+    elif form == 'exit0':
+        obs = m.get_obs(*args, exit_id=np.zeros(n, np.uint8), **kw)
+    elif form in ('separate_staged', 'separate_unstaged'):
+        obs = m.get_obs(*args, shift=('ego',) if form == 'separate_staged' else ('cand',), **kw)
+    else:
+        assert form == 'masked'
+        mask = (np.arange(n) % 3 == 1)
+        init = np.full((n, m.D), np.float32(-7.25))
+        half = m.get_obs(*args, row_mask=mask.astype(np.uint8), obs_init=init, **kw)
+        assert (half[~mask] == np.float32(-7.25)).all()
+        obs = m.get_obs(*args, row_mask=(~mask).astype(np.uint8), obs_init=half, **kw)
+    assert obs.shape == g['obs'].shape
+    rows_bit_equal(obs[:, :6], g['obs'][:, :6], labels, '%s%s ego columns (%s, %s)' % (tag, what, task, form))
+    close(obs[:, 6:9], g['obs'][:, 6:9], RTOL, ATOL['g4'], '%s%s tracking columns (%s)' % (tag, what, task))
+    rows_bit_equal(obs[:, 9:], g['obs'][:, 9:], labels, '%s%s vehicle block (%s, %s)' % (tag, what, task, form))
+    if form == 'single':
+        seen = g['obs'].copy()
+        seen[:, 6] = g['done_delta_y']                           # the obs[6] _judge_done saw (set by the generator in E and H)
+        done = m.judge_done(g['ego'], g['params'], seen, g['cand'], g['cand_mode'], g['cand_lw'], g['v_light'])
+        rows_bit_equal(done, g['done_code'], labels, '%s%s done code (%s)' % (tag, what, task))
+        rows_bit_equal(done == 1, g['collision'] != 0, labels, '%s%s collision flag (%s)' % (tag, what, task))
+
+
+def check_g20_env_edges(make, task, tag='', form='single'):
+    """G20 (oracle/gen_golden_env_edges.py): filter bounds, sort ties, the stop-line car, counts, done rules, walls, stability, the
+    priority chain and the collision circles on hand-made edge scenes, the reference's recorded outputs as the expectation."""
+    _check_g20(g20_arrays('g20_env_edges_%s' % task), make, task, tag, form, 'G20')
+
+
+def check_g20w_env_edges(make, task, tag='', form='single'):
+    """G20's families A-D at the project's 16-slot list (more than two slots of a mode), the reference's block regrouped by rank."""
+    _check_g20(g20_arrays('g20w_env_edges_%s_N16' % task), make, task, tag, form, 'G20W')
+
+
 def check_g7_through_env_step(make, tag=''):
     """G7 = BASELINE.json configs[0]: one `left` env, 8 surrounding vehicles, 200 steps (SUMO-free composition generated from
     the reference's own methods) — through eb_env_step, the composite entry CrossroadEnd2end.step uses (one launch on the

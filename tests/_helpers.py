@@ -370,9 +370,24 @@ class HostModel(object):
         self.api.env_ego_step(self.h, n, self._ptr(eg), self._ptr(ac), self._ptr(nxt), self._ptr(par), self.stream)
         return self._ret(nxt), self._ret(par)
 
+    def _shifted(self, a):
+        """the float32 array at an address 4 bytes past a 16-byte boundary (the one-launch kernels want their arrays aligned: a
+        library call with such an argument takes its separate-launch path)"""
+        a = np.ascontiguousarray(a, np.float32)
+        buf = np.empty(a.size + 8, np.float32)
+        k = ((4 - buf.ctypes.data) % 16) // 4
+        v = buf[k:k + a.size].reshape(a.shape)
+        v[...] = a
+        return v
+
     def get_obs(self, ego, cand, cand_mode, v_light=None, ref_idx=None, path_id=0, virtual=None, exit_id=None, row_mask=None,
-                obs_init=None):
+                obs_init=None, shift=()):
+        """shift: which of 'ego', 'cand' to hand over 4 bytes off a 16-byte boundary (see _shifted)"""
         eg, cd, ri = self._in(ego), self._in(cand), self._in(ref_idx, np.int32)
+        if 'ego' in shift:
+            eg = self._shifted(ego)
+        if 'cand' in shift:
+            cd = self._shifted(cand)
         cm, vl, vf, ex = self._in(cand_mode, np.uint8), self._in(v_light, np.uint8), self._in(virtual, np.uint8), self._in(exit_id, np.uint8)
         n, m = len(eg), cd.shape[1]
         out = self._out((n, self.D)) if obs_init is None else self._in(np.array(obs_init, np.float32))   # (a copy: the oracle writes in place)
@@ -547,6 +562,15 @@ class DeviceModel(HostModel):
 
     def _out(self, shape, dtype=np.float32):
         return self.torch.empty(tuple(shape), dtype=getattr(self.torch, self._TD[np.dtype(dtype)]), device=self.dev)
+
+    def _shifted(self, a):
+        t = self._in(a)
+        buf = self.torch.empty(t.numel() + 8, dtype=self.torch.float32, device=self.dev)
+        k = ((4 - buf.data_ptr()) % 16) // 4
+        v = buf[k:k + t.numel()].view(t.shape)
+        v.copy_(t)
+        assert v.data_ptr() % 16 == 4
+        return v
 
     def _ptr(self, t):
         return None if t is None else C.c_void_p(t.data_ptr())

@@ -3,14 +3,29 @@ equals its own single calls — the same check the GPU suite runs on the one-lau
 import pytest
 
 from tests._env_step_check import (CASES, auto_reset_bad_args_case, auto_reset_case, composite_case, flow_rule_bad_args_case,
-                                   flow_auto_reset_case, flow_rule_case, masked_obs_case, parked_ego_case, reset_pool_case,
-                                   respawn_conflict_case, time_limit_case, wrap_guard_case)
+                                   flow_auto_reset_case, flow_rule_case, g20_parked_auto_reset_case, g20_parked_case, g20_parked_flow_case,
+                                   masked_obs_case, parked_ego_case, reset_pool_case, respawn_conflict_case, time_limit_case, wrap_guard_case)
 from tests._helpers import HostModel
 
 
 @pytest.mark.parametrize('task,B,M,NV,nf', CASES[3:7])
 def test_oracle_env_step_composite(oracle, task, B, M, NV, nf):
     composite_case(lambda t, **kw: HostModel(oracle, t, **kw), task, B, M, NV, nf)
+
+
+@pytest.mark.parametrize('widened', [False, True], ids=['native', 'N16'])
+@pytest.mark.parametrize('task', ['left', 'straight', 'right'])
+def test_oracle_env_step_on_the_parked_g20_scenes(oracle, task, widened):
+    """fixture G20's families A-D, parked, through the composite: the positions come through with their input bits (no allowance), the
+    composite equals the six calls, and its block's x, y, v columns equal the reference's"""
+    g20_parked_case(lambda t, **kw: HostModel(oracle, t, **kw), task, widened=widened)
+
+
+@pytest.mark.parametrize('widened', [False, True], ids=['native', 'N16'])
+@pytest.mark.parametrize('task', ['left', 'straight', 'right'])
+def test_oracle_auto_reset_and_flow_rule_on_the_parked_g20_scenes(oracle, task, widened):
+    g20_parked_auto_reset_case(lambda t, **kw: HostModel(oracle, t, **kw), task, widened=widened)
+    g20_parked_flow_case(lambda t, **kw: HostModel(oracle, t, **kw), task, widened=widened)
 
 
 @pytest.mark.parametrize('task', ['left', 'straight', 'right'])

@@ -167,6 +167,19 @@ def test_g6_ego_dynamics_r_bound_and_corners(oracle, task):
                           'alpha_f_bound', 'alpha_r_bound', 'r_bound', 'Corner_point'}                              # E2E:151-183
 
 
+# ---- G20: env-side logic on edge scenes (filter bounds, sort ties, walls, the done chain) ---------
+@pytest.mark.parametrize('form', ['single', 'exit0', 'masked', 'separate_staged', 'separate_unstaged'])
+@pytest.mark.parametrize('task', TASKS)
+def test_g20_env_edges(oracle, task, form):
+    CK.check_g20_env_edges(lambda task, **kw: HostModel(oracle, task, **kw), task, form=form)
+
+
+@pytest.mark.parametrize('form', ['single', 'exit0', 'masked', 'separate_staged', 'separate_unstaged'])
+@pytest.mark.parametrize('task', TASKS)
+def test_g20w_env_edges_16_slots(oracle, task, form):
+    CK.check_g20w_env_edges(lambda task, **kw: HostModel(oracle, task, **kw), task, form=form)
+
+
 # ---- G7: BASELINE.json configs[0] — one env, 8 vehicles, 200 steps ------------------------------
 def test_g7_config1_single_env_200_steps(oracle):
     g = golden('g7_config1_left')
