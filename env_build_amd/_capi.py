@@ -250,10 +250,28 @@ TRAIN_FAMILIES = {
 }
 _FAMILY_TABLES = (FAMILIES, MORE_FAMILIES, POLICY_FAMILIES, TRAIN_FAMILIES)
 
+# include/envbuild_policy_rollout_grad.h: the closed-loop rollout with its parameter gradient.  A table with a version of its own like
+# the others, kept in a FIFTH family table that is consulted AFTER _FAMILY_TABLES: that tuple is the set its tests enumerate.
+EB_POLICY_ROLLOUT_GRAD_ABI_VERSION = 1
+POLICY_ROLLOUT_GRAD_MAX_STEPS = 128
+POLICY_ROLLOUT_GRAD_PROTOTYPES = {
+    'eb_policy_rollout_grad_abi_version': (C.c_int, []),
+    'eb_policy_rollout_grad_supported': (C.c_int, [_P, _P, C.POINTER(_I)]),
+    'eb_policy_rollout_grad_workspace_bytes': (C.c_int, [_P, _P, _I, _I, C.POINTER(C.c_size_t)]),
+    # (h, policy, n_env, steps, obs_in, ref_idx, path_id, action_range, w5 (host), workspace, workspace_bytes, obs_out, out5_steps,
+    #  actions_steps, obs_steps, cost, g_actions_steps, g_obs0, g_params, stream)
+    'eb_policy_rollout_grad': (C.c_int, [_P, _P, _I, _I, _P, _P, _I, C.c_float, _P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+}
+LOOP_GRAD_FAMILIES = {
+    'policy_rollout_grad': ('envbuild_policy_rollout_grad.h', 'closed-loop policy rollout gradient', 'policy-rollout-gradient',
+                            'eb_policy_rollout_grad_abi_version', EB_POLICY_ROLLOUT_GRAD_ABI_VERSION, POLICY_ROLLOUT_GRAD_PROTOTYPES),
+}
+_ALL_FAMILY_TABLES = _FAMILY_TABLES + (LOOP_GRAD_FAMILIES,)
+
 
 def family_row(family):
-    """The six-tuple of one optional family: FAMILIES first, then MORE_FAMILIES, POLICY_FAMILIES and TRAIN_FAMILIES."""
-    for table in _FAMILY_TABLES:
+    """The six-tuple of one optional family: FAMILIES first, then MORE_FAMILIES, POLICY_FAMILIES, TRAIN_FAMILIES and LOOP_GRAD_FAMILIES."""
+    for table in _ALL_FAMILY_TABLES:
         if family in table:
             return table[family]
     raise KeyError(family)
@@ -279,7 +297,7 @@ class CApi(object):
         self.backend = self.lib.eb_backend().decode()
 
     def family_fn(self, family, symbol):
-        """The raw ctypes function of one entry of an optional family (a key of FAMILIES, MORE_FAMILIES, POLICY_FAMILIES or TRAIN_FAMILIES), the family bound on first use;
+        """The raw ctypes function of one entry of an optional family (a key of FAMILIES, MORE_FAMILIES, POLICY_FAMILIES, TRAIN_FAMILIES or LOOP_GRAD_FAMILIES), the family bound on first use;
         EbError when this library does not export it or speaks another version of it."""
         header, label, abi, version_symbol, version, prototypes = family_row(family)
         fns = self.__dict__.setdefault('_%s_fns' % family, {})
@@ -321,6 +339,9 @@ class CApi(object):
 
     def mlp_grad_fn(self, symbol):
         return self.family_fn('mlp_grad', symbol)
+
+    def policy_rollout_grad_fn(self, symbol):
+        return self.family_fn('policy_rollout_grad', symbol)
 
     def check(self, rc):
         if rc != 0:
@@ -368,7 +389,7 @@ class CApi(object):
     def __getattr__(self, name):
         # eb_xxx(...) with return-code checking: api.rollout_step(h, ...)
         sym = 'eb_' + name
-        family = next((f for table in _FAMILY_TABLES for f, row in table.items() if sym in row[5]), None)
+        family = next((f for table in _ALL_FAMILY_TABLES for f, row in table.items() if sym in row[5]), None)
         fn = self.family_fn(family, sym) if family else getattr(self.lib, sym)
 
         def call(*args):

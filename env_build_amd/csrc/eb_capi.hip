@@ -33,6 +33,8 @@
 #include "eb_policy_rollout.h"
 #include "../../include/envbuild_mlp_grad.h"
 #include "eb_policy_grad.h"
+#include "../../include/envbuild_policy_rollout_grad.h"
+#include "eb_policy_rollout_grad.h"
 #include "eb_grad.h"
 #include "eb_kernels.h"
 
@@ -2357,6 +2359,137 @@ int eb_mlp_backward(eb_mlp m, int32_t n, const float* obs, const float* g_out, i
     G.ws = static_cast<float*>(workspace);
     EB_HIP(hipSetDevice(m->cfg.device));
     EB_HIP(eb::launch_mlp_backward(G, (hipStream_t)stream));
+    return EB_OK;
+}
+
+}  // extern "C"
+
+// ---- include/envbuild_policy_rollout_grad.h: the closed-loop rollout and its gradient (eb_policy_rollout_grad.hip) ----
+// the first condition of eb_policy_rollout_grad_supported's list this pair of handles does not meet, in g_err, as the code to return;
+// EB_OK when there is none
+static int policy_rollout_grad_fits(eb_handle h, eb_mlp m) {
+    const int D = obs_dim(h->cfg);
+    if (m->precision != EB_MLP_PRECISION_F32)
+        return fail(EB_EINVAL, "eb_policy_rollout_grad: the policy's precision must be EB_MLP_PRECISION_F32 (the gradient is that of the fp32 "
+                               "forward; eb_mlp_set_precision)");
+    if (m->units > eb::MLP_GRAD_MAX_UNITS)
+        return fail_limit("eb_policy_rollout_grad: hidden width %d pads to %d, beyond the kernels' limit of %d", (int)m->cfg.n_units, m->units,
+                          eb::MLP_GRAD_MAX_UNITS);
+    if (m->cfg.obs_dim != D) return fail_limit("eb_policy_rollout_grad: the policy's obs_dim %d is not the model's %d", (int)m->cfg.obs_dim, D);
+    if (m->cfg.out_dim != 4)
+        return fail_limit("eb_policy_rollout_grad: the policy's out_dim %d is not 4 (mean and log-std of two actions)", (int)m->cfg.out_dim);
+    if (h->cfg.n_veh > eb::PRG_MAX_VEH)
+        return fail_limit("eb_policy_rollout_grad: n_veh %d exceeds the kernel's limit of %d vehicle slots", (int)h->cfg.n_veh, eb::PRG_MAX_VEH);
+    if (h->cfg.n_future != 0)
+        return fail_limit("eb_policy_rollout_grad: n_future %d is not supported (0, the reference's default)", (int)h->cfg.n_future);
+    if (m->cfg.device != h->cfg.device) return fail(EB_EINVAL, "eb_policy_rollout_grad: policy and model live on different devices");
+    const size_t lds = eb::policy_rollout_grad_lds_bytes(D, h->cfg.n_veh, std::max(m->k_pad0, m->units) + 4);
+    if (lds > eb::policy_rollout_grad_lds_limit())
+        return fail_limit("eb_policy_rollout_grad: a block needs %zu bytes of LDS, a compute unit has %zu for it", lds,
+                          eb::policy_rollout_grad_lds_limit());
+    if (m->layers_set != (1u << (m->cfg.n_hidden + 1)) - 1u)
+        return fail(EB_ESTATE, "eb_policy_rollout_grad: a layer was never set (eb_mlp_set_layer for every layer, or eb_mlp_set_params_device)");
+    return EB_OK;
+}
+
+// n_env and steps against the entry's caps; the rows of the row reduction in *rows
+static int policy_rollout_grad_shape(int32_t n_env, int32_t steps, long long* n_pad, long long* rows) {
+    if (n_env < 0) return fail(EB_EINVAL, "eb_policy_rollout_grad: n_env < 0");
+    if (steps < 1 || steps > eb::PRG_MAX_STEPS)
+        return fail_limit("eb_policy_rollout_grad: steps %d is outside 1 .. %d", (int)steps, eb::PRG_MAX_STEPS);
+    *n_pad = ((long long)n_env + eb::MLP_ROWS - 1) / eb::MLP_ROWS * eb::MLP_ROWS;
+    *rows = *n_pad * steps;
+    if (*rows > eb::PRG_MAX_ROWS)
+        return fail_limit("eb_policy_rollout_grad: %d steps x %lld padded envs are %lld rows, one row reduction takes %lld: split the batch",
+                          (int)steps, *n_pad, *rows, eb::PRG_MAX_ROWS);
+    return EB_OK;
+}
+
+// the row reduction's arguments and the workspace's size: mlp_grad_layout for `rows` rows, then the tape
+static size_t policy_rollout_grad_layout(eb_mlp m, long long rows, float action_range, eb::MlpGradArgs* G, long long* tape_off) {
+    mlp_grad_args(m, (int32_t)rows, eb::MLP_HEAD_ACTION, action_range, G);
+    const size_t mlp_bytes = eb::mlp_grad_layout(*G);
+    *tape_off = (long long)(mlp_bytes / sizeof(float));
+    return mlp_bytes + (size_t)rows * eb::PRG_TAPE_FLOATS * sizeof(float);
+}
+
+extern "C" {
+
+int eb_policy_rollout_grad_abi_version(void) { return EB_POLICY_ROLLOUT_GRAD_ABI_VERSION; }
+
+int eb_policy_rollout_grad_supported(eb_handle h, eb_mlp policy, int32_t* ok) {
+    if (!h) return fail(EB_EINVAL, "eb_policy_rollout_grad_supported: null handle");
+    if (!policy) return fail(EB_EINVAL, "eb_policy_rollout_grad_supported: null policy");
+    if (!ok) return fail(EB_EINVAL, "eb_policy_rollout_grad_supported: null output pointer");
+    *ok = policy_rollout_grad_fits(h, policy) == EB_OK ? 1 : 0;
+    return EB_OK;
+}
+
+int eb_policy_rollout_grad_workspace_bytes(eb_handle h, eb_mlp policy, int32_t n_env, int32_t steps, size_t* bytes) {
+    if (!h) return fail(EB_EINVAL, "eb_policy_rollout_grad_workspace_bytes: null handle");
+    if (!policy) return fail(EB_EINVAL, "eb_policy_rollout_grad_workspace_bytes: null policy");
+    if (!bytes) return fail(EB_EINVAL, "eb_policy_rollout_grad_workspace_bytes: null output pointer");
+    int rc = policy_rollout_grad_fits(h, policy);
+    if (rc) return rc;
+    long long n_pad, rows;
+    rc = policy_rollout_grad_shape(n_env, steps, &n_pad, &rows);
+    if (rc) return rc;
+    eb::MlpGradArgs G;
+    long long tape_off;
+    *bytes = n_env == 0 ? 0 : policy_rollout_grad_layout(policy, rows, 0.0f, &G, &tape_off);
+    return EB_OK;
+}
+
+int eb_policy_rollout_grad(eb_handle h, eb_mlp policy, int32_t n_env, int32_t steps, const float* obs_in, const int32_t* ref_idx,
+                           int32_t path_id, float action_range, const float* w5, void* workspace, size_t workspace_bytes,
+                           float* obs_out, float* out5_steps, float* actions_steps, float* obs_steps, float* cost,
+                           float* g_actions_steps, float* g_obs0, float* g_params, void* stream) {
+    int rc = check_tape(h, "eb_policy_rollout_grad: null handle");
+    if (rc) return rc;
+    if (!policy) return fail(EB_EINVAL, "eb_policy_rollout_grad: null policy");
+    rc = policy_rollout_grad_fits(h, policy);
+    if (rc) return rc;
+    long long n_pad, rows;
+    rc = policy_rollout_grad_shape(n_env, steps, &n_pad, &rows);
+    if (rc) return rc;
+    eb::MlpGradArgs G;
+    long long tape_off = 0;
+    const size_t need = policy_rollout_grad_layout(policy, rows, action_range, &G, &tape_off);
+    G.g_params = g_params;
+    if (n_env == 0) {                                                           // zero rows: the reduce kernel writes zeros, nothing else runs
+        if (!g_params) return EB_OK;
+        EB_HIP(hipSetDevice(h->cfg.device));
+        EB_HIP(eb::launch_mlp_wgrad(G, (hipStream_t)stream));
+        return EB_OK;
+    }
+    if (!obs_in || !w5 || !workspace) return fail(EB_EINVAL, "eb_policy_rollout_grad: null obs_in, w5 or workspace");
+    if (obs_out == obs_in) return fail(EB_EINVAL, "eb_policy_rollout_grad: obs_out must not alias obs_in");
+    if (workspace_bytes < need)
+        return fail_limit("eb_policy_rollout_grad: the workspace holds %zu bytes, %d envs x %d steps need %zu "
+                          "(eb_policy_rollout_grad_workspace_bytes)", workspace_bytes, (int)n_env, (int)steps, need);
+    rc = check_path_arg(h, &ref_idx, &path_id);
+    if (rc) return rc;
+    EB_HIP(hipSetDevice(h->cfg.device));
+    eb::PolicyRolloutGradArgs A;
+    std::memset(&A, 0, sizeof A);
+    fill_tape_scene(h, n_env, steps, A);
+    A.obs0 = obs_in; A.ref_idx = ref_idx; A.path_id = path_id;
+    A.obs_out = obs_out; A.out5_steps = out5_steps; A.actions_steps = actions_steps; A.obs_steps = obs_steps; A.cost = cost;
+    A.g_actions_steps = g_actions_steps; A.g_obs0 = g_obs0;
+    A.nv_magic = eb::div_magic(A.n_veh);
+    A.n_pad = (int)n_pad;
+    for (int k = 0; k < 5; ++k) A.w5[k] = w5[k];
+    // the policy, as mlp_grad_args hands it to the backward's kernels
+    const eb::MlpArgs& F = G.fwd;
+    A.scale = F.scale; A.n_hidden = F.n_hidden; A.units = F.units; A.hidden_act = F.hidden_act; A.out_act = F.out_act;
+    A.action_range = action_range; A.row_stride = F.row_stride; A.kt_out = G.kt_out;
+    for (int L = 0; L < eb::MLP_MAX_HIDDEN; ++L) A.hid[L] = F.hid[L];
+    A.outl = F.outl;
+    G.ws = A.ws = static_cast<float*>(workspace);
+    for (int L = 0; L < eb::MLP_GRAD_LAYERS; ++L) { A.wt[L] = G.wt[L]; A.x_off[L] = G.x_off[L]; A.d_off[L] = G.d_off[L]; }
+    A.tape_off = tape_off;
+    EB_HIP(eb::launch_policy_rollout_grad(h->cfg.task, A, (hipStream_t)stream));
+    if (g_params) EB_HIP(eb::launch_mlp_wgrad(G, (hipStream_t)stream));
     return EB_OK;
 }
 

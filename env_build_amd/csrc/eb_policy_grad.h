@@ -64,5 +64,7 @@ struct MlpGradArgs {
 // workspace size in bytes for A.fwd.n rows
 size_t mlp_grad_layout(MlpGradArgs& A);
 hipError_t launch_mlp_backward(const MlpGradArgs& A, hipStream_t s);
+// mlp_wgrad_kernel + mlp_wgrad_reduce_kernel without the data pass: the workspace was filled by another kernel
+hipError_t launch_mlp_wgrad(const MlpGradArgs& A, hipStream_t s);
 
 }  // namespace eb

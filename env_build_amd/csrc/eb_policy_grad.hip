@@ -565,6 +565,26 @@ hipError_t launch_mlp_backward(const MlpGradArgs& A, hipStream_t s) {
     return hipSuccess;
 }
 
+// the row reduction alone: A.ws already holds x_l and d_l for A.fwd.n rows in mlp_grad_layout's places (eb_policy_rollout_grad.hip's
+// block writes them step by step); same grids, so same sums, as the tail of launch_mlp_backward
+hipError_t launch_mlp_wgrad(const MlpGradArgs& A, hipStream_t s) {
+    const MlpArgs& F = A.fwd;
+    if (!A.g_params) return hipSuccess;
+    const int splits = F.n > 0 ? (F.n + MLP_GRAD_SPLIT_ROWS - 1) / MLP_GRAD_SPLIT_ROWS : 0;
+    if (F.n > 0) {
+        MlpGradArgs B = A;
+        for (int L = 0; L <= F.n_hidden; ++L) {
+            B.wl[L].x = A.ws + A.x_off[L];
+            B.wl[L].d = A.ws + A.d_off[L];
+        }
+        hipLaunchKernelGGL(mlp_wgrad_kernel, dim3(A.n_tasks, (splits + 3) / 4), dim3(MLP_THREADS), 0, s, B);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(mlp_wgrad_reduce_kernel, dim3((unsigned)((A.param_count + 255) / 256)), dim3(256), 0, s, A, splits);
+    return hipGetLastError();
+}
+
 // ---- eb_mlp_set_params_device ----
 // binary16 bits of x: the hardware conversion (round to nearest even, overflow to +-inf, subnormal results kept)
 EB_DEV uint16_t f16_bits_dev(float x) { return __builtin_bit_cast(uint16_t, (_Float16)x); }

@@ -7,6 +7,9 @@ inference handle evaluates.  The handle is brought up to date with eb_mlp_set_pa
 since the last upload (its `_version`): no host copy, no synchronisation, one policy.  The same handle serves the shield,
 `policy_rollout` and `HierarchicalDecision`, at either precision; differentiating needs precision 'fp32'.
 
+`rollout_loss` is the ADP loss of a whole closed-loop rollout under a `TrainableMLPNet` as ONE autograd node: value and parameter
+gradient come from eb_policy_rollout_grad (include/envbuild_policy_rollout_grad.h) in its forward.
+
 `mlp_backward_reference` restates the header's contract in NumPy.  There is no CPU path for the network itself.
 """
 import ctypes as C
@@ -19,7 +22,7 @@ from . import _capi
 from .dynamics_and_models import _dev
 from .policy import MLPNet, _act_det, _tanh_det
 
-__all__ = ['TrainableMLPNet', 'mlp_backward_reference']
+__all__ = ['TrainableMLPNet', 'mlp_backward_reference', 'rollout_loss']
 
 
 def _act(act, x, dtype):
@@ -255,3 +258,50 @@ class TrainableMLPNet(MLPNet):
 
     def mode(self, x, action_range):
         return _Evaluate.apply(self, 1, -1.0 if action_range is None else float(action_range), self._graph_in(x), *self._params)
+
+
+class _RolloutLoss(torch.autograd.Function):
+    """J = sum over envs of the rollout's weighted cost; the entry runs in forward and leaves dJ/dtheta for backward"""
+
+    @staticmethod
+    def forward(ctx, model, net, steps, w5, action_range, fused, *params):
+        from .policy_rollout import _composed_grad, _fused_grad
+        net._sync()
+        run = _fused_grad if fused else _composed_grad
+        out = run(model, net, -1.0 if action_range is None else float(action_range), steps, w5, ('cost', 'g_params'))
+        ctx.g_flat = out['g_params']
+        ctx.slices = net._slices
+        return out['cost'].sum()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        flat = ctx.g_flat * g
+        return (None,) * 6 + tuple(flat[a:b].view(shape) for a, b, shape in ctx.slices)
+
+
+def rollout_loss(model, net, obs0, ref_idx, horizon, w5, action_range=1.0, fused=None):
+    """J = sum over envs and steps of out5 weighted by w5, for the closed-loop rollout of `horizon` steps of `model` (a 'training'-mode
+    EnvironmentModel / DifferentiableEnvironmentModel) under the TrainableMLPNet `net` from obs0 [B, D] with paths ref_idx [B]: a scalar
+    tensor on the autograd graph whose backward hands upstream * dJ/dtheta to the network's parameters.  ADP's loss
+    (examples/adp_policy_gradient.py:rollout_loss with lam) is w5 = (-1, lam, 0, 0, 0) / (horizon * B).
+
+    One autograd node: eb_policy_rollout_grad runs in the forward (three launches whatever the horizon) and the gradient is complete
+    when forward returns.  A handle whose flat tensor was written since its last upload is refreshed first, as every launch on a
+    TrainableMLPNet is.  Weights modified between this forward and its backward do not matter here — unlike call / mode, whose
+    backward recomputes — because nothing is recomputed: the gradient is that of the weights the forward ran with.
+    fused=None takes the one-call entry where eb_policy_rollout_grad_supported says yes, the composed loop of single entries
+    elsewhere (policy_rollout.policy_rollout_grad's rule)."""
+    from . import policy_rollout as pr
+    if not isinstance(net, TrainableMLPNet):
+        raise TypeError('rollout_loss differentiates a TrainableMLPNet, got %s' % type(net).__name__)
+    steps = int(horizon)
+    if steps < 1:
+        raise ValueError('horizon must be at least 1')
+    w5 = pr._w5(w5)
+    model.reset(obs0.detach() if isinstance(obs0, torch.Tensor) else obs0, ref_idx)
+    if fused is None:
+        ok = C.c_int32(0)
+        model.api.policy_rollout_grad_supported(model.handle, net._handle, C.byref(ok))
+        fused = bool(ok.value)
+    return _RolloutLoss.apply(model, net, steps, w5, action_range, bool(fused), *net._params)

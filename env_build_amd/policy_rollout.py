@@ -7,7 +7,11 @@ every step's five outputs, actions and states, the shield's sum and flag.
 When the policy is this package's own `LoadPolicy` / `Policy4Toyota` with an fp16 `MLPNet`, and the pair fits the kernel
 (include/envbuild_policy_rollout.h:eb_policy_rollout_supported), the whole horizon is ONE launch — policy and model step fused, the
 rows never leaving the compute unit — and every array equals the loop's bit for bit.  Any other policy (an fp32 network, a callable)
-runs the generic loop of `model.rollout_out(policy(model.obses))`.  Host glue only."""
+runs the generic loop of `model.rollout_out(policy(model.obses))`.  Host glue only.
+
+`policy_rollout_grad` is the training side: the same rollout under an fp32 network together with the gradient of its weighted cost with
+respect to the network's parameters (include/envbuild_policy_rollout_grad.h) — three launches whatever the horizon where the pair fits
+the kernel, the composed loop of the existing single entries elsewhere."""
 import ctypes as C
 
 import torch
@@ -17,6 +21,7 @@ from .dynamics_and_models import DevArray, _stream, _unwrap
 from .shield import PENALTIES, _native_policy
 
 WANT = ('out5', 'actions', 'obs')
+GRAD_WANT = ('out5', 'actions', 'obs', 'cost', 'g_actions', 'g_obs0', 'g_params')
 
 
 def _fused_pair(model, policy):
@@ -120,4 +125,146 @@ def _fused(model, native, steps, penalty, want):
         out['obs_steps'] = DevArray(obss)
     out['punish'] = DevArray(punish)
     out['safe'] = DevArray(safe.bool())
+    return out
+
+
+# ---- the rollout with its parameter gradient ----
+def _net_of(policy, action_range):
+    """(MLPNet, action_range) of a LoadPolicy / Policy4Toyota, or of a bare MLPNet with the action_range given"""
+    from .policy import MLPNet
+    if isinstance(policy, MLPNet):
+        if policy.output_dim != 4:
+            raise ValueError('the policy network must have 4 outputs (mean and log-std of two actions), got %d' % policy.output_dim)
+        return policy, action_range
+    native = _native_policy(policy)
+    if native is None:
+        raise ValueError('policy_rollout_grad needs an MLPNet / TrainableMLPNet or a LoadPolicy / Policy4Toyota with a deterministic policy')
+    return native
+
+
+def _w5(w5):
+    w5 = [float(v) for v in w5]
+    if len(w5) != 5:
+        raise ValueError('w5 must hold the five weights of out5')
+    return w5
+
+
+def policy_rollout_grad(model, policy, obses, steps, w5, path_index=None, want=('cost', 'g_params'), ref_indexes=None, action_range=1.0,
+                        fused=None):
+    """The closed-loop rollout of `steps` steps under an fp32 network and the gradient of J = sum over envs of cost with respect to the
+    network's parameters.  -> dict of DevArrays: 'obs' [B, D] (the state after the last step) and by `want` (a subset of GRAD_WANT)
+    'out5_steps' [steps, 5, B], 'actions_steps' [steps, B, 2], 'obs_steps' [steps, B, D], 'cost' [B] (the sum over t of out5 weighted
+    by w5, in include/envbuild_cand.h's order), 'g_actions_steps' [steps, B, 2], 'g_obs0' [B, 9], 'g_params' (flat, in
+    Model.get_weights() order); 'fused' says whether eb_policy_rollout_grad ran.
+
+    w5: five weights, also the cotangent of out5 at every step and env; ADP's loss is (-1, lam, 0, 0, 0) / (steps * B).
+    `policy`: an MLPNet / TrainableMLPNet (its action head with `action_range`), or a LoadPolicy / Policy4Toyota.  `path_index` selects
+    the path for a model in 'selecting' mode; a 'training'-mode model takes `ref_indexes` (or keeps its own).
+    fused=None uses the one-call entry where eb_policy_rollout_grad_supported says yes and the composed loop of the existing entries
+    (eb_policy_run_batch, eb_rollout_step, eb_rollout_step_vjp, eb_mlp_backward) elsewhere: the same arrays bit for bit, g_params as
+    the float32 sum over t of the per-step gradients.  fused=True insists on the entry (a refused pair raises with the C reason),
+    fused=False on the loop."""
+    want = tuple(want)
+    if any(w not in GRAD_WANT for w in want):
+        raise ValueError('want must be a subset of %s' % (GRAD_WANT,))
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError('steps must be at least 1')
+    w5 = _w5(w5)
+    net, action_range = _net_of(policy, action_range)
+    if path_index is not None:
+        model.add_traj(obses, path_index)
+    else:
+        model.reset(obses, model.ref_indexes if ref_indexes is None else ref_indexes)
+    if model.state_dtype != torch.float32:
+        raise _capi.EbError("policy_rollout_grad: state_dtype='float16' has no reverse pass; use state_dtype='float32'")
+    ar = -1.0 if action_range is None else float(action_range)
+    if fused is None:
+        ok = C.c_int32(0)
+        model.api.policy_rollout_grad_supported(model.handle, net._handle, C.byref(ok))
+        fused = bool(ok.value)
+    out = (_fused_grad if fused else _composed_grad)(model, net, ar, steps, w5, want)
+    model.obses = DevArray(out['obs'])
+    model._after_tracking()
+    return {k: (v if k == 'fused' else DevArray(v)) for k, v in out.items()}
+
+
+_GRAD_NAMES = {'out5': 'out5_steps', 'actions': 'actions_steps', 'obs': 'obs_steps', 'cost': 'cost', 'g_actions': 'g_actions_steps',
+               'g_obs0': 'g_obs0', 'g_params': 'g_params'}
+
+
+def _param_count(model, net):
+    count = C.c_int64(0)
+    model.api.mlp_param_count(net._handle, C.byref(count))
+    return count.value
+
+
+def _fused_grad(model, net, ar, steps, w5, want):
+    """one eb_policy_rollout_grad -> dict of tensors"""
+    obs = _unwrap(model.obses).detach()
+    B, D = obs.shape
+    dev = model.device
+    ri, pid = model._path_args()
+    handle = net._handle
+    need = C.c_size_t(0)
+    model.api.policy_rollout_grad_workspace_bytes(model.handle, handle, B, steps, C.byref(need))
+    ws = torch.empty((max(need.value, 16),), dtype=torch.uint8, device=dev)
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    shapes = {'out5': (steps, 5, B), 'actions': (steps, B, 2), 'obs': (steps, B, D), 'cost': (B,), 'g_actions': (steps, B, 2),
+              'g_obs0': (B, 9), 'g_params': (_param_count(model, net),)}
+    bufs = {k: (f32(*shapes[k]) if k in want else None) for k in GRAD_WANT}
+    obs_out = torch.empty_like(obs)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    model.api.policy_rollout_grad(model.handle, handle, B, steps, p(obs), p(ri), pid, C.c_float(ar), (C.c_float * 5)(*w5), p(ws), need.value,
+                                  p(obs_out), *[p(bufs[k]) for k in GRAD_WANT], _stream(dev))
+    out = {'fused': True, 'obs': obs_out}
+    out.update({_GRAD_NAMES[k]: v for k, v in bufs.items() if v is not None})
+    return out
+
+
+def _composed_grad(model, net, ar, steps, w5, want):
+    """the loop of existing entries the one-call form is held to: forward `steps` x [eb_policy_run_batch -> eb_rollout_step], then for
+    t = steps - 1 .. 0 eb_rollout_step_vjp and eb_mlp_backward, lambda_t = s_t[:, :9] + p_t[:, :9]"""
+    api = model.api
+    obs = _unwrap(model.obses).detach()
+    B, D = obs.shape
+    dev = model.device
+    ri, pid = model._path_args()
+    handle = net._handle
+    stream = _stream(dev)
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    pre, acts, out5 = f32(steps + 1, B, D), f32(steps, B, 2), f32(steps, 5, B)
+    pre[0] = obs
+    scaled = f32(B, 2)
+    for t in range(steps):
+        api.policy_run_batch(handle, B, p(pre[t]), C.c_float(ar), p(acts[t]), stream)
+        api.rollout_step(model.handle, B, p(pre[t]), p(acts[t]), p(ri), pid, p(pre[t + 1]), p(out5[t]), p(scaled), stream)
+    need = C.c_size_t(0)
+    api.mlp_backward_workspace_bytes(handle, B, C.byref(need))
+    ws = torch.empty((max(need.value, 16),), dtype=torch.uint8, device=dev)
+    g5 = torch.tensor(w5, dtype=torch.float32, device=dev).view(5, 1).expand(5, B).contiguous()
+    lam, s, pt, g_act = torch.zeros((B, 9), dtype=torch.float32, device=dev), f32(B, 9), f32(B, D), f32(steps, B, 2)
+    g_step = f32(_param_count(model, net)) if 'g_params' in want else None
+    g_par = torch.zeros_like(g_step) if g_step is not None else None
+    vjp = api.grad_fn('eb_rollout_step_vjp')
+    for t in range(steps - 1, -1, -1):
+        api.check(vjp(model.handle, B, p(pre[t]), p(acts[t]), p(ri), pid, p(lam), 9, p(g5), p(s), 9, p(g_act[t]), stream))
+        api.mlp_backward(handle, B, p(pre[t]), p(g_act[t]), 1, C.c_float(ar), p(ws), need.value, None, p(pt), p(g_step), stream)
+        lam = s + pt[:, :9]
+        if g_par is not None:
+            g_par = g_par + g_step
+    out = {'fused': False, 'obs': pre[steps].clone()}
+    if 'cost' in want:          # include/envbuild_cand.h: s_t = the rows with a non-zero weight in row order, J = ascending t from +0
+        rows = [r for r in range(5) if w5[r] != 0.0]
+        J = torch.zeros((B,), dtype=torch.float32, device=dev)
+        for t in range(steps if rows else 0):
+            st = None
+            for r in rows:
+                term = out5[t, r] * w5[r]
+                st = term if st is None else st + term
+            J = J + st
+        out['cost'] = J
+    given = {'out5': out5, 'actions': acts, 'obs': pre[1:], 'g_actions': g_act, 'g_obs0': lam, 'g_params': g_par}
+    out.update({_GRAD_NAMES[k]: given[k] for k in want if k != 'cost'})
     return out

@@ -1,0 +1,160 @@
+"""What the CPU and the GPU tests of eb_policy_rollout_grad (include/envbuild_policy_rollout_grad.h) share: the entry as one call, and
+the yardstick — the loop of existing single calls through the same two handles, forward and back.  A helper module like _tape.py and
+_policy_cases.py: pytest does not collect it, and importing it touches no device."""
+import ctypes as C
+
+import numpy as np
+
+from env_build_amd.synthetic import assemble_obs, make_rollout_inputs
+from tests._helpers import HostModel, oracle_lib
+from tests._policy_cases import make_layers
+from tests._tape import TapeModel, cost_in_the_headers_order
+
+SENTINEL = -77.25
+W5 = (-1.0, 10.0, 0.0, 0.0, 0.0)                # ADP's loss before its 1 / (steps * n_env): rewards against the training penalty
+OUTPUTS = ('last', 'out5', 'actions', 'obs', 'cost', 'g_actions', 'g_obs0', 'g_params')
+PER_ROW = ('last', 'out5', 'actions', 'obs', 'cost', 'g_actions', 'g_obs0')
+
+
+def same(a, b):
+    return a.shape == b.shape and np.array_equal(a, b, equal_nan=True)
+
+
+def floats(v):
+    return (C.c_float * len(v))(*[float(x) for x in v])
+
+
+def param_count(dev, m):
+    count = C.c_int64(-1)
+    dev.api.mlp_param_count(m, C.byref(count))
+    return count.value
+
+
+def supported(dev, m):
+    ok = C.c_int32(-7)
+    dev.api.policy_rollout_grad_supported(dev.h, m, C.byref(ok))
+    return ok.value, dev.api.lib.eb_last_error().decode()
+
+
+def workspace_bytes(dev, m, n, steps):
+    need = C.c_size_t(0)
+    dev.api.policy_rollout_grad_workspace_bytes(dev.h, m, int(n), int(steps), C.byref(need))
+    return need.value
+
+
+def shapes(n, D, steps, count):
+    return {'last': (n, D), 'out5': (steps, 5, n), 'actions': (steps, n, 2), 'obs': (steps, n, D), 'cost': (n,),
+            'g_actions': (steps, n, 2), 'g_obs0': (n, 9), 'g_params': (count,)}
+
+
+def entry(dev, m, obs, steps, w5=W5, ref_idx=None, path_id=0, ar=1.0, want=OUTPUTS):
+    """eb_policy_rollout_grad -> dict of NumPy arrays; an output that is not in `want` is passed as NULL, the others start as SENTINEL"""
+    torch = dev.torch
+    ob, ri = dev._in(obs), dev._in(ref_idx, np.int32)
+    n, D = ob.shape
+    need = workspace_bytes(dev, m, n, steps)
+    ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev.dev)
+    bufs = {k: (torch.full(s, SENTINEL, device=dev.dev) if k in want else None) for k, s in shapes(n, D, steps, param_count(dev, m)).items()}
+    p = dev._ptr
+    dev.api.policy_rollout_grad(dev.h, m, n, int(steps), p(ob), p(ri), int(path_id), C.c_float(ar), floats(w5), p(ws), need,
+                                *[p(bufs[k]) for k in OUTPUTS], dev.stream)
+    return {k: dev._ret(v) for k, v in bufs.items() if v is not None}
+
+
+def mlp_backward(dev, m, obs, g, ar, want_params):
+    """one eb_mlp_backward with head 1 over device tensors -> (g_obs or None, g_params or None) as device tensors"""
+    torch = dev.torch
+    n = obs.shape[0]
+    need = C.c_size_t(0)
+    dev.api.mlp_backward_workspace_bytes(m, n, C.byref(need))
+    ws = torch.empty((max(need.value, 16),), dtype=torch.uint8, device=dev.dev)
+    g_obs = None if want_params else torch.empty_like(obs)
+    g_par = torch.empty((param_count(dev, m),), device=dev.dev) if want_params else None
+    p = dev._ptr
+    dev.api.mlp_backward(m, n, p(obs), p(g), 1, C.c_float(ar), p(ws), need.value, None, p(g_obs), p(g_par), dev.stream)
+    return g_obs, g_par
+
+
+def loop(dev, m, obs0, steps, w5=W5, ref_idx=None, path_id=0, ar=1.0, g_params=False):
+    """the yardstick: `steps` x [eb_policy_run_batch -> eb_rollout_step], then for t = steps - 1 .. 0 eb_rollout_step_vjp with
+    g_obs_out = lambda_{t+1} and g_out5 = w5 at every env, eb_mlp_backward (head 1) on its g_actions, lambda_t = s_t[:, :9] + p_t[:, :9].
+    With g_params, one more eb_mlp_backward over the steps * n rows (t, env) in t-major order.  `dev` is a TapeModel."""
+    torch = dev.torch
+    ob, ri = dev._in(obs0), dev._in(ref_idx, np.int32)
+    n, D = ob.shape
+    pre, acts, out5s = [ob], [], []
+    sc = torch.empty((n, 2), device=dev.dev)
+    p = dev._ptr
+    for t in range(steps):
+        a, nxt, o5 = torch.empty((n, 2), device=dev.dev), torch.empty((n, D), device=dev.dev), torch.empty((5, n), device=dev.dev)
+        dev.api.policy_run_batch(m, n, p(pre[t]), C.c_float(ar), p(a), dev.stream)
+        dev.api.rollout_step(dev.h, n, p(pre[t]), p(a), p(ri), int(path_id), p(nxt), p(o5), p(sc), dev.stream)
+        pre.append(nxt); acts.append(a); out5s.append(o5)
+    lam = torch.zeros((n, 9), device=dev.dev)
+    g5 = torch.tensor([float(v) for v in w5], device=dev.dev).view(5, 1).expand(5, n).contiguous()
+    gas = [None] * steps
+    for t in range(steps - 1, -1, -1):
+        s, ga = dev.t_step_vjp(pre[t], acts[t], ri, path_id, lam, g5)
+        pt, _ = mlp_backward(dev, m, pre[t], ga, ar, False)
+        lam = (s[:, :9] + pt[:, :9]).contiguous()
+        gas[t] = ga
+    out5 = torch.stack(out5s)
+    ret = lambda v: dev._ret(v.contiguous())
+    out = {'last': ret(pre[steps]), 'out5': ret(out5), 'actions': ret(torch.stack(acts)), 'obs': ret(torch.stack(pre[1:])),
+           'cost': cost_in_the_headers_order(out5[None], w5)[0], 'g_actions': ret(torch.stack(gas)), 'g_obs0': ret(lam),
+           'pre': ret(torch.stack(pre[:steps]))}
+    if g_params:
+        rows, g = torch.cat(pre[:steps]).contiguous(), torch.cat(gas).contiguous()
+        out['g_params'] = ret(mlp_backward(dev, m, rows, g, ar, True)[1])
+    return out
+
+
+def assert_equal(got, want, what, keys=None):
+    for k, g in got.items():
+        if keys is not None and k not in keys:
+            continue
+        assert same(g, want[k]), '%s: %s differs in %d of %d values' % (
+            what, k, int((~((g == want[k]) | (np.isnan(g) & np.isnan(want[k])))).sum()) if g.shape == want[k].shape else -1, g.size)
+
+
+def rows_of(d, idx):
+    """the per-row outputs of `d` for the envs idx"""
+    pick = {'last': lambda v: v[idx], 'cost': lambda v: v[idx], 'g_obs0': lambda v: v[idx], 'out5': lambda v: v[:, :, idx]}
+    return {k: pick.get(k, lambda v: v[:, idx])(v) for k, v in d.items() if k in PER_ROW}
+
+
+def split_params(flat, dims):
+    obs_dim, n_hidden, n_units, out_dim = dims
+    d = [obs_dim] + [n_units] * n_hidden + [out_dim]
+    out, at = [], 0
+    for L in range(n_hidden + 1):
+        for shape in ((d[L], d[L + 1]), (d[L + 1],)):
+            size = int(np.prod(shape))
+            out.append(flat[at:at + size].reshape(shape))
+            at += size
+    assert at == len(flat)
+    return out
+
+
+_SCENES = {}
+
+
+def scene(task, N, units, n_hidden, B=200, hact='elu', gain=1.0):
+    """start states and a network, made once per case (tests/test_gpu_policy_rollout.py's scene, with the hidden activation and a
+    factor on the output layer's weights): -> obs0, ref_idx, make_mlp's arguments, obs scale"""
+    key = (task, N, units, n_hidden, B, hact, gain)
+    if key not in _SCENES:
+        host = HostModel(oracle_lib(), task, n_veh=N)
+        inp = make_rollout_inputs(task, B, N, 5, seed=21)
+        trk = host.tracking_error(inp['ego'][:, 3], inp['ego'][:, 4], inp['ego'][:, 5], inp['ego'][:, 0], 0, ref_idx=inp['ref_idx'])
+        obs0 = assemble_obs(inp['ego'], trk, inp['veh'])
+        rng = np.random.default_rng(N)
+        layers = make_layers(rng, host.D, n_hidden, units, 4)
+        layers[-1] = ((layers[-1][0] * np.float32(gain)).astype(np.float32), layers[-1][1])
+        scale = rng.uniform(0.02, 0.2, host.D).astype(np.float32)
+        _SCENES[key] = (obs0, inp['ref_idx'], (host.D, n_hidden, units, 4, hact, 'linear', layers), scale)
+    return _SCENES[key]
+
+
+def model(task, N, mode='training'):
+    return TapeModel(task, n_veh=N, mode=mode)

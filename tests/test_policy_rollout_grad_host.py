@@ -1,0 +1,112 @@
+"""CPU (-m "not gpu"): the closed-loop rollout-with-gradient family (include/envbuild_policy_rollout_grad.h) is declared as ctypes binds
+it, lives in a fifth family table that family_row / family_fn / __getattr__ consult after _capi._FAMILY_TABLES (which does not grow),
+is exported by the built library next to a gfx950 policy_rollout_grad_kernel, stays out of the hashed forward sources, refuses NULL
+handles by name without a device and is refused by name by the oracle library."""
+import ctypes as C
+import os
+import re
+
+import pytest
+
+from env_build_amd import _capi, build as eb_build
+from tests._helpers import ROOT, oracle_lib
+
+HEADER = 'envbuild_policy_rollout_grad.h'
+PINNED = ['grad', 'cand', 'cand_grad', 'sample', 'ilqr', 'mlp_f16', 'policy_rollout', 'mlp_grad']
+ENTRIES = ['eb_policy_rollout_grad', 'eb_policy_rollout_grad_abi_version', 'eb_policy_rollout_grad_supported',
+           'eb_policy_rollout_grad_workspace_bytes']
+
+
+def header_src():
+    text = open(os.path.join(ROOT, 'include', HEADER)).read()
+    return text, re.sub(r'/\*.*?\*/', '', text, flags=re.S)
+
+
+def test_header_declares_what_ctypes_binds():
+    text, src = header_src()
+    protos = _capi.POLICY_ROLLOUT_GRAD_PROTOTYPES
+    assert sorted(protos) == sorted(set(re.findall(r'\b(eb_[a-z0-9_]+)\s*\(', src))) == ENTRIES
+    for name, (_res, args) in protos.items():
+        m = re.search(r'\bint\s+%s\s*\(([^)]*)\)\s*;' % name, src)
+        assert m, '%s is not declared in include/%s' % (name, HEADER)
+        assert len([a for a in m.group(1).split(',') if a.strip() != 'void']) == len(args), name
+    assert [len(protos[n][1]) for n in ENTRIES] == [20, 0, 3, 5]
+    assert int(re.search(r'#define EB_POLICY_ROLLOUT_GRAD_ABI_VERSION (\d+)', src).group(1)) == _capi.EB_POLICY_ROLLOUT_GRAD_ABI_VERSION == 1
+    assert int(re.search(r'#define EB_POLICY_ROLLOUT_GRAD_MAX_STEPS (\d+)', src).group(1)) == _capi.POLICY_ROLLOUT_GRAD_MAX_STEPS <= 128
+    assert not set(protos) & set(_capi.PROTOTYPES)
+    for table in _capi._FAMILY_TABLES:
+        for row in table.values():
+            assert not set(protos) & set(row[5])
+    for words in ('bit for bit', 'eb_rollout_step_vjp', 'eb_mlp_backward', 'HOST pointer', 'multiple of 64', 'never another code path'):
+        assert words in text, words
+
+
+def test_the_fifth_family_table():
+    # the four pinned tables and their tuple are what they were
+    assert list(_capi.FAMILIES) == ['grad', 'cand', 'cand_grad', 'sample', 'ilqr']
+    assert list(_capi.MORE_FAMILIES) == ['mlp_f16'] and list(_capi.POLICY_FAMILIES) == ['policy_rollout']
+    assert list(_capi.TRAIN_FAMILIES) == ['mlp_grad']
+    assert _capi._FAMILY_TABLES == (_capi.FAMILIES, _capi.MORE_FAMILIES, _capi.POLICY_FAMILIES, _capi.TRAIN_FAMILIES)
+    assert list(_capi.LOOP_GRAD_FAMILIES) == ['policy_rollout_grad']
+    row = _capi.LOOP_GRAD_FAMILIES['policy_rollout_grad']
+    assert len(row) == 6 == len(_capi.FAMILIES['grad'])
+    assert row[0] == HEADER and row[3] == 'eb_policy_rollout_grad_abi_version' and row[4] == 1
+    assert row[5] is _capi.POLICY_ROLLOUT_GRAD_PROTOTYPES and isinstance(row[1], str) and isinstance(row[2], str)
+    tables = _capi._FAMILY_TABLES + (_capi.LOOP_GRAD_FAMILIES,)
+    assert [f for t in tables for f in t] == PINNED + ['policy_rollout_grad']
+    for family in PINNED + ['policy_rollout_grad']:                        # all nine
+        assert _capi.family_row(family) is next(t[family] for t in tables if family in t)
+        assert len(_capi.family_row(family)) == 6
+    for missing in ('no_such_family', 'mlp_grad_f16'):
+        with pytest.raises(KeyError):
+            _capi.family_row(missing)
+    assert _capi.CApi.policy_rollout_grad_fn
+
+
+def test_hip_library_exports_the_entries_and_a_gfx950_kernel():
+    lib_path = eb_build.build()            # hipcc --offload-arch=gfx950 (cross-compiles without a GPU)
+    import torch  # noqa: F401  (binds the HIP runtime torch ships before ours, as the product does)
+    lib, blob = C.CDLL(lib_path), open(lib_path, 'rb').read()
+    for name in ENTRIES:
+        assert hasattr(lib, name), name
+    assert lib.eb_policy_rollout_grad_abi_version() == 1
+    assert b'gfx950' in blob and b'policy_rollout_grad_kernel' in blob and b'mlp_wgrad_kernel' in blob
+    public = os.path.join('..', '..', 'include', HEADER)
+    new = {'eb_policy_rollout_grad.hip', 'eb_policy_rollout_grad.h', 'eb_policy_rollout_grad_device.h', public}
+    assert 'eb_policy_rollout_grad.hip' in eb_build.SOURCES and new - {'eb_policy_rollout_grad.hip'} <= set(eb_build.HEADERS)
+    for f in eb_build.SOURCES + eb_build.HEADERS:
+        assert os.path.isfile(os.path.join(eb_build.CSRC, f)), f
+    for files in eb_build.KERNEL_SOURCES.values():
+        assert not set(files) & (new | {'eb_policy_grad.hip', 'eb_policy_grad.h', 'eb_capi.hip'})
+    # the refusals need no device: the handles are checked first
+    lib.eb_last_error.restype = C.c_char_p
+    ok = C.c_int32(7)
+    assert lib.eb_policy_rollout_grad_supported(None, None, C.byref(ok)) == -1 and ok.value == 7
+    assert b'eb_policy_rollout_grad_supported: null handle' in lib.eb_last_error()
+    need = C.c_size_t(7)
+    lib.eb_policy_rollout_grad_workspace_bytes.argtypes = _capi.POLICY_ROLLOUT_GRAD_PROTOTYPES['eb_policy_rollout_grad_workspace_bytes'][1]
+    assert lib.eb_policy_rollout_grad_workspace_bytes(None, None, 4, 5, C.byref(need)) == -1 and need.value == 7
+    assert b'eb_policy_rollout_grad_workspace_bytes: null handle' in lib.eb_last_error()
+    lib.eb_policy_rollout_grad.argtypes = _capi.POLICY_ROLLOUT_GRAD_PROTOTYPES['eb_policy_rollout_grad'][1]
+    assert lib.eb_policy_rollout_grad(None, None, 4, 5, None, None, 0, 1.0, None, None, 0, *([None] * 9)) == -1
+    assert b'eb_policy_rollout_grad: null handle' in lib.eb_last_error()
+
+
+def test_the_oracle_library_is_refused_with_the_family_label_and_header():
+    api = oracle_lib()
+    assert api.backend == 'oracle'
+    header, label = _capi.LOOP_GRAD_FAMILIES['policy_rollout_grad'][:2]
+    assert header == HEADER
+    for sym in ENTRIES:
+        with pytest.raises(_capi.EbError) as e:
+            getattr(api, sym[3:])
+        assert label in str(e.value) and header in str(e.value), sym
+        for fn in (api.policy_rollout_grad_fn, lambda s: api.family_fn('policy_rollout_grad', s)):
+            with pytest.raises(_capi.EbError) as e:
+                fn(sym)
+            assert label in str(e.value) and header in str(e.value), sym
+    assert not hasattr(api.lib, 'eb_policy_rollout_grad')
+    # the other families still resolve through the tables they were in
+    with pytest.raises(_capi.EbError) as e:
+        api.mlp_backward
+    assert _capi.TRAIN_FAMILIES['mlp_grad'][1] in str(e.value)
