@@ -1,19 +1,22 @@
-// eb_policy_rollout_grad_device.h — what policy_rollout_grad_kernel (eb_policy_rollout_grad.hip) restates of eb_policy_grad.hip's
-// device code: the deterministic activations with their derivatives, mlp_kernel's layer chain on v_mfma_f32_32x32x2_f32, and the two
-// epilogues that leave x_l / d_l in LDS and in the workspace.  The text is that file's, under other names: eb_policy_grad.hip's
-// machine code does not move when this kernel changes, and the two files' bits agree because their text does
-// (tests/test_gpu_policy_rollout_grad.py holds them to each other).
+// eb_mlp_device.h — the device code every policy-network kernel shares, written once: eb_policy.hip (fp32 forward), eb_policy_grad.hip
+// (backward), eb_policy_rollout_grad.hip (closed-loop rollout with its parameter gradient) and, through eb_policy_f16_device.h,
+// eb_policy_f16.hip and eb_policy_rollout.hip (binary16); eb_rollout_tape_sample.hip takes exp_det.  The deterministic activations
+// and their derivatives, one hidden layer's k-loop on v_mfma_f32_32x32x2_f32 and the epilogues that leave a layer's outputs /
+// cotangents in LDS and in the backward's workspace.  The policy family's numerical contract is this text: fp16 and fp32 agree on
+// activation bits, the fused rollouts equal the loop of single calls bit for bit and the oracle's eb_expf / eb_tanhf match because
+// there is one definition of each function.  Everything is EB_DEV (forced inline): a translation unit's machine code depends on what
+// it calls, not on what else this header holds.
 #pragma once
-#include "eb_policy_grad.h"
+#include "eb_kernels.h"
 
 namespace eb {
-namespace prg {
+namespace mlp {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-namespace act {
-
+// ---- deterministic exp / tanh (Cephes scheme, explicit fma; oracle: eb_expf / eb_tanhf) ----
+// Written without branches (selects): the epilogue applies them to 64 accumulator values per lane and layer.
 EB_DEV float exp_det(float x0) {
     const float x = x0 > 88.0f ? 88.0f : (x0 < -87.0f ? -87.0f : x0);   // NaN falls through both compares
     const float fx = __builtin_rintf(x * 1.44269504088896341f);
@@ -48,6 +51,10 @@ EB_DEV float tanh_det(float x) {
     return ax > 44.0f ? sat : (ax >= 0.625f ? big : small);              // NaN: both compares false -> small = NaN
 }
 
+// ELU = x > 0 ? x : exp_det(x) - 1, written for the epilogue (64 values per lane and layer): only x <= 0 reaches the
+// exponential's result, so the upper clamp goes, the scaling by 2^n is one v_ldexp_f32 (exactly the multiplication by the
+// bit-built power of two, denormal results included) and a NaN needs no select — it travels through the fma chain by
+// itself (v_cvt_i32_f32 of NaN is 0).  Same bits as exp_det(x) - 1 for every x <= 0, so the oracle's eb_expf stays as it is.
 EB_DEV float elu_det(float x0) {
     const float x = x0 < -87.0f ? -87.0f : x0;
     const float fx = __builtin_rintf(x * 1.44269504088896341f);
@@ -98,14 +105,13 @@ EB_DEV float derivative_rt(int act, float y) {
     }
 }
 
-}  // namespace act
-
-// eb_policy_grad.hip's grad_layer_chain, restated: one layer's k-loop for the RT x CT tiles of a wave.  a_row: LDS address of
-// A[row tile rt0][i][h][0]; wp: packed weights (pack_weights); steps = k_pad / 8.  Fragments are fetched two steps ahead into one of
-// three register sets; the loop is unrolled by three so that the sets rotate by name.
+// One layer's k-loop for the RT x CT tiles of a wave.  a_row: LDS address of A[row tile rt0][i][h][0];
+// wp: this layer's packed weights; steps = k_pad / 8.  acc enters holding the bias.  Fragments are fetched two
+// steps ahead into one of three register sets; the loop is unrolled by three so that the sets rotate by name
+// (a register copy would make every step wait for the load it has just issued).
 template <int RT, int CT>
-EB_DEV void layer_chain(const float* a_row, int row_tile_stride, const f32x4* __restrict__ wp, int steps, int ct0, int lane,
-                             f32x16 (&acc)[RT][CT]) {
+EB_DEV void layer_chain(const float* a_row, int row_tile_stride, const f32x4* __restrict__ wp, int steps, int ct0,
+                        int lane, f32x16 (&acc)[RT][CT]) {
     const f32x4* bsrc[CT];
 #pragma unroll
     for (int c = 0; c < CT; ++c) bsrc[c] = wp + (size_t)(ct0 + c) * steps * 64 + lane;
@@ -126,6 +132,7 @@ EB_DEV void layer_chain(const float* a_row, int row_tile_stride, const f32x4* __
                 for (int c = 0; c < CT; ++c)
                     acc[r][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[set][r][q], bq[set][c][q], acc[r][c], 0, 0, 0);
     };
+    // the scheduling fences keep every fetch where it is written: two steps (32 MFMAs) ahead of its use
 #define EB_STEP(FSET, FS, RSET)                   \
     fetch(FSET, FS);                              \
     __builtin_amdgcn_sched_barrier(0);            \
@@ -145,8 +152,25 @@ EB_DEV void layer_chain(const float* a_row, int row_tile_stride, const f32x4* __
 #undef EB_STEP
 }
 
-// eb_policy.hip's store_hidden, restated, with the copy the backward needs: a layer's outputs through the activation into the LDS
-// activation buffer AND into the workspace (xg: row 0 of this block, `units` floats per row).
+// A layer's outputs back into the LDS activation buffer (its layout: eb_policy.hip, at mlp_kernel), through the activation.
+template <int RT, int CT, int ACT>
+EB_DEV void store_hidden(float* lds, int RS, int HS, int rt0, int ct0, int i, int h, const f32x16 (&acc)[RT][CT]) {
+#pragma unroll
+    for (int r = 0; r < RT; ++r)
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+            const int col = (ct0 + c) * 32 + i;
+            float* dst = lds + (col & 1) * HS + (col >> 1);
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int row = (rt0 + r) * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
+                dst[row * RS] = activate<ACT>(acc[r][c][v]);
+            }
+        }
+}
+
+// store_hidden with the copy the backward needs: a layer's outputs through the activation into the LDS activation buffer AND into
+// the workspace (xg: row 0 of this block, `units` floats per row).
 template <int RT, int CT, int ACT>
 EB_DEV void store_hidden(float* lds, int RS, int HS, int rt0, int ct0, int i, int h, const f32x16 (&acc)[RT][CT], float* xg, int units) {
 #pragma unroll
@@ -159,7 +183,7 @@ EB_DEV void store_hidden(float* lds, int RS, int HS, int rt0, int ct0, int i, in
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
                 const int urow = (rt0 + r) * 32 + (v & 3) + 8 * (v >> 2);
-                const float y = act::activate<ACT>(acc[r][c][v]);
+                const float y = activate<ACT>(acc[r][c][v]);
                 dst[(urow + 4 * h) * RS] = y;
                 (xg + (size_t)urow * units)[lane_off] = y;
             }
@@ -171,7 +195,7 @@ EB_DEV void store_hidden(float* lds, int RS, int HS, int rt0, int ct0, int i, in
 // workspace (mlp_wgrad_kernel's B operand).
 template <int RT, int CT, int ACT>
 EB_DEV void store_delta(float* lds, int RS, int HS, int rt0, int ct0, int i, int h, const f32x16 (&acc)[RT][CT], const float* xg,
-                             float* dg, int units) {
+                        float* dg, int units) {
 #pragma unroll
     for (int r = 0; r < RT; ++r)
 #pragma unroll
@@ -182,7 +206,7 @@ EB_DEV void store_delta(float* lds, int RS, int HS, int rt0, int ct0, int i, int
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
                 const int urow = (rt0 + r) * 32 + (v & 3) + 8 * (v >> 2);
-                const float d = acc[r][c][v] * act::derivative<ACT>((xg + (size_t)urow * units)[lane_off]);
+                const float d = acc[r][c][v] * derivative<ACT>((xg + (size_t)urow * units)[lane_off]);
                 dst[(urow + 4 * h) * RS] = d;
                 (dg + (size_t)urow * units)[lane_off] = d;
             }
@@ -190,5 +214,5 @@ EB_DEV void store_delta(float* lds, int RS, int HS, int rt0, int ct0, int i, int
         }
 }
 
-}  // namespace prg
+}  // namespace mlp
 }  // namespace eb

@@ -19,149 +19,11 @@
 //     tile of 16 per wave (all four waves).
 //   * widths are padded with zero weights / zero bias to the next supported U; a padded unit outputs
 //     act(0) = 0 for all four activations and meets zero weights in the next layer — exact no-ops in the chain.
-#include "eb_kernels.h"
+// The deterministic activations, the hidden layers' k-loop (layer_chain) and their epilogue (store_hidden) are in eb_mlp_device.h,
+// shared with the backward, the binary16 kernels and the closed-loop rollouts.
+#include "eb_mlp_device.h"
 
 namespace eb {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// ---- deterministic exp / tanh (Cephes scheme, explicit fma; oracle: eb_expf / eb_tanhf) ----
-// Written without branches (selects): the epilogue applies them to 64 accumulator values per lane and layer.
-EB_DEV float exp_det(float x0) {
-    const float x = x0 > 88.0f ? 88.0f : (x0 < -87.0f ? -87.0f : x0);   // NaN falls through both compares
-    const float fx = __builtin_rintf(x * 1.44269504088896341f);
-    float r = __builtin_fmaf(-fx, 0.693359375f, x);
-    r = __builtin_fmaf(-fx, -2.12194440e-4f, r);
-    const float z = r * r;
-    float p = 1.9875691500e-4f;
-    p = __builtin_fmaf(p, r, 1.3981999507e-3f);
-    p = __builtin_fmaf(p, r, 8.3334519073e-3f);
-    p = __builtin_fmaf(p, r, 4.1665795894e-2f);
-    p = __builtin_fmaf(p, r, 1.6666665459e-1f);
-    p = __builtin_fmaf(p, r, 5.0000001201e-1f);
-    const float y = __builtin_fmaf(p, z, r) + 1.0f;
-    const int n = (x0 == x0) ? (int)fx : 0;                              // -126 .. 127
-    const float v = y * __builtin_bit_cast(float, (unsigned)(n + 127) << 23);
-    return (x0 == x0) ? v : x0;
-}
-
-EB_DEV float tanh_det(float x) {
-    const float ax = __builtin_fabsf(x);
-    const float s = exp_det(ax + ax);
-    const float t = 1.0f - 2.0f / (s + 1.0f);
-    const float big = x < 0.0f ? -t : t;
-    const float z = x * x;
-    float p = -5.70498872745e-3f;
-    p = __builtin_fmaf(p, z, 2.06390887954e-2f);
-    p = __builtin_fmaf(p, z, -5.37397155531e-2f);
-    p = __builtin_fmaf(p, z, 1.33314422036e-1f);
-    p = __builtin_fmaf(p, z, -3.33332819422e-1f);
-    const float small = __builtin_fmaf(p * z, x, x);
-    const float sat = x > 0.0f ? 1.0f : -1.0f;
-    return ax > 44.0f ? sat : (ax >= 0.625f ? big : small);              // NaN: both compares false -> small = NaN
-}
-
-// ELU = x > 0 ? x : exp_det(x) - 1, written for the epilogue (64 values per lane and layer): only x <= 0 reaches the
-// exponential's result, so the upper clamp goes, the scaling by 2^n is one v_ldexp_f32 (exactly the multiplication by the
-// bit-built power of two, denormal results included) and a NaN needs no select — it travels through the fma chain by
-// itself (v_cvt_i32_f32 of NaN is 0).  Same bits as exp_det(x) - 1 for every x <= 0, so the oracle's eb_expf stays as it is.
-EB_DEV float elu_det(float x0) {
-    const float x = x0 < -87.0f ? -87.0f : x0;
-    const float fx = __builtin_rintf(x * 1.44269504088896341f);
-    float r = __builtin_fmaf(-fx, 0.693359375f, x);
-    r = __builtin_fmaf(-fx, -2.12194440e-4f, r);
-    const float z = r * r;
-    float p = 1.9875691500e-4f;
-    p = __builtin_fmaf(p, r, 1.3981999507e-3f);
-    p = __builtin_fmaf(p, r, 8.3334519073e-3f);
-    p = __builtin_fmaf(p, r, 4.1665795894e-2f);
-    p = __builtin_fmaf(p, r, 1.6666665459e-1f);
-    p = __builtin_fmaf(p, r, 5.0000001201e-1f);
-    const float y = __builtin_fmaf(p, z, r) + 1.0f;
-    const float v = __builtin_amdgcn_ldexpf(y, (int)fx);
-    return x0 > 0.0f ? x0 : v - 1.0f;
-}
-
-template <int ACT>
-EB_DEV float activate(float x) {
-    if (ACT == MLP_ACT_RELU) return x > 0.0f ? x : 0.0f;
-    if (ACT == MLP_ACT_ELU) return elu_det(x);
-    if (ACT == MLP_ACT_TANH) return tanh_det(x);
-    return x;
-}
-EB_DEV float activate_rt(int act, float x) {
-    switch (act) {
-        case MLP_ACT_RELU: return activate<MLP_ACT_RELU>(x);
-        case MLP_ACT_ELU: return activate<MLP_ACT_ELU>(x);
-        case MLP_ACT_TANH: return activate<MLP_ACT_TANH>(x);
-        default: return x;
-    }
-}
-
-// One layer's k-loop for the RT x CT tiles of a wave.  a_row: LDS address of A[row tile rt0][i][h][0];
-// wp: this layer's packed weights; steps = k_pad / 8.  acc enters holding the bias.  Fragments are fetched two
-// steps ahead into one of three register sets; the loop is unrolled by three so that the sets rotate by name
-// (a register copy would make every step wait for the load it has just issued).
-template <int RT, int CT>
-EB_DEV void layer_chain(const float* a_row, int row_tile_stride, const f32x4* __restrict__ wp, int steps, int ct0,
-                        int lane, f32x16 (&acc)[RT][CT]) {
-    const f32x4* bsrc[CT];
-#pragma unroll
-    for (int c = 0; c < CT; ++c) bsrc[c] = wp + (size_t)(ct0 + c) * steps * 64 + lane;
-    f32x4 bq[3][CT], aq[3][RT];
-    auto fetch = [&](int set, int s) {
-        const int sc = s < steps ? s : steps - 1;
-#pragma unroll
-        for (int c = 0; c < CT; ++c) bq[set][c] = bsrc[c][(size_t)sc * 64];
-#pragma unroll
-        for (int r = 0; r < RT; ++r) aq[set][r] = *reinterpret_cast<const f32x4*>(a_row + r * row_tile_stride + sc * 4);
-    };
-    auto run = [&](int set) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)                                                          // k pairs in order
-#pragma unroll
-            for (int r = 0; r < RT; ++r)
-#pragma unroll
-                for (int c = 0; c < CT; ++c)
-                    acc[r][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[set][r][q], bq[set][c][q], acc[r][c], 0, 0, 0);
-    };
-    // the scheduling fences keep every fetch where it is written: two steps (32 MFMAs) ahead of its use
-#define EB_STEP(FSET, FS, RSET)                   \
-    fetch(FSET, FS);                              \
-    __builtin_amdgcn_sched_barrier(0);            \
-    run(RSET);                                    \
-    __builtin_amdgcn_sched_barrier(0)
-    fetch(0, 0);
-    fetch(1, 1);
-    __builtin_amdgcn_sched_barrier(0);
-    int s = 0;
-    for (; s + 3 <= steps; s += 3) {
-        EB_STEP(2, s + 2, 0);
-        EB_STEP(0, s + 3, 1);
-        EB_STEP(1, s + 4, 2);
-    }
-    if (s < steps) { EB_STEP(2, s + 2, 0); }
-    if (s + 1 < steps) run(1);
-#undef EB_STEP
-}
-
-// A layer's outputs back into the LDS activation buffer (the layout below), through the activation.
-template <int RT, int CT, int ACT>
-EB_DEV void store_hidden(float* lds, int RS, int HS, int rt0, int ct0, int i, int h, const f32x16 (&acc)[RT][CT]) {
-#pragma unroll
-    for (int r = 0; r < RT; ++r)
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            const int col = (ct0 + c) * 32 + i;
-            float* dst = lds + (col & 1) * HS + (col >> 1);
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int row = (rt0 + r) * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
-                dst[row * RS] = activate<ACT>(acc[r][c][v]);
-            }
-        }
-}
 
 // LDS layout of the activations: element (row i, input k) at i * RS + (k & 1) * HS + (k >> 1); RS = Kmax + 4
 // floats (the pad spreads the 32 rows of a fragment read over all banks), HS = Kmax / 2.
@@ -212,7 +74,7 @@ __global__ __launch_bounds__(MLP_THREADS, CT == 4 ? 1 : 2) void mlp_kernel(const
     const int ct0 = RT == 2 ? wave * CT : (wave >> 1);
     for (int L = 0; L < A.n_hidden; ++L) {
         const MlpLayer& ly = A.hid[L];
-        f32x16 acc[RT][CT];
+        mlp::f32x16 acc[RT][CT];
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
             const float b = ly.b[(ct0 + c) * 32 + i];
@@ -221,14 +83,14 @@ __global__ __launch_bounds__(MLP_THREADS, CT == 4 ? 1 : 2) void mlp_kernel(const
 #pragma unroll
                 for (int v = 0; v < 16; ++v) acc[r][c][v] = b;
         }
-        layer_chain<RT, CT>(lds + (rt0 * 32 + i) * RS + h * HS, 32 * RS, reinterpret_cast<const f32x4*>(ly.w),
+        mlp::layer_chain<RT, CT>(lds + (rt0 * 32 + i) * RS + h * HS, 32 * RS, reinterpret_cast<const mlp::f32x4*>(ly.w),
                             ly.k_pad >> 3, ct0, lane, acc);
         __syncthreads();                                              // every wave has read this layer's inputs
         switch (A.hidden_act) {
-            case MLP_ACT_RELU: store_hidden<RT, CT, MLP_ACT_RELU>(lds, RS, HS, rt0, ct0, i, h, acc); break;
-            case MLP_ACT_ELU: store_hidden<RT, CT, MLP_ACT_ELU>(lds, RS, HS, rt0, ct0, i, h, acc); break;
-            case MLP_ACT_TANH: store_hidden<RT, CT, MLP_ACT_TANH>(lds, RS, HS, rt0, ct0, i, h, acc); break;
-            default: store_hidden<RT, CT, MLP_ACT_LINEAR>(lds, RS, HS, rt0, ct0, i, h, acc); break;
+            case MLP_ACT_RELU: mlp::store_hidden<RT, CT, MLP_ACT_RELU>(lds, RS, HS, rt0, ct0, i, h, acc); break;
+            case MLP_ACT_ELU: mlp::store_hidden<RT, CT, MLP_ACT_ELU>(lds, RS, HS, rt0, ct0, i, h, acc); break;
+            case MLP_ACT_TANH: mlp::store_hidden<RT, CT, MLP_ACT_TANH>(lds, RS, HS, rt0, ct0, i, h, acc); break;
+            default: mlp::store_hidden<RT, CT, MLP_ACT_LINEAR>(lds, RS, HS, rt0, ct0, i, h, acc); break;
         }
         __syncthreads();
     }
@@ -241,17 +103,17 @@ __global__ __launch_bounds__(MLP_THREADS, CT == 4 ? 1 : 2) void mlp_kernel(const
         const int i16 = lane & 15, kq = lane >> 4, hsel = kq >> 1;
         const int steps4 = A.outl.k_pad >> 4;                               // groups of four MFMAs (16 inputs)
         const float* a_ptr = lds + (wave * 16 + i16) * RS + (kq & 1) * HS;  // element (k >> 1) = m of this lane's parity at a_ptr[m]
-        const f32x4* w16 = reinterpret_cast<const f32x4*>(A.outl.w);
+        const mlp::f32x4* w16 = reinterpret_cast<const mlp::f32x4*>(A.outl.w);
         const int ct16 = (A.out_dim + 15) >> 4;
         for (int ct = 0; ct < ct16; ++ct) {
             const float b = A.outl.b[ct * 16 + i16];
-            f32x4 acc = {b, b, b, b};
-            const f32x4* wsrc = w16 + (size_t)ct * steps4 * 64 + lane;
-            f32x4 bq = wsrc[0];
+            mlp::f32x4 acc = {b, b, b, b};
+            const mlp::f32x4* wsrc = w16 + (size_t)ct * steps4 * 64 + lane;
+            mlp::f32x4 bq = wsrc[0];
             for (int s4 = 0; s4 < steps4; ++s4) {
-                const f32x4 bn = wsrc[(size_t)(s4 + 1 < steps4 ? s4 + 1 : s4) * 64];      // the next group's weights under these MFMAs
-                const f32x4 a01 = *reinterpret_cast<const f32x4*>(a_ptr + 8 * s4);
-                const f32x4 a23 = *reinterpret_cast<const f32x4*>(a_ptr + 8 * s4 + 4);
+                const mlp::f32x4 bn = wsrc[(size_t)(s4 + 1 < steps4 ? s4 + 1 : s4) * 64];      // the next group's weights under these MFMAs
+                const mlp::f32x4 a01 = *reinterpret_cast<const mlp::f32x4*>(a_ptr + 8 * s4);
+                const mlp::f32x4 a23 = *reinterpret_cast<const mlp::f32x4*>(a_ptr + 8 * s4 + 4);
                 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(hsel ? a01[1] : a01[0], bq[0], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(hsel ? a01[3] : a01[2], bq[1], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(hsel ? a23[1] : a23[0], bq[2], acc, 0, 0, 0);
@@ -264,7 +126,7 @@ __global__ __launch_bounds__(MLP_THREADS, CT == 4 ? 1 : 2) void mlp_kernel(const
 #pragma unroll
                     for (int v = 0; v < 4; ++v) {
                         const int row = wave * 16 + 4 * kq + v;
-                        if (row < rows_here) A.out[(size_t)(row0 + row) * A.out_dim + col] = activate_rt(A.out_act, acc[v]);
+                        if (row < rows_here) A.out[(size_t)(row0 + row) * A.out_dim + col] = mlp::activate_rt(A.out_act, acc[v]);
                     }
                 }
             } else {   // deterministic action: action_range * tanh(mean), utils/policy.py:89-92
@@ -273,9 +135,9 @@ __global__ __launch_bounds__(MLP_THREADS, CT == 4 ? 1 : 2) void mlp_kernel(const
 #pragma unroll
                     for (int v = 0; v < 4; ++v) {
                         const int row = wave * 16 + 4 * kq + v;
-                        const float mean = activate_rt(A.out_act, acc[v]);
+                        const float mean = mlp::activate_rt(A.out_act, acc[v]);
                         if (row < rows_here)
-                            A.out[(size_t)(row0 + row) * act_dim + col] = A.action_range > 0.0f ? A.action_range * tanh_det(mean) : mean;
+                            A.out[(size_t)(row0 + row) * act_dim + col] = A.action_range > 0.0f ? A.action_range * mlp::tanh_det(mean) : mean;
                     }
                 }
             }

@@ -14,8 +14,9 @@
 //     packing (pack_weights_f16); the result D[unit (v & 3) + 8 (v >> 2) + 4 (l >> 5)][observation l & 31] puts FOUR consecutive units
 //     of one observation in a lane's registers 4g .. 4g+3: the epilogue packs them and writes 8 bytes, where the untransposed product
 //     would write 2.
-//   * the bias is the accumulator's initial value; the epilogue applies the activation in fp32, converts with round-to-nearest-even
-//     (v_cvt_f16_f32 under the default mode) and writes back once every wave has read its inputs.
+//   * the bias is the accumulator's initial value; the epilogue applies the activation in fp32 (eb_mlp_device.h's, the one
+//     eb_policy.hip applies), converts with round-to-nearest-even (v_cvt_f16_f32 under the default mode) and writes back once every
+//     wave has read its inputs.
 //   * widths are padded with zero weights / zero bias to the next supported U, k to 16.  A padded unit is WRITTEN as zero whatever
 //     its accumulator holds (an inf or NaN input times a zero weight is NaN), so a row's non-finite pattern is that of the unpadded
 //     network.
@@ -77,13 +78,13 @@ __global__ __launch_bounds__(MLP_THREADS, CT == 4 ? 1 : 2) void mlp_f16_kernel(c
     const int ct0 = RT == 2 ? wave * CT : (wave >> 1);
     for (int L = 0; L < A.n_hidden; ++L) {
         const MlpF16Layer& ly = A.hid[L];
-        f32x16 acc[RT][CT];
+        mlp::f32x16 acc[RT][CT];
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
-            const f32x4* bsrc = reinterpret_cast<const f32x4*>(ly.b + (ct0 + c) * 32 + 4 * h);   // units 8 g + 4 h + e
+            const mlp::f32x4* bsrc = reinterpret_cast<const mlp::f32x4*>(ly.b + (ct0 + c) * 32 + 4 * h);   // units 8 g + 4 h + e
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const f32x4 b = bsrc[2 * g];
+                const mlp::f32x4 b = bsrc[2 * g];
 #pragma unroll
                 for (int r = 0; r < RT; ++r)
 #pragma unroll
@@ -113,7 +114,7 @@ __global__ __launch_bounds__(MLP_THREADS, CT == 4 ? 1 : 2) void mlp_f16_kernel(c
         const int ct16 = (A.out_dim + 15) >> 4;
         for (int ct = 0; ct < ct16; ++ct) {
             const float b = A.outl.b[ct * 16 + i16];
-            f32x4 acc = {b, b, b, b};
+            mlp::f32x4 acc = {b, b, b, b};
             const f16x8* wsrc = w16 + (size_t)ct * steps * 64 + lane;
             f16x8 bq = wsrc[0];
             for (int s = 0; s < steps; ++s) {
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(MLP_THREADS, CT == 4 ? 1 : 2) void mlp_f16_kernel(c
 #pragma unroll
                     for (int v = 0; v < 4; ++v) {
                         const int row = wave * 16 + 4 * kq + v;
-                        if (row < rows_here) A.out[(size_t)(row0 + row) * A.out_dim + col] = f16act::activate_rt(A.out_act, acc[v]);
+                        if (row < rows_here) A.out[(size_t)(row0 + row) * A.out_dim + col] = mlp::activate_rt(A.out_act, acc[v]);
                     }
                 }
             } else {   // deterministic action: action_range * tanh(mean), utils/policy.py:89-92
@@ -137,9 +138,9 @@ __global__ __launch_bounds__(MLP_THREADS, CT == 4 ? 1 : 2) void mlp_f16_kernel(c
 #pragma unroll
                     for (int v = 0; v < 4; ++v) {
                         const int row = wave * 16 + 4 * kq + v;
-                        const float mean = f16act::activate_rt(A.out_act, acc[v]);
+                        const float mean = mlp::activate_rt(A.out_act, acc[v]);
                         if (row < rows_here)
-                            A.out[(size_t)(row0 + row) * act_dim + col] = A.action_range > 0.0f ? A.action_range * f16act::tanh_det(mean) : mean;
+                            A.out[(size_t)(row0 + row) * act_dim + col] = A.action_range > 0.0f ? A.action_range * mlp::tanh_det(mean) : mean;
                     }
                 }
             }

@@ -1,87 +1,16 @@
 // eb_policy_f16_device.h — the device code the binary16 policy kernels share: eb_policy_f16.hip (one policy evaluation per launch) and
-// eb_policy_rollout.hip (the policy inside the closed-loop rollout).  The vector types, the deterministic activations, one hidden
-// layer's k-loop on v_mfma_f32_32x32x16_f16 and its epilogue — one text, so one order of every sum in both kernels
+// eb_policy_rollout.hip (the policy inside the closed-loop rollout).  The binary16 vector types, one hidden layer's k-loop
+// on v_mfma_f32_32x32x16_f16 and its epilogue — one text, so one order of every sum in both kernels; the fp32 vector types and the
+// deterministic activations are eb_mlp_device.h's, the ones the fp32 kernels apply
 // (include/envbuild_mlp_f16.h states the arithmetic; the layout notes are at the top of eb_policy_f16.hip).
 #pragma once
+#include "eb_mlp_device.h"
 #include "eb_policy_f16.h"
 
 namespace eb {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
-// ---- the deterministic activations of eb_policy.hip, restated (that file's machine code is pinned; same bits for every input) ----
-namespace f16act {
-EB_DEV float exp_det(float x0) {
-    const float x = x0 > 88.0f ? 88.0f : (x0 < -87.0f ? -87.0f : x0);   // NaN falls through both compares
-    const float fx = __builtin_rintf(x * 1.44269504088896341f);
-    float r = __builtin_fmaf(-fx, 0.693359375f, x);
-    r = __builtin_fmaf(-fx, -2.12194440e-4f, r);
-    const float z = r * r;
-    float p = 1.9875691500e-4f;
-    p = __builtin_fmaf(p, r, 1.3981999507e-3f);
-    p = __builtin_fmaf(p, r, 8.3334519073e-3f);
-    p = __builtin_fmaf(p, r, 4.1665795894e-2f);
-    p = __builtin_fmaf(p, r, 1.6666665459e-1f);
-    p = __builtin_fmaf(p, r, 5.0000001201e-1f);
-    const float y = __builtin_fmaf(p, z, r) + 1.0f;
-    const int n = (x0 == x0) ? (int)fx : 0;                              // -126 .. 127
-    const float v = y * __builtin_bit_cast(float, (unsigned)(n + 127) << 23);
-    return (x0 == x0) ? v : x0;
-}
-
-EB_DEV float tanh_det(float x) {
-    const float ax = __builtin_fabsf(x);
-    const float s = exp_det(ax + ax);
-    const float t = 1.0f - 2.0f / (s + 1.0f);
-    const float big = x < 0.0f ? -t : t;
-    const float z = x * x;
-    float p = -5.70498872745e-3f;
-    p = __builtin_fmaf(p, z, 2.06390887954e-2f);
-    p = __builtin_fmaf(p, z, -5.37397155531e-2f);
-    p = __builtin_fmaf(p, z, 1.33314422036e-1f);
-    p = __builtin_fmaf(p, z, -3.33332819422e-1f);
-    const float small = __builtin_fmaf(p * z, x, x);
-    const float sat = x > 0.0f ? 1.0f : -1.0f;
-    return ax > 44.0f ? sat : (ax >= 0.625f ? big : small);              // NaN: both compares false -> small = NaN
-}
-
-// x > 0 ? x : exp_det(x) - 1 (eb_policy.hip:elu_det: the same bits for every x <= 0)
-EB_DEV float elu_det(float x0) {
-    const float x = x0 < -87.0f ? -87.0f : x0;
-    const float fx = __builtin_rintf(x * 1.44269504088896341f);
-    float r = __builtin_fmaf(-fx, 0.693359375f, x);
-    r = __builtin_fmaf(-fx, -2.12194440e-4f, r);
-    const float z = r * r;
-    float p = 1.9875691500e-4f;
-    p = __builtin_fmaf(p, r, 1.3981999507e-3f);
-    p = __builtin_fmaf(p, r, 8.3334519073e-3f);
-    p = __builtin_fmaf(p, r, 4.1665795894e-2f);
-    p = __builtin_fmaf(p, r, 1.6666665459e-1f);
-    p = __builtin_fmaf(p, r, 5.0000001201e-1f);
-    const float y = __builtin_fmaf(p, z, r) + 1.0f;
-    const float v = __builtin_amdgcn_ldexpf(y, (int)fx);
-    return x0 > 0.0f ? x0 : v - 1.0f;
-}
-
-template <int ACT>
-EB_DEV float activate(float x) {
-    if (ACT == MLP_ACT_RELU) return x > 0.0f ? x : 0.0f;
-    if (ACT == MLP_ACT_ELU) return elu_det(x);
-    if (ACT == MLP_ACT_TANH) return tanh_det(x);
-    return x;
-}
-EB_DEV float activate_rt(int act, float x) {
-    switch (act) {
-        case MLP_ACT_RELU: return activate<MLP_ACT_RELU>(x);
-        case MLP_ACT_ELU: return activate<MLP_ACT_ELU>(x);
-        case MLP_ACT_TANH: return activate<MLP_ACT_TANH>(x);
-        default: return x;
-    }
-}
-}  // namespace f16act
 
 // One layer's k-loop for the RT (observation) x CT (unit) tiles of a wave.  x_row: LDS address of X[row tile rt0][i][8 h]; wp: this
 // layer's packed weights; steps = k_pad / 16.  acc enters holding the bias.  The loop moves in groups of four steps (64 inputs: 4 RT CT
@@ -89,7 +18,7 @@ EB_DEV float activate_rt(int act, float x) {
 // the last step re-read it (valid memory, never used).
 template <int RT, int CT>
 EB_DEV void layer_chain_f16(const _Float16* x_row, int row_tile_stride, const f16x8* __restrict__ wp, int steps, int ct0, int lane,
-                            f32x16 (&acc)[RT][CT]) {
+                            mlp::f32x16 (&acc)[RT][CT]) {
     const f16x8* wsrc[CT];
 #pragma unroll
     for (int c = 0; c < CT; ++c) wsrc[c] = wp + (size_t)(ct0 + c) * steps * 64 + lane;
@@ -142,7 +71,7 @@ EB_DEV void layer_chain_f16(const _Float16* x_row, int row_tile_stride, const f1
 
 // A layer's outputs back into the LDS activation buffer as binary16, through the activation; units at and beyond n_units are zero.
 template <int RT, int CT, int ACT>
-EB_DEV void store_hidden_f16(_Float16* lds, int RS, int rt0, int ct0, int i, int h, int n_units, const f32x16 (&acc)[RT][CT]) {
+EB_DEV void store_hidden_f16(_Float16* lds, int RS, int rt0, int ct0, int i, int h, int n_units, const mlp::f32x16 (&acc)[RT][CT]) {
 #pragma unroll
     for (int r = 0; r < RT; ++r)
 #pragma unroll
@@ -154,7 +83,7 @@ EB_DEV void store_hidden_f16(_Float16* lds, int RS, int rt0, int ct0, int i, int
                 f16x4 p;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float a = f16act::activate<ACT>(acc[r][c][4 * g + e]);
+                    const float a = mlp::activate<ACT>(acc[r][c][4 * g + e]);
                     p[e] = (_Float16)(u0 + 8 * g + e < n_units ? a : 0.0f);                  // round to nearest even, overflow to inf
                 }
                 *reinterpret_cast<f16x4*>(dst + 8 * g) = p;

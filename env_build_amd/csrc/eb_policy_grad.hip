@@ -6,8 +6,8 @@
 //     binary16 packings of eb_policy_f16.hip, the padded biases and the transposed packing below) filled from ONE flat device buffer
 //     in Model.get_weights() order.  One launch, no host copy.
 //   * mlp_bwd_data_kernel<RT, CT> — one block = 64 rows x 4 waves with the forward's tiling (eb_policy.hip: U = 64 / 128 / 256).  The
-//     forward is recomputed with mlp_kernel's own chain (layer_chain / store_hidden restated below: bias in the accumulator, products
-//     added in ascending k), so `out` has eb_mlp_forward's bits; every x_l goes to the workspace.  Then the chain runs backwards: the
+//     forward is recomputed with mlp_kernel's own chain (layer_chain / store_hidden of eb_mlp_device.h: bias in the accumulator,
+//     products added in ascending k), so `out` has eb_mlp_forward's bits; every x_l goes to the workspace.  Then the chain runs backwards: the
 //     cotangent d_l sits in LDS in the activation layout as the A operand, the B operand is pack_weights applied to W_l TRANSPOSED
 //     (the handle's d_wt[]), the accumulator starts at zero and the epilogue multiplies by the activation's derivative taken from the
 //     activation's OUTPUT, which the same lane wrote to the workspace on the way forward (the tiling of both passes is the same, so a
@@ -21,188 +21,9 @@
 //     Same inputs, same bits: the order of every sum is fixed by the launch geometry, which depends on n and the handle only.
 #include "eb_policy_grad.h"
 
+#include "eb_mlp_device.h"
+
 namespace eb {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-namespace gradact {   // eb_policy.hip's deterministic exp / tanh / elu, restated (this file shares no translation unit with it)
-
-EB_DEV float exp_det(float x0) {
-    const float x = x0 > 88.0f ? 88.0f : (x0 < -87.0f ? -87.0f : x0);   // NaN falls through both compares
-    const float fx = __builtin_rintf(x * 1.44269504088896341f);
-    float r = __builtin_fmaf(-fx, 0.693359375f, x);
-    r = __builtin_fmaf(-fx, -2.12194440e-4f, r);
-    const float z = r * r;
-    float p = 1.9875691500e-4f;
-    p = __builtin_fmaf(p, r, 1.3981999507e-3f);
-    p = __builtin_fmaf(p, r, 8.3334519073e-3f);
-    p = __builtin_fmaf(p, r, 4.1665795894e-2f);
-    p = __builtin_fmaf(p, r, 1.6666665459e-1f);
-    p = __builtin_fmaf(p, r, 5.0000001201e-1f);
-    const float y = __builtin_fmaf(p, z, r) + 1.0f;
-    const int n = (x0 == x0) ? (int)fx : 0;                              // -126 .. 127
-    const float v = y * __builtin_bit_cast(float, (unsigned)(n + 127) << 23);
-    return (x0 == x0) ? v : x0;
-}
-
-EB_DEV float tanh_det(float x) {
-    const float ax = __builtin_fabsf(x);
-    const float s = exp_det(ax + ax);
-    const float t = 1.0f - 2.0f / (s + 1.0f);
-    const float big = x < 0.0f ? -t : t;
-    const float z = x * x;
-    float p = -5.70498872745e-3f;
-    p = __builtin_fmaf(p, z, 2.06390887954e-2f);
-    p = __builtin_fmaf(p, z, -5.37397155531e-2f);
-    p = __builtin_fmaf(p, z, 1.33314422036e-1f);
-    p = __builtin_fmaf(p, z, -3.33332819422e-1f);
-    const float small = __builtin_fmaf(p * z, x, x);
-    const float sat = x > 0.0f ? 1.0f : -1.0f;
-    return ax > 44.0f ? sat : (ax >= 0.625f ? big : small);              // NaN: both compares false -> small = NaN
-}
-
-EB_DEV float elu_det(float x0) {
-    const float x = x0 < -87.0f ? -87.0f : x0;
-    const float fx = __builtin_rintf(x * 1.44269504088896341f);
-    float r = __builtin_fmaf(-fx, 0.693359375f, x);
-    r = __builtin_fmaf(-fx, -2.12194440e-4f, r);
-    const float z = r * r;
-    float p = 1.9875691500e-4f;
-    p = __builtin_fmaf(p, r, 1.3981999507e-3f);
-    p = __builtin_fmaf(p, r, 8.3334519073e-3f);
-    p = __builtin_fmaf(p, r, 4.1665795894e-2f);
-    p = __builtin_fmaf(p, r, 1.6666665459e-1f);
-    p = __builtin_fmaf(p, r, 5.0000001201e-1f);
-    const float y = __builtin_fmaf(p, z, r) + 1.0f;
-    const float v = __builtin_amdgcn_ldexpf(y, (int)fx);
-    return x0 > 0.0f ? x0 : v - 1.0f;
-}
-
-template <int ACT>
-EB_DEV float activate(float x) {
-    if (ACT == MLP_ACT_RELU) return x > 0.0f ? x : 0.0f;
-    if (ACT == MLP_ACT_ELU) return elu_det(x);
-    if (ACT == MLP_ACT_TANH) return tanh_det(x);
-    return x;
-}
-EB_DEV float activate_rt(int act, float x) {
-    switch (act) {
-        case MLP_ACT_RELU: return activate<MLP_ACT_RELU>(x);
-        case MLP_ACT_ELU: return activate<MLP_ACT_ELU>(x);
-        case MLP_ACT_TANH: return activate<MLP_ACT_TANH>(x);
-        default: return x;
-    }
-}
-
-// the derivative of an activation from its OUTPUT y, one fp32 operation each (include/envbuild_mlp_grad.h)
-template <int ACT>
-EB_DEV float derivative(float y) {
-    if (ACT == MLP_ACT_RELU) return y > 0.0f ? 1.0f : 0.0f;
-    if (ACT == MLP_ACT_ELU) return y > 0.0f ? 1.0f : y + 1.0f;
-    if (ACT == MLP_ACT_TANH) return 1.0f - y * y;
-    return 1.0f;
-}
-EB_DEV float derivative_rt(int act, float y) {
-    switch (act) {
-        case MLP_ACT_RELU: return derivative<MLP_ACT_RELU>(y);
-        case MLP_ACT_ELU: return derivative<MLP_ACT_ELU>(y);
-        case MLP_ACT_TANH: return derivative<MLP_ACT_TANH>(y);
-        default: return 1.0f;
-    }
-}
-
-}  // namespace gradact
-
-// eb_policy.hip's layer_chain, restated: one layer's k-loop for the RT x CT tiles of a wave.  a_row: LDS address of
-// A[row tile rt0][i][h][0]; wp: packed weights (pack_weights); steps = k_pad / 8.  Fragments are fetched two steps ahead into one of
-// three register sets; the loop is unrolled by three so that the sets rotate by name.
-template <int RT, int CT>
-EB_DEV void grad_layer_chain(const float* a_row, int row_tile_stride, const f32x4* __restrict__ wp, int steps, int ct0, int lane,
-                             f32x16 (&acc)[RT][CT]) {
-    const f32x4* bsrc[CT];
-#pragma unroll
-    for (int c = 0; c < CT; ++c) bsrc[c] = wp + (size_t)(ct0 + c) * steps * 64 + lane;
-    f32x4 bq[3][CT], aq[3][RT];
-    auto fetch = [&](int set, int s) {
-        const int sc = s < steps ? s : steps - 1;
-#pragma unroll
-        for (int c = 0; c < CT; ++c) bq[set][c] = bsrc[c][(size_t)sc * 64];
-#pragma unroll
-        for (int r = 0; r < RT; ++r) aq[set][r] = *reinterpret_cast<const f32x4*>(a_row + r * row_tile_stride + sc * 4);
-    };
-    auto run = [&](int set) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)                                                          // k pairs in order
-#pragma unroll
-            for (int r = 0; r < RT; ++r)
-#pragma unroll
-                for (int c = 0; c < CT; ++c)
-                    acc[r][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[set][r][q], bq[set][c][q], acc[r][c], 0, 0, 0);
-    };
-#define EB_STEP(FSET, FS, RSET)                   \
-    fetch(FSET, FS);                              \
-    __builtin_amdgcn_sched_barrier(0);            \
-    run(RSET);                                    \
-    __builtin_amdgcn_sched_barrier(0)
-    fetch(0, 0);
-    fetch(1, 1);
-    __builtin_amdgcn_sched_barrier(0);
-    int s = 0;
-    for (; s + 3 <= steps; s += 3) {
-        EB_STEP(2, s + 2, 0);
-        EB_STEP(0, s + 3, 1);
-        EB_STEP(1, s + 4, 2);
-    }
-    if (s < steps) { EB_STEP(2, s + 2, 0); }
-    if (s + 1 < steps) run(1);
-#undef EB_STEP
-}
-
-// eb_policy.hip's store_hidden, restated, with the copy the backward needs: a layer's outputs through the activation into the LDS
-// activation buffer AND into the workspace (xg: row 0 of this block, `units` floats per row).
-template <int RT, int CT, int ACT>
-EB_DEV void grad_store_hidden(float* lds, int RS, int HS, int rt0, int ct0, int i, int h, const f32x16 (&acc)[RT][CT], float* xg, int units) {
-#pragma unroll
-    for (int r = 0; r < RT; ++r)
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            const int col = (ct0 + c) * 32 + i;
-            float* dst = lds + (col & 1) * HS + (col >> 1);
-            const int lane_off = 4 * h * units + col;                   // the lane's part of the address; the rest is wave-uniform
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int urow = (rt0 + r) * 32 + (v & 3) + 8 * (v >> 2);
-                const float y = gradact::activate<ACT>(acc[r][c][v]);
-                dst[(urow + 4 * h) * RS] = y;
-                (xg + (size_t)urow * units)[lane_off] = y;
-            }
-        }
-}
-
-// The backward epilogue of a hidden layer: cotangent of the layer's outputs (the accumulators) times the derivative from the outputs
-// the same lane stored on the way forward -> the cotangent of its pre-activations, into LDS (the next product's A operand) and the
-// workspace (mlp_wgrad_kernel's B operand).
-template <int RT, int CT, int ACT>
-EB_DEV void grad_store_delta(float* lds, int RS, int HS, int rt0, int ct0, int i, int h, const f32x16 (&acc)[RT][CT], const float* xg,
-                             float* dg, int units) {
-#pragma unroll
-    for (int r = 0; r < RT; ++r)
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            const int col = (ct0 + c) * 32 + i;
-            float* dst = lds + (col & 1) * HS + (col >> 1);
-            const int lane_off = 4 * h * units + col;                   // the lane's part of the address; the rest is wave-uniform
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int urow = (rt0 + r) * 32 + (v & 3) + 8 * (v >> 2);
-                const float d = acc[r][c][v] * gradact::derivative<ACT>((xg + (size_t)urow * units)[lane_off]);
-                dst[(urow + 4 * h) * RS] = d;
-                (dg + (size_t)urow * units)[lane_off] = d;
-            }
-            __builtin_amdgcn_sched_barrier(0);                           // one tile's sixteen loads in flight, not every tile's
-        }
-}
 
 // LDS layout of the activations and of the cotangents: element (row i, input k) at i * RS + (k & 1) * HS + (k >> 1); RS = Kmax + 4
 // floats, HS = Kmax / 2 (eb_policy.hip).
@@ -258,7 +79,7 @@ __global__ __launch_bounds__(MLP_THREADS, 2) void mlp_bwd_data_kernel(const MlpG
     const float* a_row = lds + (rt0 * 32 + i) * RS + h * HS;
     for (int L = 0; L < H; ++L) {
         const MlpLayer& ly = A.hid[L];
-        f32x16 acc[RT][CT];
+        mlp::f32x16 acc[RT][CT];
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
             const float b = ly.b[(ct0 + c) * 32 + i];
@@ -267,14 +88,14 @@ __global__ __launch_bounds__(MLP_THREADS, 2) void mlp_bwd_data_kernel(const MlpG
 #pragma unroll
                 for (int v = 0; v < 16; ++v) acc[r][c][v] = b;
         }
-        grad_layer_chain<RT, CT>(a_row, 32 * RS, reinterpret_cast<const f32x4*>(ly.w), ly.k_pad >> 3, ct0, lane, acc);
+        mlp::layer_chain<RT, CT>(a_row, 32 * RS, reinterpret_cast<const mlp::f32x4*>(ly.w), ly.k_pad >> 3, ct0, lane, acc);
         __syncthreads();                                              // every wave has read this layer's inputs
         float* xg = G.ws + G.x_off[L + 1] + (size_t)row0 * U;
         switch (A.hidden_act) {
-            case MLP_ACT_RELU: grad_store_hidden<RT, CT, MLP_ACT_RELU>(lds, RS, HS, rt0, ct0, i, h, acc, xg, U); break;
-            case MLP_ACT_ELU: grad_store_hidden<RT, CT, MLP_ACT_ELU>(lds, RS, HS, rt0, ct0, i, h, acc, xg, U); break;
-            case MLP_ACT_TANH: grad_store_hidden<RT, CT, MLP_ACT_TANH>(lds, RS, HS, rt0, ct0, i, h, acc, xg, U); break;
-            default: grad_store_hidden<RT, CT, MLP_ACT_LINEAR>(lds, RS, HS, rt0, ct0, i, h, acc, xg, U); break;
+            case MLP_ACT_RELU: mlp::store_hidden<RT, CT, MLP_ACT_RELU>(lds, RS, HS, rt0, ct0, i, h, acc, xg, U); break;
+            case MLP_ACT_ELU: mlp::store_hidden<RT, CT, MLP_ACT_ELU>(lds, RS, HS, rt0, ct0, i, h, acc, xg, U); break;
+            case MLP_ACT_TANH: mlp::store_hidden<RT, CT, MLP_ACT_TANH>(lds, RS, HS, rt0, ct0, i, h, acc, xg, U); break;
+            default: mlp::store_hidden<RT, CT, MLP_ACT_LINEAR>(lds, RS, HS, rt0, ct0, i, h, acc, xg, U); break;
         }
         __syncthreads();
     }
@@ -285,7 +106,7 @@ __global__ __launch_bounds__(MLP_THREADS, 2) void mlp_bwd_data_kernel(const MlpG
         const int i16 = lane & 15, kq = lane >> 4, hsel = kq >> 1;
         const int steps4 = A.outl.k_pad >> 4;
         const float* a_ptr = lds + (wave * 16 + i16) * RS + (kq & 1) * HS;
-        const f32x4* w16 = reinterpret_cast<const f32x4*>(A.outl.w);
+        const mlp::f32x4* w16 = reinterpret_cast<const mlp::f32x4*>(A.outl.w);
         const int ct16 = (A.out_dim + 15) >> 4;
         const int act_dim = A.out_dim >> 1;
 #pragma unroll
@@ -294,13 +115,13 @@ __global__ __launch_bounds__(MLP_THREADS, 2) void mlp_bwd_data_kernel(const MlpG
             for (int v = 0; v < 4; ++v) dl[ct][v] = 0.0f;
             if (ct < ct16) {
                 const float b = A.outl.b[ct * 16 + i16];
-                f32x4 acc = {b, b, b, b};
-                const f32x4* wsrc = w16 + (size_t)ct * steps4 * 64 + lane;
-                f32x4 bq = wsrc[0];
+                mlp::f32x4 acc = {b, b, b, b};
+                const mlp::f32x4* wsrc = w16 + (size_t)ct * steps4 * 64 + lane;
+                mlp::f32x4 bq = wsrc[0];
                 for (int s4 = 0; s4 < steps4; ++s4) {
-                    const f32x4 bn = wsrc[(size_t)(s4 + 1 < steps4 ? s4 + 1 : s4) * 64];
-                    const f32x4 a01 = *reinterpret_cast<const f32x4*>(a_ptr + 8 * s4);
-                    const f32x4 a23 = *reinterpret_cast<const f32x4*>(a_ptr + 8 * s4 + 4);
+                    const mlp::f32x4 bn = wsrc[(size_t)(s4 + 1 < steps4 ? s4 + 1 : s4) * 64];
+                    const mlp::f32x4 a01 = *reinterpret_cast<const mlp::f32x4*>(a_ptr + 8 * s4);
+                    const mlp::f32x4 a23 = *reinterpret_cast<const mlp::f32x4*>(a_ptr + 8 * s4 + 4);
                     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(hsel ? a01[1] : a01[0], bq[0], acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(hsel ? a01[3] : a01[2], bq[1], acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(hsel ? a23[1] : a23[0], bq[2], acc, 0, 0, 0);
@@ -313,15 +134,15 @@ __global__ __launch_bounds__(MLP_THREADS, 2) void mlp_bwd_data_kernel(const MlpG
                 for (int v = 0; v < 4; ++v) {
                     const int row = wave * 16 + 4 * kq + v;
                     const bool live = row < rows_here && col < gcols;
-                    const float y = gradact::activate_rt(A.out_act, acc[v]);
+                    const float y = mlp::activate_rt(A.out_act, acc[v]);
                     const float g = live ? G.g_out[(size_t)(row0 + row) * gcols + col] : 0.0f;
                     float o = y, d = g;
                     if (A.head != MLP_HEAD_LOGITS && A.action_range > 0.0f) {   // action = action_range * tanh(mean)
-                        const float t = gradact::tanh_det(y);
+                        const float t = mlp::tanh_det(y);
                         o = A.action_range * t;
                         d = (g * A.action_range) * (1.0f - t * t);
                     }
-                    d = d * gradact::derivative_rt(A.out_act, y);
+                    d = d * mlp::derivative_rt(A.out_act, y);
                     if (live && A.out) A.out[(size_t)(row0 + row) * gcols + col] = o;
                     dl[ct][v] = live ? d : 0.0f;                         // rows beyond n and the log-std columns: exact zeros
                 }
@@ -344,22 +165,22 @@ __global__ __launch_bounds__(MLP_THREADS, 2) void mlp_bwd_data_kernel(const MlpG
 
     // ---- backwards: d_{L-1} = (d_L * W_L^T) (.) act'(x_L), the transposed packing as the B operand, no bias ----
     for (int L = H; L >= 1; --L) {
-        f32x16 acc[RT][CT];
+        mlp::f32x16 acc[RT][CT];
 #pragma unroll
         for (int c = 0; c < CT; ++c)
 #pragma unroll
             for (int r = 0; r < RT; ++r)
 #pragma unroll
                 for (int v = 0; v < 16; ++v) acc[r][c][v] = 0.0f;
-        grad_layer_chain<RT, CT>(a_row, 32 * RS, reinterpret_cast<const f32x4*>(G.wt[L]), (L == H ? G.kt_out : U) >> 3, ct0, lane, acc);
+        mlp::layer_chain<RT, CT>(a_row, 32 * RS, reinterpret_cast<const mlp::f32x4*>(G.wt[L]), (L == H ? G.kt_out : U) >> 3, ct0, lane, acc);
         __syncthreads();                                              // every wave has read d_L
         const float* xg = G.ws + G.x_off[L] + (size_t)row0 * U;
         float* dg = G.ws + G.d_off[L - 1] + (size_t)row0 * U;
         switch (A.hidden_act) {
-            case MLP_ACT_RELU: grad_store_delta<RT, CT, MLP_ACT_RELU>(lds, RS, HS, rt0, ct0, i, h, acc, xg, dg, U); break;
-            case MLP_ACT_ELU: grad_store_delta<RT, CT, MLP_ACT_ELU>(lds, RS, HS, rt0, ct0, i, h, acc, xg, dg, U); break;
-            case MLP_ACT_TANH: grad_store_delta<RT, CT, MLP_ACT_TANH>(lds, RS, HS, rt0, ct0, i, h, acc, xg, dg, U); break;
-            default: grad_store_delta<RT, CT, MLP_ACT_LINEAR>(lds, RS, HS, rt0, ct0, i, h, acc, xg, dg, U); break;
+            case MLP_ACT_RELU: mlp::store_delta<RT, CT, MLP_ACT_RELU>(lds, RS, HS, rt0, ct0, i, h, acc, xg, dg, U); break;
+            case MLP_ACT_ELU: mlp::store_delta<RT, CT, MLP_ACT_ELU>(lds, RS, HS, rt0, ct0, i, h, acc, xg, dg, U); break;
+            case MLP_ACT_TANH: mlp::store_delta<RT, CT, MLP_ACT_TANH>(lds, RS, HS, rt0, ct0, i, h, acc, xg, dg, U); break;
+            default: mlp::store_delta<RT, CT, MLP_ACT_LINEAR>(lds, RS, HS, rt0, ct0, i, h, acc, xg, dg, U); break;
         }
         __syncthreads();
     }
@@ -368,12 +189,12 @@ __global__ __launch_bounds__(MLP_THREADS, 2) void mlp_bwd_data_kernel(const MlpG
     if (G.g_obs) {
         const int tiles = (D + 31) >> 5;
         for (int ct = wave; ct < tiles; ct += 4) {
-            f32x16 acc[2][1];
+            mlp::f32x16 acc[2][1];
 #pragma unroll
             for (int r = 0; r < 2; ++r)
 #pragma unroll
                 for (int v = 0; v < 16; ++v) acc[r][0][v] = 0.0f;
-            grad_layer_chain<2, 1>(lds + i * RS + h * HS, 32 * RS, reinterpret_cast<const f32x4*>(G.wt[0]), U >> 3, ct, lane, acc);
+            mlp::layer_chain<2, 1>(lds + i * RS + h * HS, 32 * RS, reinterpret_cast<const mlp::f32x4*>(G.wt[0]), U >> 3, ct, lane, acc);
             const int col = ct * 32 + i;
             if (col < D) {
                 const float sc = A.scale ? A.scale[col] : 1.0f;
@@ -419,7 +240,7 @@ __global__ __launch_bounds__(MLP_THREADS) void mlp_wgrad_kernel(const MlpGradArg
         xp[a] = W.x + (kin[a] ? k : 0);
         dp[a] = W.d + (uin[a] ? u : 0);
     }
-    f32x16 acc[2][2];
+    mlp::f32x16 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll

@@ -11,7 +11,8 @@
 //   per step t  (1) input: x0 = f16(row * scale) into the binary16 activation buffer (one fp32 multiply, then one conversion), and the
 //                   env role (thread e < 64 = env e) publishes its pose (x, y, sin, cos);
 //               (2) the policy: eb_policy_f16_device.h's hidden layers on v_mfma_f32_32x32x16_f16, the output layer on
-//                   v_mfma_f32_16x16x32_f16 (restated from eb_policy_f16.hip), eb_policy_run_batch's head; the 64 actions go to LDS;
+//                   v_mfma_f32_16x16x32_f16 (restated from eb_policy_f16.hip), eb_policy_run_batch's head on eb_mlp_device.h's
+//                   activations; the 64 actions go to LDS;
 //               (3) every thread tests its share of the tile's records against the record's env: a near one (DAM:228) goes into the
 //                   block's queue as an INDEX — the record itself stays where it is, in the rows;
 //               (4) waves 1..3 take the queue, one entry per thread: the circle-pair terms (DAM:218-229); meanwhile the env role runs
@@ -130,13 +131,13 @@ __global__ __launch_bounds__(PR_THREADS, 2) void policy_rollout_kernel(const Pol
             const int ct0 = RT == 2 ? wave * CT : (wave >> 1);
             for (int L = 0; L < A.n_hidden; ++L) {
                 const MlpF16Layer& ly = A.hid[L];
-                f32x16 acc[RT][CT];
+                mlp::f32x16 acc[RT][CT];
 #pragma unroll
                 for (int c = 0; c < CT; ++c) {
-                    const f32x4* bsrc = reinterpret_cast<const f32x4*>(ly.b + (ct0 + c) * 32 + 4 * h);   // units 8 g + 4 h + e
+                    const mlp::f32x4* bsrc = reinterpret_cast<const mlp::f32x4*>(ly.b + (ct0 + c) * 32 + 4 * h);   // units 8 g + 4 h + e
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        const f32x4 b = bsrc[2 * g];
+                        const mlp::f32x4 b = bsrc[2 * g];
 #pragma unroll
                         for (int r = 0; r < RT; ++r)
 #pragma unroll
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(PR_THREADS, 2) void policy_rollout_kernel(const Pol
             const _Float16* a_ptr = lds + (wave * 16 + i16) * RS + 8 * kq;
             const f16x8* wsrc = reinterpret_cast<const f16x8*>(A.outl.w) + lane;
             const float b = A.outl.b[i16];
-            f32x4 acc = {b, b, b, b};
+            mlp::f32x4 acc = {b, b, b, b};
             f16x8 bq = wsrc[0];
             for (int s = 0; s < steps; ++s) {
                 const f16x8 bn = wsrc[(size_t)(s + 1 < steps ? s + 1 : s) * 64];                 // the next step's weights under this MFMA
@@ -175,8 +176,8 @@ __global__ __launch_bounds__(PR_THREADS, 2) void policy_rollout_kernel(const Pol
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
                     const int row = wave * 16 + 4 * kq + v;
-                    const float mean = f16act::activate_rt(A.out_act, acc[v]);
-                    const float a = A.action_range > 0.0f ? A.action_range * f16act::tanh_det(mean) : mean;
+                    const float mean = mlp::activate_rt(A.out_act, acc[v]);
+                    const float a = A.action_range > 0.0f ? A.action_range * mlp::tanh_det(mean) : mean;
                     reinterpret_cast<float*>(&S.act[row])[i16] = a;
                     if (row < nE && A.actions_steps) A.actions_steps[((size_t)t * n + e0 + row) * 2 + i16] = a;
                 }

@@ -9,8 +9,8 @@
 //   forward, per step t
 //               (1) x_0 = row * scale into the fp32 activation buffer and into the workspace; the env role (thread e < 64 = env e)
 //                   publishes its pose;
-//               (2) the policy as mlp_bwd_data_kernel's forward half runs it (eb_policy_rollout_grad_device.h): every x_l[t] goes to the
-//                   workspace, the output layer on 16 x 16 x 4 tiles with eb_policy_run_batch's head; actions to LDS;
+//               (2) the policy as mlp_bwd_data_kernel's forward half runs it (the same layer_chain / store_hidden of eb_mlp_device.h): every x_l[t]
+//                   goes to the workspace, the output layer on 16 x 16 x 4 tiles with eb_policy_run_batch's head; actions to LDS;
 //               (3) near records (6.31 m) into the block's queue by index, their bit into the env's slot mask;
 //               (4) waves 1..3 take the queue: the penalty terms and, scaled by w5's two penalty weights, the record's three ego
 //                   partials (grad::record_partials, formed in the forward direction as eb_rollout_tape_cand_vjp.hip forms them);
@@ -30,18 +30,16 @@
 // The activation buffer is dead during (3)-(5) and the near-record scratch during (1)-(2) and the reverse: one region of LDS holds
 // both.  One block per CU.  Synchronisation is __syncthreads() only — no flags, no polling, nothing between blocks, no atomics to
 // global memory.  Arithmetic and order are those of the single calls (eb_policy_run_batch, eb_rollout_step, eb_rollout_step_vjp,
-// eb_mlp_backward); tests/test_gpu_policy_rollout_grad.py holds every output to their loop bit for bit.
+// eb_mlp_backward): the policy's device code is eb_mlp_device.h's, the text eb_policy.hip and eb_policy_grad.hip compile;
+// tests/test_gpu_policy_rollout_grad.py holds every output to the single calls' loop bit for bit.
 #include "eb_policy_rollout_grad.h"
 
-#include "eb_policy_rollout_grad_device.h"
+#include "eb_mlp_device.h"
 #include "eb_tape_device.h"
 #include "eb_tape_grad_device.h"
 
 namespace eb {
 namespace {
-
-using prg::f32x16;
-using prg::f32x4;
 
 constexpr int PG_ROWS = MLP_ROWS;         // envs per block
 constexpr int PG_THREADS = MLP_THREADS;   // 4 waves
@@ -147,7 +145,7 @@ __global__ __launch_bounds__(PG_THREADS, 1) void policy_rollout_grad_kernel(cons
         // ---- (2) the policy: hidden layers (mlp_bwd_data_kernel's forward loop) ----
         for (int L = 0; L < NH; ++L) {
             const MlpLayer& ly = A.hid[L];
-            f32x16 acc[RT][CT];
+            mlp::f32x16 acc[RT][CT];
 #pragma unroll
             for (int c = 0; c < CT; ++c) {
                 const float b = ly.b[(ct0 + c) * 32 + i];
@@ -156,14 +154,14 @@ __global__ __launch_bounds__(PG_THREADS, 1) void policy_rollout_grad_kernel(cons
 #pragma unroll
                     for (int v = 0; v < 16; ++v) acc[r][c][v] = b;
             }
-            prg::layer_chain<RT, CT>(a_row, 32 * RS, reinterpret_cast<const f32x4*>(ly.w), ly.k_pad >> 3, ct0, lane, acc);
+            mlp::layer_chain<RT, CT>(a_row, 32 * RS, reinterpret_cast<const mlp::f32x4*>(ly.w), ly.k_pad >> 3, ct0, lane, acc);
             __syncthreads();                                              // every wave has read this layer's inputs
             float* xg = A.ws + A.x_off[L + 1] + trow * U;
             switch (A.hidden_act) {
-                case MLP_ACT_RELU: prg::store_hidden<RT, CT, MLP_ACT_RELU>(lds, RS, HS, rt0, ct0, i, h, acc, xg, U); break;
-                case MLP_ACT_ELU: prg::store_hidden<RT, CT, MLP_ACT_ELU>(lds, RS, HS, rt0, ct0, i, h, acc, xg, U); break;
-                case MLP_ACT_TANH: prg::store_hidden<RT, CT, MLP_ACT_TANH>(lds, RS, HS, rt0, ct0, i, h, acc, xg, U); break;
-                default: prg::store_hidden<RT, CT, MLP_ACT_LINEAR>(lds, RS, HS, rt0, ct0, i, h, acc, xg, U); break;
+                case MLP_ACT_RELU: mlp::store_hidden<RT, CT, MLP_ACT_RELU>(lds, RS, HS, rt0, ct0, i, h, acc, xg, U); break;
+                case MLP_ACT_ELU: mlp::store_hidden<RT, CT, MLP_ACT_ELU>(lds, RS, HS, rt0, ct0, i, h, acc, xg, U); break;
+                case MLP_ACT_TANH: mlp::store_hidden<RT, CT, MLP_ACT_TANH>(lds, RS, HS, rt0, ct0, i, h, acc, xg, U); break;
+                default: mlp::store_hidden<RT, CT, MLP_ACT_LINEAR>(lds, RS, HS, rt0, ct0, i, h, acc, xg, U); break;
             }
             __syncthreads();
         }
@@ -173,13 +171,13 @@ __global__ __launch_bounds__(PG_THREADS, 1) void policy_rollout_grad_kernel(cons
             const int steps4 = A.outl.k_pad >> 4;
             const float* a_ptr = lds + (wave * 16 + i16) * RS + (kq & 1) * HS;
             const float b = A.outl.b[i16];
-            f32x4 acc = {b, b, b, b};
-            const f32x4* wsrc = reinterpret_cast<const f32x4*>(A.outl.w) + lane;
-            f32x4 bq = wsrc[0];
+            mlp::f32x4 acc = {b, b, b, b};
+            const mlp::f32x4* wsrc = reinterpret_cast<const mlp::f32x4*>(A.outl.w) + lane;
+            mlp::f32x4 bq = wsrc[0];
             for (int s4 = 0; s4 < steps4; ++s4) {
-                const f32x4 bn = wsrc[(size_t)(s4 + 1 < steps4 ? s4 + 1 : s4) * 64];
-                const f32x4 a01 = *reinterpret_cast<const f32x4*>(a_ptr + 8 * s4);
-                const f32x4 a23 = *reinterpret_cast<const f32x4*>(a_ptr + 8 * s4 + 4);
+                const mlp::f32x4 bn = wsrc[(size_t)(s4 + 1 < steps4 ? s4 + 1 : s4) * 64];
+                const mlp::f32x4 a01 = *reinterpret_cast<const mlp::f32x4*>(a_ptr + 8 * s4);
+                const mlp::f32x4 a23 = *reinterpret_cast<const mlp::f32x4*>(a_ptr + 8 * s4 + 4);
                 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(hsel ? a01[1] : a01[0], bq[0], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(hsel ? a01[3] : a01[2], bq[1], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(hsel ? a23[1] : a23[0], bq[2], acc, 0, 0, 0);
@@ -190,8 +188,8 @@ __global__ __launch_bounds__(PG_THREADS, 1) void policy_rollout_grad_kernel(cons
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
                     const int row = wave * 16 + 4 * kq + v;
-                    const float y = prg::act::activate_rt(A.out_act, acc[v]);
-                    const float a = A.action_range > 0.0f ? A.action_range * prg::act::tanh_det(y) : y;
+                    const float y = mlp::activate_rt(A.out_act, acc[v]);
+                    const float a = A.action_range > 0.0f ? A.action_range * mlp::tanh_det(y) : y;
                     reinterpret_cast<float*>(&S.act[row])[i16] = a;
                     tape[((size_t)t * PRG_TAPE_FLOATS + 14 + i16) * np + row] = y;   // the reverse takes the head's derivative from it
                     if (row < nE && A.actions_steps) A.actions_steps[((size_t)t * n + e0 + row) * 2 + i16] = a;
@@ -398,10 +396,10 @@ __global__ __launch_bounds__(PG_THREADS, 1) void policy_rollout_grad_kernel(cons
                     const float y = T[(size_t)(14 + col) * np + row];
                     d = g;
                     if (A.action_range > 0.0f) {                                // action = action_range * tanh(mean)
-                        const float th = prg::act::tanh_det(y);
+                        const float th = mlp::tanh_det(y);
                         d = (g * A.action_range) * (1.0f - th * th);
                     }
-                    d = d * prg::act::derivative_rt(A.out_act, y);
+                    d = d * mlp::derivative_rt(A.out_act, y);
                 }
                 if (col < A.kt_out) lds[row * RS + (col & 1) * HS + (col >> 1)] = d;
                 dg[idx] = d;
@@ -411,32 +409,32 @@ __global__ __launch_bounds__(PG_THREADS, 1) void policy_rollout_grad_kernel(cons
 
         // ---- backwards: d_{L-1} = (d_L * W_L^T) (.) act'(x_L), the transposed packing as the B operand, no bias ----
         for (int L = NH; L >= 1; --L) {
-            f32x16 acc[RT][CT];
+            mlp::f32x16 acc[RT][CT];
 #pragma unroll
             for (int c = 0; c < CT; ++c)
 #pragma unroll
                 for (int r = 0; r < RT; ++r)
 #pragma unroll
                     for (int v = 0; v < 16; ++v) acc[r][c][v] = 0.0f;
-            prg::layer_chain<RT, CT>(a_row, 32 * RS, reinterpret_cast<const f32x4*>(A.wt[L]), (L == NH ? A.kt_out : U) >> 3, ct0, lane, acc);
+            mlp::layer_chain<RT, CT>(a_row, 32 * RS, reinterpret_cast<const mlp::f32x4*>(A.wt[L]), (L == NH ? A.kt_out : U) >> 3, ct0, lane, acc);
             __syncthreads();                                              // every wave has read d_L
             const float* xg = A.ws + A.x_off[L] + trow * U;
             float* dg = A.ws + A.d_off[L - 1] + trow * U;
             switch (A.hidden_act) {
-                case MLP_ACT_RELU: prg::store_delta<RT, CT, MLP_ACT_RELU>(lds, RS, HS, rt0, ct0, i, h, acc, xg, dg, U); break;
-                case MLP_ACT_ELU: prg::store_delta<RT, CT, MLP_ACT_ELU>(lds, RS, HS, rt0, ct0, i, h, acc, xg, dg, U); break;
-                case MLP_ACT_TANH: prg::store_delta<RT, CT, MLP_ACT_TANH>(lds, RS, HS, rt0, ct0, i, h, acc, xg, dg, U); break;
-                default: prg::store_delta<RT, CT, MLP_ACT_LINEAR>(lds, RS, HS, rt0, ct0, i, h, acc, xg, dg, U); break;
+                case MLP_ACT_RELU: mlp::store_delta<RT, CT, MLP_ACT_RELU>(lds, RS, HS, rt0, ct0, i, h, acc, xg, dg, U); break;
+                case MLP_ACT_ELU: mlp::store_delta<RT, CT, MLP_ACT_ELU>(lds, RS, HS, rt0, ct0, i, h, acc, xg, dg, U); break;
+                case MLP_ACT_TANH: mlp::store_delta<RT, CT, MLP_ACT_TANH>(lds, RS, HS, rt0, ct0, i, h, acc, xg, dg, U); break;
+                default: mlp::store_delta<RT, CT, MLP_ACT_LINEAR>(lds, RS, HS, rt0, ct0, i, h, acc, xg, dg, U); break;
             }
             __syncthreads();
         }
 
         // ---- (R3) (d_0 * W_0^T) (.) scale for column tile 0, one row tile per wave 0 and 1; columns 0..8 into lambda ----
         if (wave < 2) {
-            f32x16 acc[1][1];
+            mlp::f32x16 acc[1][1];
 #pragma unroll
             for (int v = 0; v < 16; ++v) acc[0][0][v] = 0.0f;
-            prg::layer_chain<1, 1>(lds + (wave * 32 + i) * RS + h * HS, 32 * RS, reinterpret_cast<const f32x4*>(A.wt[0]), U >> 3, 0, lane, acc);
+            mlp::layer_chain<1, 1>(lds + (wave * 32 + i) * RS + h * HS, 32 * RS, reinterpret_cast<const mlp::f32x4*>(A.wt[0]), U >> 3, 0, lane, acc);
             if (i < 9) {
                 const float sc = A.scale ? A.scale[i] : 1.0f;
 #pragma unroll

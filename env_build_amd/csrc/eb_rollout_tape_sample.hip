@@ -27,6 +27,7 @@
 
 #include "eb_sample.h"
 #include "eb_env_device.h"
+#include "eb_mlp_device.h"
 #include "eb_tape_device.h"
 #include "eb_tape_grad_device.h"
 
@@ -35,28 +36,9 @@ namespace {
 
 constexpr int TS_THREADS = 256;
 
-// eb_policy.hip:exp_det, restated: deterministic and branch-free
-__device__ __forceinline__ float ts_exp_det(float x0) {
-    const float x = x0 > 88.0f ? 88.0f : (x0 < -87.0f ? -87.0f : x0);   // NaN falls through both compares
-    const float fx = __builtin_rintf(x * 1.44269504088896341f);
-    float r = __builtin_fmaf(-fx, 0.693359375f, x);
-    r = __builtin_fmaf(-fx, -2.12194440e-4f, r);
-    const float z = r * r;
-    float p = 1.9875691500e-4f;
-    p = __builtin_fmaf(p, r, 1.3981999507e-3f);
-    p = __builtin_fmaf(p, r, 8.3334519073e-3f);
-    p = __builtin_fmaf(p, r, 4.1665795894e-2f);
-    p = __builtin_fmaf(p, r, 1.6666665459e-1f);
-    p = __builtin_fmaf(p, r, 5.0000001201e-1f);
-    const float y = __builtin_fmaf(p, z, r) + 1.0f;
-    const int n = (x0 == x0) ? (int)fx : 0;                              // -126 .. 127
-    const float v = y * __builtin_bit_cast(float, (unsigned)(n + 127) << 23);
-    return (x0 == x0) ? v : x0;
-}
-
 // the soft-min weight of a sample (include/envbuild_sample.h): a NaN cost and a weight that is not a number count 0
 __device__ __forceinline__ float ts_weight(float c, float best, float inv_lambda) {
-    const float w = ts_exp_det((-(c - best)) * inv_lambda);
+    const float w = mlp::exp_det((-(c - best)) * inv_lambda);
     return (c == c && w == w) ? w : 0.0f;
 }
 

@@ -43,7 +43,7 @@ def _fma32(a, b, c):
 
 
 def _exp_det(x0):
-    """csrc/eb_policy.hip:exp_det (the oracle's eb_expf) on a float32 array."""
+    """csrc/eb_mlp_device.h:exp_det (the oracle's eb_expf) on a float32 array."""
     x0 = np.asarray(x0, np.float32)
     with np.errstate(all='ignore'):
         x = np.where(x0 > 88, np.float32(88), np.where(x0 < -87, np.float32(-87), x0)).astype(np.float32)
@@ -61,7 +61,7 @@ def _exp_det(x0):
 
 
 def _tanh_det(x):
-    """csrc/eb_policy.hip:tanh_det (the oracle's eb_tanhf) on a float32 array."""
+    """csrc/eb_mlp_device.h:tanh_det (the oracle's eb_tanhf) on a float32 array."""
     x = np.asarray(x, np.float32)
     with np.errstate(all='ignore'):
         ax = np.abs(x)

@@ -45,7 +45,7 @@ int eb_sample_abi_version(void);
  *   the env's path without retrack: the same rollout, the same per-step order over the non-zero weights, the same ascending-t sum
  *   from +0.
  * Best.    The first minimum over s wins; a NaN never wins; all NaN gives sample 0.  best_cost / best_tape are that sample's bits.
- * Mean.    w_s = exp(-(cost_s - best_cost) * inv_lambda) by a deterministic branch-free exp (eb_policy.hip:exp_det restated); a NaN
+ * Mean.    w_s = exp(-(cost_s - best_cost) * inv_lambda) by a deterministic branch-free exp (csrc/eb_mlp_device.h:exp_det); a NaN
  *   cost, and a weight that is not a number (inf - inf), has weight 0 and its tape is left out.
  *   mean_tape[t][e][a] = clamp(sum_s w_s u_s / sum_s w_s, -1, 1).  The order of the sums is the kernel's own and fixed (two launches
  *   repeat their bits); it is not part of the ABI.  When sum_s w_s is not positive (all costs NaN or infinite) the mean is sample 0.

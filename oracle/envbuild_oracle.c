@@ -1820,7 +1820,7 @@ struct eb_mlp_s {
     unsigned layers_set;
 };
 
-static float eb_expf(float x) { /* Cephes expf scheme with explicit fma; device twin: eb_policy.hip:exp_det */
+static float eb_expf(float x) { /* Cephes expf scheme with explicit fma; device twin: eb_mlp_device.h:exp_det */
     if (!(x == x)) return x;
     x = x > 88.0f ? 88.0f : (x < -87.0f ? -87.0f : x);
     const float fx = rintf(x * 1.44269504088896341f);
@@ -1841,7 +1841,7 @@ static float eb_expf(float x) { /* Cephes expf scheme with explicit fma; device 
     return y * s;
 }
 
-static float eb_tanhf(float x) { /* Cephes tanhf scheme; device twin: tanh_det */
+static float eb_tanhf(float x) { /* Cephes tanhf scheme; device twin: eb_mlp_device.h:tanh_det */
     const float ax = fabsf(x);
     if (ax > 44.0f) return x > 0.0f ? 1.0f : -1.0f;
     if (ax >= 0.625f) {

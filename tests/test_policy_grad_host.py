@@ -87,6 +87,20 @@ def test_hip_library_exports_the_entries_and_gfx950_kernels():
     assert ok.value == 7 and count.value == 7 and size.value == 7
 
 
+def test_the_shared_mlp_device_code_is_written_once():
+    """exp_det, tanh_det, elu_det, activate_rt, derivative_rt, the fp32 layer_chain and store_delta are each defined in one file of
+    the library, csrc/eb_mlp_device.h, and every policy translation unit includes it, directly or through eb_policy_f16_device.h"""
+    text = {f: open(os.path.join(eb_build.CSRC, f)).read() for f in eb_build.SOURCES + eb_build.HEADERS if os.sep not in f}
+    for name in ('exp_det', 'tanh_det', 'elu_det', 'activate_rt', 'derivative_rt', 'layer_chain', 'store_delta'):
+        # a function definition, under any prefix of the name (ts_exp_det, grad_layer_chain) and after any specifiers or return type
+        definition = re.compile(r'^[ \t]*(?:[\w:<>&*]+[ \t]+)+\w*%s[ \t]*\([^;{]*\)\s*\{' % name, re.M)
+        assert {f: len(definition.findall(src)) for f, src in text.items() if definition.search(src)} == {'eb_mlp_device.h': 1}, name
+    assert 'eb_mlp_device.h' in eb_build.HEADERS and '#include "eb_mlp_device.h"' in text['eb_policy_f16_device.h']
+    for unit in ('eb_policy.hip', 'eb_policy_grad.hip', 'eb_policy_rollout_grad.hip', 'eb_policy_f16.hip', 'eb_policy_rollout.hip'):
+        assert unit in eb_build.SOURCES
+        assert re.search(r'^#include "eb_(mlp|policy_f16)_device\.h"$', text[unit], re.M), unit
+
+
 def test_the_oracle_library_is_refused_with_the_family_label_and_header():
     api = oracle_lib()
     assert api.backend == 'oracle'

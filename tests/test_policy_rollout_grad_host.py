@@ -72,7 +72,7 @@ def test_hip_library_exports_the_entries_and_a_gfx950_kernel():
     assert lib.eb_policy_rollout_grad_abi_version() == 1
     assert b'gfx950' in blob and b'policy_rollout_grad_kernel' in blob and b'mlp_wgrad_kernel' in blob
     public = os.path.join('..', '..', 'include', HEADER)
-    new = {'eb_policy_rollout_grad.hip', 'eb_policy_rollout_grad.h', 'eb_policy_rollout_grad_device.h', public}
+    new = {'eb_policy_rollout_grad.hip', 'eb_policy_rollout_grad.h', 'eb_mlp_device.h', public}
     assert 'eb_policy_rollout_grad.hip' in eb_build.SOURCES and new - {'eb_policy_rollout_grad.hip'} <= set(eb_build.HEADERS)
     for f in eb_build.SOURCES + eb_build.HEADERS:
         assert os.path.isfile(os.path.join(eb_build.CSRC, f)), f
