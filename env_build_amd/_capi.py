@@ -6,6 +6,7 @@ or fails to load — there is no CPU fallback anywhere in the package.  (tests/ 
 with the same class to compare the two libraries call-for-call.)
 """
 import ctypes as C
+import functools
 import os
 
 EB_ABI_VERSION = 5
@@ -134,8 +135,11 @@ PROTOTYPES = {
     'eb_shield_is_safe': (C.c_int, [_P, _P, _I, _P, _P, _I, _I, _I, C.c_float, _P, _P, _P, _P, _P, _P, _P]),
 }
 
-# include/envbuild_grad.h: the reverse pass of the rollout step.  A table of its own, bound on first use and only where the library
-# exports the symbols (the HIP library does; the CPU oracle and a library built before the reverse pass existed do not).
+# The optional families: each a public header with a version of its own, exported by the HIP library only (the CPU oracle and a library
+# built before a family existed do not have it) and bound by CApi.family_fn on first use.  Per family: its version, the constants its
+# header defines, and name -> (restype, argtypes) for every symbol the header declares.
+
+# include/envbuild_grad.h: the reverse pass of the rollout step
 EB_GRAD_ABI_VERSION = 2
 GRAD_PROTOTYPES = {
     'eb_grad_abi_version': (C.c_int, []),
@@ -147,8 +151,7 @@ GRAD_PROTOTYPES = {
     'eb_rollout_tape_vjp_max_horizon': (C.c_int, [_P, C.POINTER(C.c_int32)]),
 }
 
-# include/envbuild_cand.h: K candidate tapes per env from one shared scene.  A third table with a version of its own, bound on first
-# use like the gradient table (the HIP library exports the symbols; the CPU oracle does not).
+# include/envbuild_cand.h: K candidate tapes per env from one shared scene
 EB_CAND_ABI_VERSION = 1
 CAND_PROTOTYPES = {
     'eb_cand_abi_version': (C.c_int, []),
@@ -158,8 +161,7 @@ CAND_PROTOTYPES = {
     'eb_rollout_tape_cand_max': (C.c_int, [_P, _I, C.POINTER(C.c_int32)]),
 }
 
-# include/envbuild_cand_grad.h: value AND gradient of K candidate tapes per env.  A fourth table with a version of its own, bound on
-# first use like the other two (the HIP library exports the symbols; the CPU oracle does not).
+# include/envbuild_cand_grad.h: value AND gradient of K candidate tapes per env
 EB_CAND_GRAD_ABI_VERSION = 1
 CAND_GRAD_PROTOTYPES = {
     'eb_cand_grad_abi_version': (C.c_int, []),
@@ -169,8 +171,7 @@ CAND_GRAD_PROTOTYPES = {
     'eb_rollout_tape_cand_vjp_max': (C.c_int, [_P, _I, C.POINTER(C.c_int32)]),
 }
 
-# include/envbuild_sample.h: S sampled tapes per env drawn, scored and averaged in one launch.  A fifth table with a version of its
-# own, bound on first use like the others (the HIP library exports the symbols; the CPU oracle does not).
+# include/envbuild_sample.h: S sampled tapes per env drawn, scored and averaged in one launch
 EB_SAMPLE_ABI_VERSION = 1
 SAMPLE_PROTOTYPES = {
     'eb_sample_abi_version': (C.c_int, []),
@@ -181,8 +182,7 @@ SAMPLE_PROTOTYPES = {
     'eb_rollout_tape_sample_max': (C.c_int, [_P, _I, C.POINTER(C.c_int32)]),
 }
 
-# include/envbuild_ilqr.h: one iLQR iteration on the model rollout in one launch.  A sixth table with a version of its own, bound on
-# first use like the others (the HIP library exports the symbols; the CPU oracle does not).
+# include/envbuild_ilqr.h: one iLQR iteration on the model rollout in one launch
 EB_ILQR_ABI_VERSION = 1
 ILQR_PROTOTYPES = {
     'eb_ilqr_abi_version': (C.c_int, []),
@@ -192,20 +192,7 @@ ILQR_PROTOTYPES = {
     'eb_rollout_tape_ilqr_max': (C.c_int, [_P, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
-# The optional families, each a header with a version of its own: family -> (header, what a library without it lacks, the word its
-# version message uses, version symbol, expected version, prototypes).  CApi.family_fn binds a family on first use.
-FAMILIES = {
-    'grad': ('envbuild_grad.h', 'reverse pass', 'gradient', 'eb_grad_abi_version', EB_GRAD_ABI_VERSION, GRAD_PROTOTYPES),
-    'cand': ('envbuild_cand.h', 'candidate-tape rollout', 'candidate', 'eb_cand_abi_version', EB_CAND_ABI_VERSION, CAND_PROTOTYPES),
-    'cand_grad': ('envbuild_cand_grad.h', 'candidate-tape gradient', 'candidate-gradient', 'eb_cand_grad_abi_version',
-                  EB_CAND_GRAD_ABI_VERSION, CAND_GRAD_PROTOTYPES),
-    'sample': ('envbuild_sample.h', 'sampled-tape rollout', 'sampled-tape', 'eb_sample_abi_version', EB_SAMPLE_ABI_VERSION,
-               SAMPLE_PROTOTYPES),
-    'ilqr': ('envbuild_ilqr.h', 'iLQR iteration', 'iLQR', 'eb_ilqr_abi_version', EB_ILQR_ABI_VERSION, ILQR_PROTOTYPES),
-}
-
-# include/envbuild_mlp_f16.h: the policy handle's inference precision (binary16 operands on the matrix cores).  A table with a version
-# of its own like the others, kept in a SECOND family table: FAMILIES is the tape-and-gradient set its tests enumerate.
+# include/envbuild_mlp_f16.h: the policy handle's inference precision (binary16 operands on the matrix cores)
 EB_MLP_F16_ABI_VERSION = 1
 MLP_PRECISION_ID = {'fp32': 0, 'fp16': 1}                              # EB_MLP_PRECISION_*
 MLP_F16_PROTOTYPES = {
@@ -213,12 +200,8 @@ MLP_F16_PROTOTYPES = {
     'eb_mlp_set_precision': (C.c_int, [_P, _I]),
     'eb_mlp_get_precision': (C.c_int, [_P, C.POINTER(_I)]),
 }
-MORE_FAMILIES = {
-    'mlp_f16': ('envbuild_mlp_f16.h', 'fp16 policy', 'fp16-policy', 'eb_mlp_f16_abi_version', EB_MLP_F16_ABI_VERSION, MLP_F16_PROTOTYPES),
-}
 
-# include/envbuild_policy_rollout.h: `steps` x [policy -> model step] in one launch.  A table with a version of its own like the others,
-# kept in a THIRD family table: the first two are the sets their tests enumerate.
+# include/envbuild_policy_rollout.h: `steps` x [policy -> model step] in one launch
 EB_POLICY_ROLLOUT_ABI_VERSION = 1
 POLICY_ROLLOUT_PROTOTYPES = {
     'eb_policy_rollout_abi_version': (C.c_int, []),
@@ -227,13 +210,8 @@ POLICY_ROLLOUT_PROTOTYPES = {
     #  safe, stream)
     'eb_policy_rollout': (C.c_int, [_P, _P, _I, _I, _P, _P, _I, C.c_float, _I, _P, _P, _P, _P, _P, _P, _P]),
 }
-POLICY_FAMILIES = {
-    'policy_rollout': ('envbuild_policy_rollout.h', 'closed-loop policy rollout', 'policy-rollout', 'eb_policy_rollout_abi_version',
-                       EB_POLICY_ROLLOUT_ABI_VERSION, POLICY_ROLLOUT_PROTOTYPES),
-}
 
-# include/envbuild_mlp_grad.h: the policy network's backward and the device-side weight set.  A table with a version of its own like the
-# others, kept in a FOURTH family table: the first three are the sets their tests enumerate.
+# include/envbuild_mlp_grad.h: the policy network's backward and the device-side weight set
 EB_MLP_GRAD_ABI_VERSION = 1
 MLP_GRAD_PROTOTYPES = {
     'eb_mlp_grad_abi_version': (C.c_int, []),
@@ -244,14 +222,8 @@ MLP_GRAD_PROTOTYPES = {
     # (m, n, obs, g_out, head, action_range, workspace, workspace_bytes, out, g_obs, g_params, stream)
     'eb_mlp_backward': (C.c_int, [_P, _I, _P, _P, _I, C.c_float, _P, C.c_size_t, _P, _P, _P, _P]),
 }
-TRAIN_FAMILIES = {
-    'mlp_grad': ('envbuild_mlp_grad.h', 'policy backward', 'policy-gradient', 'eb_mlp_grad_abi_version', EB_MLP_GRAD_ABI_VERSION,
-                 MLP_GRAD_PROTOTYPES),
-}
-_FAMILY_TABLES = (FAMILIES, MORE_FAMILIES, POLICY_FAMILIES, TRAIN_FAMILIES)
 
-# include/envbuild_policy_rollout_grad.h: the closed-loop rollout with its parameter gradient.  A table with a version of its own like
-# the others, kept in a FIFTH family table that is consulted AFTER _FAMILY_TABLES: that tuple is the set its tests enumerate.
+# include/envbuild_policy_rollout_grad.h: the closed-loop rollout with its parameter gradient
 EB_POLICY_ROLLOUT_GRAD_ABI_VERSION = 1
 POLICY_ROLLOUT_GRAD_MAX_STEPS = 128
 POLICY_ROLLOUT_GRAD_PROTOTYPES = {
@@ -262,19 +234,26 @@ POLICY_ROLLOUT_GRAD_PROTOTYPES = {
     #  actions_steps, obs_steps, cost, g_actions_steps, g_obs0, g_params, stream)
     'eb_policy_rollout_grad': (C.c_int, [_P, _P, _I, _I, _P, _P, _I, C.c_float, _P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
-LOOP_GRAD_FAMILIES = {
+
+# One row per optional family: family -> (header, what a library without it lacks, the word its version message uses, version symbol,
+# expected version, prototypes).  A new family is a new row: family_fn, __getattr__ and CApi.<family>_fn all read this table.
+FAMILIES = {
+    'grad': ('envbuild_grad.h', 'reverse pass', 'gradient', 'eb_grad_abi_version', EB_GRAD_ABI_VERSION, GRAD_PROTOTYPES),
+    'cand': ('envbuild_cand.h', 'candidate-tape rollout', 'candidate', 'eb_cand_abi_version', EB_CAND_ABI_VERSION, CAND_PROTOTYPES),
+    'cand_grad': ('envbuild_cand_grad.h', 'candidate-tape gradient', 'candidate-gradient', 'eb_cand_grad_abi_version',
+                  EB_CAND_GRAD_ABI_VERSION, CAND_GRAD_PROTOTYPES),
+    'sample': ('envbuild_sample.h', 'sampled-tape rollout', 'sampled-tape', 'eb_sample_abi_version', EB_SAMPLE_ABI_VERSION,
+               SAMPLE_PROTOTYPES),
+    'ilqr': ('envbuild_ilqr.h', 'iLQR iteration', 'iLQR', 'eb_ilqr_abi_version', EB_ILQR_ABI_VERSION, ILQR_PROTOTYPES),
+    'mlp_f16': ('envbuild_mlp_f16.h', 'fp16 policy', 'fp16-policy', 'eb_mlp_f16_abi_version', EB_MLP_F16_ABI_VERSION, MLP_F16_PROTOTYPES),
+    'policy_rollout': ('envbuild_policy_rollout.h', 'closed-loop policy rollout', 'policy-rollout', 'eb_policy_rollout_abi_version',
+                       EB_POLICY_ROLLOUT_ABI_VERSION, POLICY_ROLLOUT_PROTOTYPES),
+    'mlp_grad': ('envbuild_mlp_grad.h', 'policy backward', 'policy-gradient', 'eb_mlp_grad_abi_version', EB_MLP_GRAD_ABI_VERSION,
+                 MLP_GRAD_PROTOTYPES),
     'policy_rollout_grad': ('envbuild_policy_rollout_grad.h', 'closed-loop policy rollout gradient', 'policy-rollout-gradient',
                             'eb_policy_rollout_grad_abi_version', EB_POLICY_ROLLOUT_GRAD_ABI_VERSION, POLICY_ROLLOUT_GRAD_PROTOTYPES),
 }
-_ALL_FAMILY_TABLES = _FAMILY_TABLES + (LOOP_GRAD_FAMILIES,)
-
-
-def family_row(family):
-    """The six-tuple of one optional family: FAMILIES first, then MORE_FAMILIES, POLICY_FAMILIES, TRAIN_FAMILIES and LOOP_GRAD_FAMILIES."""
-    for table in _ALL_FAMILY_TABLES:
-        if family in table:
-            return table[family]
-    raise KeyError(family)
+_FAMILY_OF = {symbol: family for family, row in FAMILIES.items() for symbol in row[5]}
 
 
 class EbError(RuntimeError):
@@ -297,9 +276,9 @@ class CApi(object):
         self.backend = self.lib.eb_backend().decode()
 
     def family_fn(self, family, symbol):
-        """The raw ctypes function of one entry of an optional family (a key of FAMILIES, MORE_FAMILIES, POLICY_FAMILIES, TRAIN_FAMILIES or LOOP_GRAD_FAMILIES), the family bound on first use;
-        EbError when this library does not export it or speaks another version of it."""
-        header, label, abi, version_symbol, version, prototypes = family_row(family)
+        """The raw ctypes function of one entry of an optional family (a key of FAMILIES), the family bound on first use; EbError when
+        this library does not export it or speaks another version of it."""
+        header, label, abi, version_symbol, version, prototypes = FAMILIES[family]
         fns = self.__dict__.setdefault('_%s_fns' % family, {})
         if not fns:
             missing = [n for n in prototypes if not hasattr(self.lib, n)]
@@ -315,33 +294,6 @@ class CApi(object):
                 fns.clear()
                 raise EbError('%s: %s ABI version %d, expected %d' % (self.path, abi, v, version))
         return fns[symbol]
-
-    def grad_fn(self, symbol):
-        return self.family_fn('grad', symbol)
-
-    def cand_fn(self, symbol):
-        return self.family_fn('cand', symbol)
-
-    def cand_grad_fn(self, symbol):
-        return self.family_fn('cand_grad', symbol)
-
-    def sample_fn(self, symbol):
-        return self.family_fn('sample', symbol)
-
-    def ilqr_fn(self, symbol):
-        return self.family_fn('ilqr', symbol)
-
-    def mlp_f16_fn(self, symbol):
-        return self.family_fn('mlp_f16', symbol)
-
-    def policy_rollout_fn(self, symbol):
-        return self.family_fn('policy_rollout', symbol)
-
-    def mlp_grad_fn(self, symbol):
-        return self.family_fn('mlp_grad', symbol)
-
-    def policy_rollout_grad_fn(self, symbol):
-        return self.family_fn('policy_rollout_grad', symbol)
 
     def check(self, rc):
         if rc != 0:
@@ -389,7 +341,7 @@ class CApi(object):
     def __getattr__(self, name):
         # eb_xxx(...) with return-code checking: api.rollout_step(h, ...)
         sym = 'eb_' + name
-        family = next((f for table in _ALL_FAMILY_TABLES for f, row in table.items() if sym in row[5]), None)
+        family = _FAMILY_OF.get(sym)
         fn = self.family_fn(family, sym) if family else getattr(self.lib, sym)
 
         def call(*args):
@@ -398,6 +350,9 @@ class CApi(object):
         setattr(self, name, call)
         return call
 
+
+for _family in FAMILIES:      # CApi.grad_fn(symbol) ... CApi.policy_rollout_grad_fn(symbol): family_fn with the family filled in
+    setattr(CApi, _family + '_fn', functools.partialmethod(CApi.family_fn, _family))
 
 HIP_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib',
                             'libenvbuild_hip.so')

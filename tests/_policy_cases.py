@@ -1,6 +1,6 @@
 """What the CPU and the GPU policy tests share: seeded layers and their plain torch fp32 forward (utils/model.py:18-43 +
-utils/policy.py:85-92 restated), the G13 / G14 fixture names, G13's weight lists and G14's shield check.  A helper module: pytest does
-not collect it, and torch is imported where it is used."""
+utils/policy.py:85-92 restated) and float64 autograd twin, the network configurations, the G13 / G14 fixture names, G13's weight lists
+and G14's shield check.  A helper module: pytest does not collect it, and torch is imported where it is used."""
 import glob
 import os
 
@@ -13,6 +13,14 @@ from tests._helpers import GOLDEN, close
 G13 = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(GOLDEN, 'g13_policy_*.npz')))
 # G14: HierarchicalDecision.is_safe / safe_shield (hier_decision.py:89-107) from the reference's own method bodies
 G14 = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(GOLDEN, 'g14_shield_*.npz')))
+
+CONFIGS = [
+    # obs_dim, n_hidden, n_units, out_dim, hidden act, out act
+    (41, 2, 256, 4, 'elu', 'linear'), (137, 2, 256, 4, 'elu', 'linear'), (29, 1, 64, 4, 'relu', 'linear'),
+    (45, 3, 128, 1, 'tanh', 'relu'), (265, 2, 512, 4, 'elu', 'tanh'), (33, 4, 100, 6, 'elu', 'linear'),
+    (8, 8, 32, 2, 'elu', 'linear'), (137, 2, 300, 32, 'relu', 'linear'), (300, 1, 256, 4, 'elu', 'linear'),
+]
+HOST_CONFIGS = CONFIGS + [(17, 1, 1, 1, 'elu', 'linear')]        # the CPU tests add the smallest network
 
 
 def make_layers(rng, obs_dim, n_hidden, n_units, out_dim, bias_scale=0.1):
@@ -35,6 +43,22 @@ def torch_mlp(layers, obs, hidden_act, out_act, scale=None):
         x = x @ torch.from_numpy(k) + torch.from_numpy(b)
         x = acts[out_act if L == len(layers) - 1 else hidden_act](x)
     return x.numpy()
+
+
+def torch_twin(layers, obs, g, hidden_act, out_act, scale, head, action_range):
+    """float64 autograd of a torch network built from the same layers -> (out, g_obs, g_params)"""
+    import torch
+    acts = {'linear': lambda x: x, 'relu': torch.relu, 'elu': torch.nn.functional.elu, 'tanh': torch.tanh}
+    params = [torch.tensor(np.asarray(a, np.float64), requires_grad=True) for pair in layers for a in pair]
+    x0 = torch.tensor(np.asarray(obs, np.float64), requires_grad=True)
+    x = x0 if scale is None else x0 * torch.tensor(np.asarray(scale, np.float64))
+    for L in range(len(layers)):
+        x = acts[out_act if L == len(layers) - 1 else hidden_act](x @ params[2 * L] + params[2 * L + 1])
+    if head == 1:
+        mean = x[:, :x.shape[1] // 2]
+        x = action_range * torch.tanh(mean) if action_range > 0 else mean
+    (x * torch.tensor(np.asarray(g, np.float64))).sum().backward()
+    return x.detach().numpy(), x0.grad.numpy(), [p.grad.numpy() for p in params]
 
 
 def g13_layers(g, model):

@@ -1,39 +1,23 @@
-"""What the CPU and the GPU tests of eb_policy_rollout_grad (include/envbuild_policy_rollout_grad.h) share: the entry as one call, and
-the yardstick — the loop of existing single calls through the same two handles, forward and back.  A helper module like _tape.py and
-_policy_cases.py: pytest does not collect it, and importing it touches no device."""
+"""What is specific to eb_policy_rollout_grad (include/envbuild_policy_rollout_grad.h) on top of tests/_policy.py: the entry as one call,
+and the yardstick — the loop of existing single calls through the same two handles, forward and back.  A helper module like _tape.py
+and _policy.py: pytest does not collect it, and importing it touches no device."""
 import ctypes as C
+import functools
 
 import numpy as np
 
-from env_build_amd.synthetic import assemble_obs, make_rollout_inputs
-from tests._helpers import HostModel, oracle_lib
-from tests._policy_cases import make_layers
+from tests import _policy
+from tests._policy import SENTINEL, assert_equal, param_count, same, scene, split_params  # noqa: F401  (its tests reach them through here)
 from tests._tape import TapeModel, cost_in_the_headers_order
 
-SENTINEL = -77.25
 W5 = (-1.0, 10.0, 0.0, 0.0, 0.0)                # ADP's loss before its 1 / (steps * n_env): rewards against the training penalty
 OUTPUTS = ('last', 'out5', 'actions', 'obs', 'cost', 'g_actions', 'g_obs0', 'g_params')
 PER_ROW = ('last', 'out5', 'actions', 'obs', 'cost', 'g_actions', 'g_obs0')
-
-
-def same(a, b):
-    return a.shape == b.shape and np.array_equal(a, b, equal_nan=True)
+supported = functools.partial(_policy.supported, family='policy_rollout_grad')
 
 
 def floats(v):
     return (C.c_float * len(v))(*[float(x) for x in v])
-
-
-def param_count(dev, m):
-    count = C.c_int64(-1)
-    dev.api.mlp_param_count(m, C.byref(count))
-    return count.value
-
-
-def supported(dev, m):
-    ok = C.c_int32(-7)
-    dev.api.policy_rollout_grad_supported(dev.h, m, C.byref(ok))
-    return ok.value, dev.api.lib.eb_last_error().decode()
 
 
 def workspace_bytes(dev, m, n, steps):
@@ -109,51 +93,10 @@ def loop(dev, m, obs0, steps, w5=W5, ref_idx=None, path_id=0, ar=1.0, g_params=F
     return out
 
 
-def assert_equal(got, want, what, keys=None):
-    for k, g in got.items():
-        if keys is not None and k not in keys:
-            continue
-        assert same(g, want[k]), '%s: %s differs in %d of %d values' % (
-            what, k, int((~((g == want[k]) | (np.isnan(g) & np.isnan(want[k])))).sum()) if g.shape == want[k].shape else -1, g.size)
-
-
 def rows_of(d, idx):
     """the per-row outputs of `d` for the envs idx"""
     pick = {'last': lambda v: v[idx], 'cost': lambda v: v[idx], 'g_obs0': lambda v: v[idx], 'out5': lambda v: v[:, :, idx]}
     return {k: pick.get(k, lambda v: v[:, idx])(v) for k, v in d.items() if k in PER_ROW}
-
-
-def split_params(flat, dims):
-    obs_dim, n_hidden, n_units, out_dim = dims
-    d = [obs_dim] + [n_units] * n_hidden + [out_dim]
-    out, at = [], 0
-    for L in range(n_hidden + 1):
-        for shape in ((d[L], d[L + 1]), (d[L + 1],)):
-            size = int(np.prod(shape))
-            out.append(flat[at:at + size].reshape(shape))
-            at += size
-    assert at == len(flat)
-    return out
-
-
-_SCENES = {}
-
-
-def scene(task, N, units, n_hidden, B=200, hact='elu', gain=1.0):
-    """start states and a network, made once per case (tests/test_gpu_policy_rollout.py's scene, with the hidden activation and a
-    factor on the output layer's weights): -> obs0, ref_idx, make_mlp's arguments, obs scale"""
-    key = (task, N, units, n_hidden, B, hact, gain)
-    if key not in _SCENES:
-        host = HostModel(oracle_lib(), task, n_veh=N)
-        inp = make_rollout_inputs(task, B, N, 5, seed=21)
-        trk = host.tracking_error(inp['ego'][:, 3], inp['ego'][:, 4], inp['ego'][:, 5], inp['ego'][:, 0], 0, ref_idx=inp['ref_idx'])
-        obs0 = assemble_obs(inp['ego'], trk, inp['veh'])
-        rng = np.random.default_rng(N)
-        layers = make_layers(rng, host.D, n_hidden, units, 4)
-        layers[-1] = ((layers[-1][0] * np.float32(gain)).astype(np.float32), layers[-1][1])
-        scale = rng.uniform(0.02, 0.2, host.D).astype(np.float32)
-        _SCENES[key] = (obs0, inp['ref_idx'], (host.D, n_hidden, units, 4, hact, 'linear', layers), scale)
-    return _SCENES[key]
 
 
 def model(task, N, mode='training'):

@@ -71,12 +71,14 @@ def test_product_never_imports_the_oracle():
 
 
 def test_every_optional_family_is_refused_by_name_on_a_library_without_it():
-    """_capi.FAMILIES drives the binder and __getattr__: on the oracle library, which exports none of the optional families, every
+    """_capi.FAMILIES drives the binder and __getattr__: on the oracle library, which exports none of the nine optional families, every
     symbol of every row is refused with that row's own label, and the row's one-line method agrees."""
     api = oracle_lib()
     rows = _capi.FAMILIES
     assert [row[5] for row in rows.values()] == [_capi.GRAD_PROTOTYPES, _capi.CAND_PROTOTYPES, _capi.CAND_GRAD_PROTOTYPES,
-                                                 _capi.SAMPLE_PROTOTYPES, _capi.ILQR_PROTOTYPES]
+                                                 _capi.SAMPLE_PROTOTYPES, _capi.ILQR_PROTOTYPES, _capi.MLP_F16_PROTOTYPES,
+                                                 _capi.POLICY_ROLLOUT_PROTOTYPES, _capi.MLP_GRAD_PROTOTYPES,
+                                                 _capi.POLICY_ROLLOUT_GRAD_PROTOTYPES]
     for family, (header, label, _abi, version_symbol, version, prototypes) in rows.items():
         assert os.path.isfile(os.path.join(ROOT, 'include', header)) and version_symbol in prototypes
         assert version == getattr(_capi, 'EB_%s_ABI_VERSION' % family.upper())

@@ -11,21 +11,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from env_build_amd.synthetic import assemble_obs, make_rollout_inputs  # noqa: E402
 from tests._helpers import DeviceModel, HostModel, oracle_lib  # noqa: E402
-from tests._policy_cases import make_layers, torch_mlp  # noqa: E402
+from tests._policy import same  # noqa: E402
+from tests._policy_cases import CONFIGS, make_layers, torch_mlp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 PEN_RTOL = 1e-6
-
-CONFIGS = [
-    # obs_dim, n_hidden, n_units, out_dim, hidden act, out act
-    (41, 2, 256, 4, 'elu', 'linear'), (137, 2, 256, 4, 'elu', 'linear'), (29, 1, 64, 4, 'relu', 'linear'),
-    (45, 3, 128, 1, 'tanh', 'relu'), (265, 2, 512, 4, 'elu', 'tanh'), (33, 4, 100, 6, 'elu', 'linear'),
-    (8, 8, 32, 2, 'elu', 'linear'), (137, 2, 300, 32, 'relu', 'linear'), (300, 1, 256, 4, 'elu', 'linear'),
-]
-
-
-def same(a, b):
-    return np.array_equal(a, b, equal_nan=True)
 
 
 @pytest.mark.parametrize('cfg', CONFIGS, ids=lambda c: '%dx%dx%d_%s' % (c[0], c[1], c[2], c[4]))

@@ -17,36 +17,14 @@ from env_build_amd.policy import _tanh_det, mlp_f16_reference  # noqa: E402
 from env_build_amd.synthetic import assemble_obs, make_rollout_inputs  # noqa: E402
 from tests._grad_cases import column_tolerance  # noqa: E402
 from tests._helpers import DeviceModel, HostModel, golden, oracle_lib  # noqa: E402
-from tests._policy_cases import G14, make_layers  # noqa: E402
-from tests.test_gpu_policy import CONFIGS  # noqa: E402
+from tests._policy import F16, F32, f16_mlp, loop, loop_view, same, sparse_signs  # noqa: E402
+from tests._policy_cases import CONFIGS, G14, make_layers  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-F32, F16 = 0, 1
-
-
-def same(a, b):
-    return np.array_equal(a, b, equal_nan=True)
-
-
-def f16_mlp(dev, *args):
-    """DeviceModel.make_mlp with the handle switched to fp16"""
-    m = dev.make_mlp(*args)
-    dev.api.mlp_set_precision(m, F16)
-    return m
-
 
 # ---- 1: exact ----
 EXACT_SHAPES = [(1, 1, 1, 1), (15, 1, 31, 2), (16, 2, 32, 4), (17, 2, 33, 17), (41, 2, 256, 4), (137, 2, 256, 4), (265, 2, 512, 4),
                 (33, 4, 100, 6), (8, 8, 32, 2), (300, 1, 256, 32)]
-
-
-def sparse_signs(rng, k, cols, nnz):
-    """[k, cols] in {-1, 0, 1} with at most nnz non-zeros per column"""
-    w = np.zeros((k, cols), np.float32)
-    for j in range(cols):
-        rows = rng.choice(k, size=min(k, nnz), replace=False)
-        w[rows, j] = rng.choice(np.array([-1.0, 1.0], np.float32), size=len(rows))
-    return w
 
 
 def exact_chain(layers, obs, scale, relu):
@@ -203,12 +181,8 @@ def test_rows_are_independent_and_launches_repeat(dims, hact):
 
 # ---- 5: shield ----
 def generic_loop(dev, m, obs0, ref_idx, steps, penalty):
-    obs, punish = obs0, None
-    for _ in range(steps):
-        obs, out5, _ = dev.rollout_step(obs, dev.policy_run_batch(m, 2, obs, 1.0), ref_idx)
-        p = out5[3 if penalty == 0 else 2]
-        punish = p.copy() if punish is None else punish + p
-    return (~(punish > 0)).astype(np.uint8), punish, obs
+    view = loop_view(loop(dev, m, obs0, steps, ref_idx), steps, penalty)
+    return view['safe'], view['punish'], view['last']
 
 
 @pytest.mark.parametrize('task,N', [('left', 8), ('right', 5), ('left', 32)])

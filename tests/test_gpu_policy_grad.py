@@ -17,34 +17,10 @@ from env_build_amd import _capi  # noqa: E402
 from env_build_amd import policy_grad  # noqa: E402
 from env_build_amd.policy_grad import _act, mlp_backward_reference  # noqa: E402
 from tests._helpers import DeviceModel, HostModel, oracle_lib  # noqa: E402
-from tests._policy_cases import make_layers  # noqa: E402
+from tests._policy import F16, F32, SENTINEL, param_count, same, sparse_signs, split_params  # noqa: E402
+from tests._policy_cases import make_layers, torch_twin  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-F32, F16 = 0, 1
-SENTINEL = -77.25
-
-
-def same(a, b):
-    return np.array_equal(a, b, equal_nan=True)
-
-
-def split_params(flat, dims):
-    obs_dim, n_hidden, n_units, out_dim = dims
-    d = [obs_dim] + [n_units] * n_hidden + [out_dim]
-    out, at = [], 0
-    for L in range(n_hidden + 1):
-        for shape in ((d[L], d[L + 1]), (d[L + 1],)):
-            size = int(np.prod(shape))
-            out.append(flat[at:at + size].reshape(shape))
-            at += size
-    assert at == len(flat)
-    return out
-
-
-def param_count(dev, m):
-    count = C.c_int64(-1)
-    dev.api.mlp_param_count(m, C.byref(count))
-    return count.value
 
 
 def backward(dev, m, dims, obs, g, head=0, action_range=1.0, want=('out', 'g_obs', 'g_params')):
@@ -93,15 +69,6 @@ MANY_ROWS_SHAPES = [(29, 1, 64, 32), (45, 3, 128, 24), (41, 2, 256, 4)]
 EXACT_CASES = [(s, EXACT_SIZES) for s in EXACT_SHAPES] + [(s, MANY_ROWS_SIZES) for s in MANY_ROWS_SHAPES]
 EXACT_IDS = ['%dx%dx%dx%d' % s for s in EXACT_SHAPES] + ['%dx%dx%dx%d-2048+' % s for s in MANY_ROWS_SHAPES]
 GRAN = 2.0 ** -4
-
-
-def sparse_signs(rng, k, cols, nnz):
-    """[k, cols] in {-1, 0, 1} with at most nnz non-zeros per column"""
-    w = np.zeros((k, cols), np.float32)
-    for j in range(cols):
-        rows = rng.choice(k, size=min(k, nnz), replace=False)
-        w[rows, j] = rng.choice(np.array([-1.0, 1.0], np.float32), size=len(rows))
-    return w
 
 
 def exact_premise(layers, obs, g, scale, relu, head):
@@ -618,7 +585,6 @@ def test_trainable_mlpnet_gradients_optimiser_step_and_fp16():
     import torch
     from env_build_amd.policy import MLPNet
     from env_build_amd.policy_grad import TrainableMLPNet
-    from tests.test_policy_grad_host import torch_twin
     dims = (41, 2, 100, 4)
     rng = np.random.default_rng(11)
     net = TrainableMLPNet(dims[0], dims[1], dims[2], 'elu', dims[3], seed=4)
@@ -682,7 +648,6 @@ def test_trainable_mlpnet_critic_with_a_relu_output():
     call(x).sum().backward() against the torch twin under the rule of (2), rows on the output's kink leaving first"""
     import torch
     from env_build_amd.policy_grad import TrainableMLPNet
-    from tests.test_policy_grad_host import torch_twin
     dims = (41, 3, 100, 1)
     rng = np.random.default_rng(12)
     net = TrainableMLPNet(dims[0], dims[1], dims[2], 'tanh', dims[3], name='obj_v', output_activation='relu', seed=5)

@@ -4,6 +4,7 @@ eb_rollout_step through the same fp16 handle, and every comparison is bit for bi
 sizes, horizons, penalties, action ranges, modes and scale, (2) row independence and repeatability, (3) eb_shield_is_safe, (4) the
 reference's G14 flags, (5) eb_policy_rollout_supported and the refusals, (6) the façade and the example."""
 import ctypes as C
+import functools
 import os
 import sys
 
@@ -13,29 +14,14 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from env_build_amd import _capi  # noqa: E402
-from env_build_amd.synthetic import assemble_obs, make_rollout_inputs  # noqa: E402
-from tests._helpers import DeviceModel, HostModel, golden, oracle_lib  # noqa: E402
+from tests import _policy  # noqa: E402
+from tests._helpers import DeviceModel, golden  # noqa: E402
+from tests._policy import F16, F32, assert_equal, f16_mlp, loop, loop_view, same, scene  # noqa: E402
 from tests._policy_cases import G14, make_layers  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-F32, F16 = 0, 1
 EVERYTHING = ('out5', 'actions', 'obs', 'punish', 'safe')
-
-
-def same(a, b):
-    return np.array_equal(a, b, equal_nan=True)
-
-
-def f16_mlp(dev, *args):
-    m = dev.make_mlp(*args)
-    dev.api.mlp_set_precision(m, F16)
-    return m
-
-
-def supported(dev, m):
-    ok = C.c_int32(-7)
-    dev.api.policy_rollout_supported(dev.h, m, C.byref(ok))
-    return ok.value, dev.api.lib.eb_last_error().decode()
+supported =functools.partial(_policy.supported, family='policy_rollout')
 
 
 def entry(dev, m, obs, steps, ref_idx=None, path_id=0, ar=1.0, penalty=0, want=EVERYTHING):
@@ -52,51 +38,6 @@ def entry(dev, m, obs, steps, ref_idx=None, path_id=0, ar=1.0, penalty=0, want=E
     dev.api.policy_rollout(dev.h, m, n, int(steps), p(ob), p(ri), int(path_id), C.c_float(ar), int(penalty), p(bufs['last']),
                            p(bufs['out5']), p(bufs['actions']), p(bufs['obs']), p(bufs['punish']), p(bufs['safe']), dev.stream)
     return {k: dev._ret(v) for k, v in bufs.items() if v is not None}
-
-
-def loop(dev, m, obs0, steps, ref_idx=None, path_id=0, ar=1.0):
-    """the yardstick: `steps` x [eb_policy_run_batch -> eb_rollout_step], the per-step arrays kept (generic_loop of
-    tests/test_gpu_policy_f16.py, restated)"""
-    obs, out5s, acts, obss = obs0, [], [], []
-    for _ in range(steps):
-        a = dev.policy_run_batch(m, 2, obs, ar)
-        obs, out5, _ = dev.rollout_step(obs, a, ref_idx, path_id)
-        out5s.append(out5); acts.append(a); obss.append(obs)
-    return {'out5': np.stack(out5s), 'actions': np.stack(acts), 'obs': np.stack(obss)}
-
-
-def loop_view(ref, steps, penalty):
-    """what the entry must give for the first `steps` steps of a loop's record"""
-    row = 3 if penalty == 0 else 2
-    punish = ref['out5'][0, row].copy()
-    for t in range(1, steps):
-        punish = punish + ref['out5'][t, row]
-    return {'last': ref['obs'][steps - 1], 'out5': ref['out5'][:steps], 'actions': ref['actions'][:steps], 'obs': ref['obs'][:steps],
-            'punish': punish, 'safe': (~(punish > 0)).astype(np.uint8)}
-
-
-def assert_equal(got, want, what):
-    for k, g in got.items():
-        assert g.shape == want[k].shape and same(g, want[k]), '%s: %s differs in %d of %d values' % (
-            what, k, int((~((g == want[k]) | (np.isnan(g) & np.isnan(want[k])))).sum()), g.size)
-
-
-_SCENES = {}
-
-
-def scene(task, N, units, n_hidden, B=200):
-    """start states and a network, made once per case: make_rollout_inputs(task, B, N, 5, seed=21) + assemble_obs, make_layers(default_rng(N))"""
-    key = (task, N, units, n_hidden, B)
-    if key not in _SCENES:
-        host = HostModel(oracle_lib(), task, n_veh=N)
-        inp = make_rollout_inputs(task, B, N, 5, seed=21)
-        trk = host.tracking_error(inp['ego'][:, 3], inp['ego'][:, 4], inp['ego'][:, 5], inp['ego'][:, 0], 0, ref_idx=inp['ref_idx'])
-        obs0 = assemble_obs(inp['ego'], trk, inp['veh'])
-        rng = np.random.default_rng(N)
-        layers = make_layers(rng, host.D, n_hidden, units, 4)
-        scale = rng.uniform(0.02, 0.2, host.D).astype(np.float32)
-        _SCENES[key] = (obs0, inp['ref_idx'], (host.D, n_hidden, units, 4, 'elu', 'linear', layers), scale)
-    return _SCENES[key]
 
 
 # ---- 1: every output == the loop ----
@@ -204,14 +145,9 @@ def refused(dev, m, obs, match, ref_idx=None, **kw):
     steps = kw.get('steps', 5)
     outs = [dev._out(s, d) for s, d in (((n, D), np.float32), ((max(steps, 1), 5, n), np.float32), ((max(steps, 1), n, 2), np.float32),
                                         ((max(steps, 1), n, D), np.float32), ((n,), np.float32), ((n,), np.uint8))]
-    for o in outs:
-        o.fill_(77)
     p = dev._ptr
-    with pytest.raises(ValueError, match=match):
-        dev.api.policy_rollout(dev.h, m, kw.get('n', n), steps, p(ob), p(ri), kw.get('path_id', 0), C.c_float(1.0), kw.get('penalty', 0),
-                               *[p(o) for o in outs], dev.stream)
-    for o in outs:
-        assert bool((dev._ret(o) == 77).all())
+    _policy.refused(dev, lambda *o: dev.api.policy_rollout(dev.h, m, kw.get('n', n), steps, p(ob), p(ri), kw.get('path_id', 0), C.c_float(1.0),
+                                                           kw.get('penalty', 0), *o, dev.stream), outs, match, fill=77)
 
 
 def test_supported_says_what_the_kernel_takes_and_the_entry_refuses_the_rest():

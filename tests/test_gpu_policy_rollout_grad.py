@@ -14,11 +14,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from env_build_amd import _capi  # noqa: E402
 from env_build_amd.policy_grad import mlp_backward_reference  # noqa: E402
-from tests import _policy_rollout_grad as H  # noqa: E402
+from tests import _policy, _policy_rollout_grad as H  # noqa: E402
+from tests._policy import F16, F32  # noqa: E402
 from tests._policy_cases import make_layers  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-F32, F16 = 0, 1
 W5 = H.W5
 
 
@@ -162,14 +162,12 @@ def refused(dev, m, obs, match, ref_idx=None, exc=ValueError, **kw):
     n, D = ob.shape
     steps = kw.get('steps', 5)
     shp = H.shapes(n, D, min(max(steps, 1), 5), 70000)
-    outs = [torch.full(shp[k], H.SENTINEL, device=dev.dev) for k in H.OUTPUTS]
-    ws = torch.full((kw.get('ws_floats', 1 << 22),), H.SENTINEL, device=dev.dev)
+    outs = [torch.empty(shp[k], device=dev.dev) for k in H.OUTPUTS]
+    ws = torch.empty((kw.get('ws_floats', 1 << 22),), device=dev.dev)
     p = dev._ptr
-    with pytest.raises(exc, match=match):
-        dev.api.policy_rollout_grad(dev.h, m, kw.get('n', n), steps, p(ob), p(ri), kw.get('path_id', 0), C.c_float(1.0), H.floats(W5),
-                                    p(ws), kw.get('ws_bytes', ws.numel() * 4), *[p(o) for o in outs], dev.stream)
-    for o in outs + [ws]:
-        assert bool((dev._ret(o) == H.SENTINEL).all())
+    _policy.refused(dev, lambda w, *o: dev.api.policy_rollout_grad(dev.h, m, kw.get('n', n), steps, p(ob), p(ri), kw.get('path_id', 0),
+                                                                   C.c_float(1.0), H.floats(W5), w, kw.get('ws_bytes', ws.numel() * 4), *o,
+                                                                   dev.stream), [ws] + outs, match, exc)
 
 
 def test_supported_says_what_the_kernel_takes_and_the_entry_refuses_the_rest():

@@ -1,90 +1,15 @@
-"""CPU (-m "not gpu"): the policy-backward family (include/envbuild_mlp_grad.h) is declared as ctypes binds it, lives in a fourth family
-table, is exported by the built library next to gfx950 mlp_bwd_data_kernel / mlp_wgrad_kernel, stays out of the hashed forward sources
-and is refused by name by the oracle library; and the NumPy restatement of its contract
-(env_build_amd.policy_grad.mlp_backward_reference) run in float64 is torch's float64 autograd of a twin built from the same layers."""
-import ctypes as C
+"""CPU (-m "not gpu"): the shared MLP device code is defined once, and the NumPy restatement of the policy backward's contract
+(env_build_amd.policy_grad.mlp_backward_reference, include/envbuild_mlp_grad.h) run in float64 is torch's float64 autograd of a twin
+built from the same layers.  (The family's ABI: tests/test_family_abi.py.)"""
 import os
 import re
 
 import numpy as np
 import pytest
 
-from env_build_amd import _capi, build as eb_build
+from env_build_amd import build as eb_build
 from env_build_amd.policy_grad import mlp_backward_reference
-from tests._helpers import ROOT, oracle_lib
-from tests._policy_cases import make_layers
-from tests.test_policy_f16_host import CONFIGS
-
-HEADER = 'envbuild_mlp_grad.h'
-ALL_FAMILIES = ['grad', 'cand', 'cand_grad', 'sample', 'ilqr', 'mlp_f16', 'policy_rollout', 'mlp_grad']
-
-
-def header_src():
-    text = open(os.path.join(ROOT, 'include', HEADER)).read()
-    return text, re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-
-
-def test_header_declares_what_ctypes_binds():
-    text, src = header_src()
-    protos = _capi.MLP_GRAD_PROTOTYPES
-    assert sorted(protos) == sorted(set(re.findall(r'\b(eb_[a-z0-9_]+)\s*\(', src)))
-    assert sorted(protos) == ['eb_mlp_backward', 'eb_mlp_backward_workspace_bytes', 'eb_mlp_grad_abi_version', 'eb_mlp_grad_supported',
-                              'eb_mlp_param_count', 'eb_mlp_set_params_device']
-    for name, (_res, args) in protos.items():
-        m = re.search(r'\bint\s+%s\s*\(([^)]*)\)\s*;' % name, src)
-        assert m, '%s is not declared in include/%s' % (name, HEADER)
-        assert len([a for a in m.group(1).split(',') if a.strip() != 'void']) == len(args), name
-    assert len(protos['eb_mlp_backward'][1]) == 12
-    assert not set(protos) & set(_capi.PROTOTYPES)
-    for table in (_capi.FAMILIES, _capi.MORE_FAMILIES, _capi.POLICY_FAMILIES):
-        for row in table.values():
-            assert not set(protos) & set(row[5])
-    for words in ('NOT part of the contract', 'mlp_backward_reference', 'non-finite', 'bit for bit', 'y > 0 ? 1 : y + 1', 'EB_ESTATE',
-                  'Model.get_weights()'):
-        assert words in text, words
-
-
-def test_abi_number_and_the_fourth_family_table():
-    _text, src = header_src()
-    assert int(re.search(r'#define EB_MLP_GRAD_ABI_VERSION (\d+)', src).group(1)) == _capi.EB_MLP_GRAD_ABI_VERSION == 1
-    assert list(_capi.TRAIN_FAMILIES) == ['mlp_grad']
-    assert _capi._FAMILY_TABLES == (_capi.FAMILIES, _capi.MORE_FAMILIES, _capi.POLICY_FAMILIES, _capi.TRAIN_FAMILIES)
-    row = _capi.TRAIN_FAMILIES['mlp_grad']
-    assert len(row) == 6 == len(_capi.FAMILIES['grad'])
-    assert row[0] == HEADER and row[3] == 'eb_mlp_grad_abi_version' and row[4] == 1 and row[5] is _capi.MLP_GRAD_PROTOTYPES
-    assert [f for table in _capi._FAMILY_TABLES for f in table] == ALL_FAMILIES
-    for family in ALL_FAMILIES:
-        assert len(_capi.family_row(family)) == 6 and _capi.family_row(family)[3] in _capi.family_row(family)[5]
-    assert _capi.family_row('mlp_grad') is row
-    with pytest.raises(KeyError):
-        _capi.family_row('mlp_grad_f16')
-
-
-def test_hip_library_exports_the_entries_and_gfx950_kernels():
-    lib_path = eb_build.build()            # hipcc --offload-arch=gfx950 (cross-compiles without a GPU)
-    import torch  # noqa: F401  (binds the HIP runtime torch ships before ours, as the product does)
-    lib, blob = C.CDLL(lib_path), open(lib_path, 'rb').read()
-    for name in _capi.MLP_GRAD_PROTOTYPES:
-        assert hasattr(lib, name), name
-    assert lib.eb_mlp_grad_abi_version() == 1
-    assert b'gfx950' in blob
-    for kernel in (b'mlp_bwd_data_kernel', b'mlp_wgrad_kernel', b'mlp_wgrad_reduce_kernel', b'mlp_pack_kernel'):
-        assert kernel in blob, kernel
-    public = os.path.join('..', '..', 'include', HEADER)
-    assert 'eb_policy_grad.hip' in eb_build.SOURCES and {'eb_policy_grad.h', public} <= set(eb_build.HEADERS)
-    for files in eb_build.KERNEL_SOURCES.values():
-        assert not set(files) & {'eb_policy_grad.hip', 'eb_policy_grad.h', public}
-    # the refusals of a NULL handle need no device: the handle is checked first, and each entry names itself
-    lib.eb_last_error.restype = C.c_char_p
-    ok, count, size = C.c_int32(7), C.c_int64(7), C.c_size_t(7)
-    for name, args in (('eb_mlp_grad_supported', (None, C.byref(ok))), ('eb_mlp_param_count', (None, C.byref(count))),
-                       ('eb_mlp_set_params_device', (None, None, None)), ('eb_mlp_backward_workspace_bytes', (None, C.c_int32(4), C.byref(size))),
-                       ('eb_mlp_backward', (None, C.c_int32(4), None, None, C.c_int32(0), C.c_float(1.0), None, C.c_size_t(0), None, None, None, None))):
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _capi.MLP_GRAD_PROTOTYPES[name]
-        assert fn(*args) == -1, name
-        assert name.encode() in lib.eb_last_error() and b'null handle' in lib.eb_last_error(), name
-    assert ok.value == 7 and count.value == 7 and size.value == 7
+from tests._policy_cases import HOST_CONFIGS as CONFIGS, make_layers, torch_twin
 
 
 def test_the_shared_mlp_device_code_is_written_once():
@@ -101,41 +26,7 @@ def test_the_shared_mlp_device_code_is_written_once():
         assert re.search(r'^#include "eb_(mlp|policy_f16)_device\.h"$', text[unit], re.M), unit
 
 
-def test_the_oracle_library_is_refused_with_the_family_label_and_header():
-    api = oracle_lib()
-    assert api.backend == 'oracle'
-    header, label = _capi.TRAIN_FAMILIES['mlp_grad'][:2]
-    assert header == HEADER
-    for name in ('mlp_backward', 'mlp_set_params_device', 'mlp_grad_supported', 'mlp_param_count', 'mlp_backward_workspace_bytes',
-                 'mlp_grad_abi_version'):
-        assert 'eb_' + name in _capi.MLP_GRAD_PROTOTYPES
-        with pytest.raises(_capi.EbError) as e:
-            getattr(api, name)
-        assert label in str(e.value) and header in str(e.value), name
-        for fn in (api.mlp_grad_fn, lambda s: api.family_fn('mlp_grad', s)):
-            with pytest.raises(_capi.EbError) as e:
-                fn('eb_' + name)
-            assert label in str(e.value) and header in str(e.value), name
-    assert not hasattr(api.lib, 'eb_mlp_backward')
-
-
-def torch_twin(layers, obs, g, hidden_act, out_act, scale, head, action_range):
-    """float64 autograd of a torch network built from the same layers -> (out, g_obs, g_params)"""
-    import torch
-    acts = {'linear': lambda x: x, 'relu': torch.relu, 'elu': torch.nn.functional.elu, 'tanh': torch.tanh}
-    params = [torch.tensor(np.asarray(a, np.float64), requires_grad=True) for pair in layers for a in pair]
-    x0 = torch.tensor(np.asarray(obs, np.float64), requires_grad=True)
-    x = x0 if scale is None else x0 * torch.tensor(np.asarray(scale, np.float64))
-    for L in range(len(layers)):
-        x = acts[out_act if L == len(layers) - 1 else hidden_act](x @ params[2 * L] + params[2 * L + 1])
-    if head == 1:
-        mean = x[:, :x.shape[1] // 2]
-        x = action_range * torch.tanh(mean) if action_range > 0 else mean
-    (x * torch.tensor(np.asarray(g, np.float64))).sum().backward()
-    return x.detach().numpy(), x0.grad.numpy(), [p.grad.numpy() for p in params]
-
-
-# what tests/test_gpu_policy_grad.py rests on the restatement for, beyond CONFIGS (that module is GPU-marked as a whole; restated here):
+# what tests/test_gpu_policy_grad.py rests on the restatement for, beyond CONFIGS:
 # its exact shapes with out_dim 8 .. 32 and obs_dim 192 / 193 / 300 (relu / linear alternating), its wide random configs, and the
 # one-term shapes with every hidden activation times every output activation — relu and elu outputs, out_dim 17 / 18 / 32, obs_dim 300
 GRAD_CONFIGS = [(16, 2, 64, 8, 'linear', 'linear'), (193, 2, 64, 9, 'relu', 'linear'), (192, 1, 256, 16, 'linear', 'linear'),
