@@ -35,6 +35,8 @@
 #include "eb_policy_grad.h"
 #include "../../include/envbuild_policy_rollout_grad.h"
 #include "eb_policy_rollout_grad.h"
+#include "../../include/envbuild_policy_sample.h"
+#include "eb_policy_sample.h"
 #include "eb_grad.h"
 #include "eb_kernels.h"
 
@@ -2359,6 +2361,85 @@ int eb_mlp_backward(eb_mlp m, int32_t n, const float* obs, const float* g_out, i
     G.ws = static_cast<float*>(workspace);
     EB_HIP(hipSetDevice(m->cfg.device));
     EB_HIP(eb::launch_mlp_backward(G, (hipStream_t)stream));
+    return EB_OK;
+}
+
+}  // extern "C"
+
+// ---- include/envbuild_policy_sample.h: the stochastic policy head (eb_policy_sample.hip) ----
+// the first condition of eb_policy_sample's list this handle does not meet, in g_err, as the code to return; EB_OK when there is none
+static int policy_sample_fits(eb_mlp m) {
+    if (m->precision != EB_MLP_PRECISION_F32)
+        return fail(EB_EINVAL, "eb_policy_sample: the handle's precision must be EB_MLP_PRECISION_F32 (an fp16 handle samples through "
+                               "eb_mlp_forward and eb_policy_sample_from_logits)");
+    if (m->cfg.out_dim < 2 || (m->cfg.out_dim & 1)) return fail(EB_EINVAL, "eb_policy_sample: out_dim must be 2 * act_dim");
+    if (m->layers_set != (1u << (m->cfg.n_hidden + 1)) - 1u)
+        return fail(EB_ESTATE, "eb_policy_sample: a layer was never set (eb_mlp_set_layer for every layer, or eb_mlp_set_params_device)");
+    return EB_OK;
+}
+
+static int policy_sample_head(const char* who, int32_t n, int32_t out_dim, const float* eps, const int32_t* row_ids, uint64_t seed,
+                              uint64_t counter, float action_range, float* actions, float* logp, float* eps_out, eb::PolicySampleHead* H) {
+    if (n < 0 || out_dim < 2 || out_dim > 32 || (out_dim & 1) || (n > 0 && !actions) || action_range != action_range) {
+        std::snprintf(g_err, sizeof g_err, "%s: bad argument (n >= 0, out_dim even in 2..32, actions, action_range not NaN)", who);
+        return EB_EINVAL;
+    }
+    H->eps = eps; H->row_ids = row_ids; H->seed = seed; H->counter = counter;
+    H->action_range = action_range;
+    H->log_ar = action_range > 0.0f ? (float)std::log((double)action_range) : 0.0f;
+    H->actions = actions; H->logp = logp; H->eps_out = eps_out;
+    return EB_OK;
+}
+
+extern "C" {
+
+int eb_policy_sample_abi_version(void) { return EB_POLICY_SAMPLE_ABI_VERSION; }
+
+int eb_policy_sample_supported(eb_mlp m, int32_t* ok) {
+    if (!m) return fail(EB_EINVAL, "eb_policy_sample_supported: null handle");
+    if (!ok) return fail(EB_EINVAL, "eb_policy_sample_supported: null output pointer");
+    *ok = policy_sample_fits(m) == EB_OK ? 1 : 0;
+    return EB_OK;
+}
+
+int eb_policy_sample(eb_mlp m, int32_t n, const float* obs, const float* eps, const int32_t* row_ids, uint64_t seed, uint64_t counter,
+                     float action_range, float* actions, float* logp, float* logits_out, float* eps_out, void* stream) {
+    if (!m) return fail(EB_EINVAL, "eb_policy_sample: null handle");
+    int rc = policy_sample_fits(m);
+    if (rc) return rc;
+    if (n > 0 && !obs) return fail(EB_EINVAL, "eb_policy_sample: null obs");
+    eb::PolicySampleArgs A;
+    rc = policy_sample_head("eb_policy_sample", n, m->cfg.out_dim, eps, row_ids, seed, counter, action_range, actions, logp, eps_out, &A.head);
+    if (rc) return rc;
+    rc = mlp_args(m, 0, nullptr, nullptr, eb::MLP_HEAD_LOGITS, action_range, &A.fwd, "eb_policy_sample: null handle");   // n = 0 for its checks
+    if (rc || n == 0) return rc;
+    A.fwd.n = n; A.fwd.obs = obs; A.fwd.out = logits_out;
+    EB_HIP(hipSetDevice(m->cfg.device));
+    EB_HIP(eb::launch_policy_sample(A, (hipStream_t)stream));
+    return EB_OK;
+}
+
+int eb_policy_sample_from_logits(int32_t n, int32_t out_dim, const float* logits, const float* eps, const int32_t* row_ids, uint64_t seed,
+                                 uint64_t counter, float action_range, float* actions, float* logp, float* eps_out, void* stream) {
+    eb::PolicySampleLogitsArgs A;
+    const int rc = policy_sample_head("eb_policy_sample_from_logits", n, out_dim, eps, row_ids, seed, counter, action_range, actions, logp,
+                                      eps_out, &A.head);
+    if (rc) return rc;
+    if (n > 0 && !logits) return fail(EB_EINVAL, "eb_policy_sample_from_logits: null logits");
+    if (n == 0) return EB_OK;
+    A.logits = logits; A.n = n; A.out_dim = out_dim;
+    EB_HIP(eb::launch_policy_sample_from_logits(A, (hipStream_t)stream));
+    return EB_OK;
+}
+
+int eb_policy_sample_vjp(int32_t n, int32_t out_dim, const float* logits, const float* eps, float action_range, const float* g_actions,
+                         const float* g_logp, float* g_logits, void* stream) {
+    if (n < 0 || out_dim < 2 || out_dim > 32 || (out_dim & 1) || action_range != action_range)
+        return fail(EB_EINVAL, "eb_policy_sample_vjp: bad argument (n >= 0, out_dim even in 2..32, action_range not NaN)");
+    if (n > 0 && (!logits || !eps || !g_logits)) return fail(EB_EINVAL, "eb_policy_sample_vjp: null logits, eps or g_logits");
+    if (n == 0) return EB_OK;
+    const eb::PolicySampleVjpArgs A{logits, eps, g_actions, g_logp, g_logits, n, out_dim, action_range};
+    EB_HIP(eb::launch_policy_sample_vjp(A, (hipStream_t)stream));
     return EB_OK;
 }
 

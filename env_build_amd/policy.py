@@ -1,13 +1,14 @@
 """The policy side of the reference's decision loop, on the GPU: `MLPNet` (utils/model.py:18-43), `Policy4Toyota`
-(utils/policy.py:19-101, the deterministic inference surface) and `LoadPolicy` (utils/load_policy.py:19-63) with
+(utils/policy.py:19-101, the inference surface, deterministic and stochastic) and `LoadPolicy` (utils/load_policy.py:19-63) with
 the 'scale' observation preprocessor (utils/preprocessor.py:116-123).
 
 Same names, constructor arguments and methods as the reference; the arithmetic is one fused HIP kernel per call
 (env_build_amd/csrc/eb_policy.hip: fp32 matrix cores, the whole network in one launch; with precision='fp16' the opt-in
 binary16 kernel of env_build_amd/csrc/eb_policy_f16.hip, include/envbuild_mlp_f16.h).  The shield and the path selection
 only ever call `run_batch` / `obj_value_batch`; the network's backward and a trainable `MLPNet` whose weights stay on the
-device are env_build_amd.policy_grad (`TrainableMLPNet`, include/envbuild_mlp_grad.h).  Optimisers, stochastic sampling
-and log-probabilities are out of scope.
+device are env_build_amd.policy_grad (`TrainableMLPNet`, include/envbuild_mlp_grad.h).  With deterministic_policy false,
+`compute_action` samples the tanh-Gaussian policy and returns the actions with their log-probabilities in one launch
+(env_build_amd.policy_sample, include/envbuild_policy_sample.h); `seed` makes the draws repeat.  Optimisers are out of scope.
 
 TensorFlow checkpoints cannot be read here (no TF, and the reference's checkpoints are git-ignored): weights are
 exchanged as the list `Model.get_weights()` returns — [kernel0, bias0, kernel1, bias1, ...], kernels [in, out] —
@@ -42,37 +43,37 @@ def _fma32(a, b, c):
     return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(np.float32)
 
 
-def _exp_det(x0):
-    """csrc/eb_mlp_device.h:exp_det (the oracle's eb_expf) on a float32 array."""
+def _exp_det(x0, fma=_fma32):
+    """csrc/eb_mlp_device.h:exp_det (the oracle's eb_expf) on a float32 array; `fma`: the fused multiply-add it is evaluated with."""
     x0 = np.asarray(x0, np.float32)
     with np.errstate(all='ignore'):
         x = np.where(x0 > 88, np.float32(88), np.where(x0 < -87, np.float32(-87), x0)).astype(np.float32)
         fx = np.rint(x * np.float32(1.44269504088896341)).astype(np.float32)
-        r = _fma32(-fx, np.float32(0.693359375), x)
-        r = _fma32(-fx, np.float32(-2.12194440e-4), r)
+        r = fma(-fx, np.float32(0.693359375), x)
+        r = fma(-fx, np.float32(-2.12194440e-4), r)
         z = r * r
         p = np.full_like(r, 1.9875691500e-4)
         for c in (1.3981999507e-3, 8.3334519073e-3, 4.1665795894e-2, 1.6666665459e-1, 5.0000001201e-1):
-            p = _fma32(p, r, np.float32(c))
-        y = _fma32(p, z, r) + np.float32(1)
+            p = fma(p, r, np.float32(c))
+        y = fma(p, z, r) + np.float32(1)
         n = np.where(np.isnan(x0), 0, fx).astype(np.int32)
         v = y * ((n + 127).astype(np.uint32) << np.uint32(23)).view(np.float32)
     return np.where(np.isnan(x0), x0, v).astype(np.float32)
 
 
-def _tanh_det(x):
-    """csrc/eb_mlp_device.h:tanh_det (the oracle's eb_tanhf) on a float32 array."""
+def _tanh_det(x, fma=_fma32):
+    """csrc/eb_mlp_device.h:tanh_det (the oracle's eb_tanhf) on a float32 array; `fma` as in _exp_det."""
     x = np.asarray(x, np.float32)
     with np.errstate(all='ignore'):
         ax = np.abs(x)
-        s = _exp_det(ax + ax)
+        s = _exp_det(ax + ax, fma)
         t = np.float32(1) - np.float32(2) / (s + np.float32(1))
         big = np.where(x < 0, -t, t)
         z = x * x
         p = np.full_like(x, -5.70498872745e-3)
         for c in (2.06390887954e-2, -5.37397155531e-2, 1.33314422036e-1, -3.33332819422e-1):
-            p = _fma32(p, z, np.float32(c))
-        small = _fma32(p * z, x, x)
+            p = fma(p, z, np.float32(c))
+        small = fma(p * z, x, x)
         sat = np.where(x > 0, np.float32(1), np.float32(-1))
     return np.where(ax > 44, sat, np.where(ax >= 0.625, big, small)).astype(np.float32)
 
@@ -250,6 +251,11 @@ class Policy4Toyota(object):
         self.obj_v = MLPNet(obs_dim, n_hiddens, n_units, act, 1, name='obj_v', output_activation='relu',
                             device=device, seed=seed + 1, precision=precision)
         self.models = (self.obj_v, self.policy,)
+        self._sample_seed, self._sample_counter = int(seed), 0
+
+    def seed(self, seed):
+        """Restart the stochastic branch's noise stream: call k after seed(s) draws from (s, k), whatever came before."""
+        self._sample_seed, self._sample_counter = int(seed), 0
 
     def get_weights(self):
         return [model.get_weights() for model in self.models]
@@ -273,7 +279,11 @@ class Policy4Toyota(object):
 
     def compute_action(self, obs):                     # utils/policy.py:85-98
         if not getattr(self.args, 'deterministic_policy', True):
-            raise NotImplementedError('sampling from the policy distribution is a training-side feature (out of scope)')
+            from .policy_sample import sample_actions
+            out = sample_actions(self.policy, obs, getattr(self.args, 'action_range', None), seed=self._sample_seed,
+                                 counter=self._sample_counter)
+            self._sample_counter += 1
+            return out['actions'], out['logp']
         return self.compute_mode(obs), 0.
 
     def compute_obj_v(self, obs):                      # utils/policy.py:100-103
