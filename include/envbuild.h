@@ -20,6 +20,15 @@
  *   - a handle is bound to one device and is not thread-safe; distinct handles are independent.
  *   - launches are asynchronous on `stream` (a hipStream_t; NULL = the HIP null stream);
  *     eb_sync() blocks until all work on the handle's device is done.
+ *   - stream capture: every entry that takes a `stream`, in this header and in the envbuild_*.h next to it, enqueues kernel launches
+ *     on that stream and nothing else (no allocation, copy, memset, host read or synchronisation), so it may be recorded into a
+ *     hipGraph by a capture on `stream` and replayed over the same buffers with other contents — after one ordinary call of the
+ *     same shape on that device: the opt-in to more than 48 KB of LDS is made per kernel at its first launch and is not a
+ *     capturable operation.  Not to be captured: eb_rollout_gated and eb_gate_feed (each spins on flags the other raises on another
+ *     stream: a replay without its partner never ends), eb_plan_launch (itself a graph launch), eb_event_record (a timing event
+ *     of the library's own), and eb_env_step / eb_env_reset_pool when they take their separate-launch paths (an unaligned array,
+ *     a tile beyond the LDS): those allocate scratch in stream order (hipMallocAsync / hipFreeAsync; eb_env_reset_pool also copies
+ *     rows with hipMemcpyAsync), which a capture may or may not accept.
  *   - all floating point is IEEE fp32, evaluated op-for-op in the reference's order with no FMA
  *     contraction; sin/cos/atan use the deterministic kernels documented in DESIGN.md so that
  *     the HIP path and the oracle agree bit-for-bit.

@@ -1,0 +1,206 @@
+"""GPU (-m gpu): every row of tests/_capture_cases.CAPTURED off the null stream.  The headers promise that launches are asynchronous
+on `stream` and, per family, how many there are; on the null stream — where every other test of the suite runs — a launch that
+dropped its stream argument, a helper launch on stream 0 or one launch too many computes the same numbers.  Here each row is
+(1) run on the null stream with two sets of contents A and B (the launches the rest of the suite holds to the oracle, the fixtures and
+the float64 restatements: the yardstick), (2) run on a side stream, (3) captured on that stream — nothing may execute, and the graph
+must hold exactly the stated kernel nodes, in one chain — and (4) replayed twice over the same buffers with B in them.  Every
+comparison is bit equality between two ways of launching the same entry; there is no tolerance.  The last test does the same for
+three façade calls under torch.cuda.graph."""
+import collections
+import functools
+
+import numpy as np
+import pytest
+
+from tests._capture import CaptureError, capture, side_stream
+from tests._capture_cases import CAPTURED, UNSPECIFIED, expected_kernels
+from tests._policy import SENTINEL, same
+
+pytestmark = pytest.mark.gpu
+ROWS = list(CAPTURED)
+
+
+def load(call, contents):
+    for k, t in call.inputs.items():
+        t.copy_(contents[k])
+
+
+def poison(call):
+    """SENTINEL into every float output, the byte 0xA5 into every other (flags, codes, fp16 rows, workspaces)"""
+    import torch
+    for t in call.outputs.values():
+        if t.is_floating_point():
+            t.fill_(SENTINEL)
+        else:
+            t.view(torch.uint8).fill_(0xA5)
+
+
+def snap(call):
+    """every buffer of the call — the outputs, and the inputs too: an in-place state buffer is both — as bytes on the host"""
+    import torch
+    torch.cuda.synchronize()
+    return {k: t.contiguous().view(torch.uint8).cpu().numpy() for k, t in list(call.inputs.items()) + list(call.outputs.items())}
+
+
+def differing(got, want, skip=UNSPECIFIED):
+    return sorted(k for k in want if k not in skip and not same(got[k], want[k]))
+
+
+@functools.lru_cache(maxsize=None)
+def observe(key):
+    """steps 1-4 for every size of the row, once -> [(size, observations)], or the exception that ended it"""
+    import torch
+    try:
+        r, side, out = CAPTURED[key], side_stream(), []
+        for size in r.sizes:
+            a, b = r.make(size, 'A'), r.make(size, 'B')
+            A, B = a.initial, b.initial
+            assert list(A) == list(B) and all(A[k].shape == B[k].shape and A[k].dtype == B[k].dtype for k in A), (key, size)
+            o = {'other contents': any(not torch.equal(A[k], B[k]) for k in A)}
+            del b
+            want = {}
+            for name, contents in (('A', A), ('B', B)):          # 1: the yardstick
+                load(a, contents), poison(a)
+                a.run(None)
+                want[name] = snap(a)
+            as_made = {k: t.contiguous().view(torch.uint8).cpu().numpy() for k, t in A.items()}
+            written = set(a.outputs) | {k for k in A if not same(want['A'][k], as_made[k])}     # outputs and in-place state
+            o['results differ'] = any(k in written for k in differing(want['A'], want['B']))
+            load(a, A), poison(a)                                  # 2: the side stream, eagerly (and the warm-up of the capture)
+            torch.cuda.synchronize()
+            a.run(side.cuda_stream)
+            o['eager'] = differing(snap(a), want['A'])
+            load(a, A), poison(a)                                  # 3: capture
+            before = snap(a)
+            cap = capture(side, a.run, '%s %s' % (key, size))
+            try:
+                o['touched by the capture'] = differing(snap(a), before, skip=())
+                o['nodes'], o['chain'] = cap.node_types(), cap.is_chain()
+                for rep in (1, 2):                                 # 4: replays with other contents
+                    load(a, B), poison(a)
+                    torch.cuda.synchronize()
+                    cap.replay()
+                    o['replay %d' % rep] = differing(snap(a), want['B'])
+            finally:
+                cap.close()
+            print('%-48s %-22s %s' % (key, size, dict(o['nodes'])))
+            out.append((size, o))
+        return out
+    except Exception as e:              # noqa: BLE001  (kept: the four tests of a row report it, the row is not run four times)
+        return e
+
+
+def observed(key):
+    res = observe(key)
+    if isinstance(res, Exception):
+        raise res
+    return res
+
+
+@pytest.mark.parametrize('key', ROWS)
+def test_side_stream_gives_the_null_streams_bits(key):
+    for size, o in observed(key):
+        assert o['other contents'] and o['results differ'], '%s %s: A and B do not tell two runs apart' % (key, size)
+        assert not o['eager'], '%s %s on a side stream: %s differ from the null-stream run' % (key, size, o['eager'])
+
+
+@pytest.mark.parametrize('key', ROWS)
+def test_capture_executes_nothing_and_holds_the_stated_nodes(key):
+    r = CAPTURED[key]
+    for size, o in observed(key):
+        assert not o['touched by the capture'], '%s %s: %s changed while the call was being captured' % (key, size, o['touched by the capture'])
+        assert o['chain'], '%s %s: the captured graph is not a single chain' % (key, size)
+        others = collections.Counter(kind for kind, _ in r.other_nodes)
+        assert {k: v for k, v in o['nodes'].items() if k != 'kernel'} == dict(others), '%s %s: nodes %s' % (key, size, dict(o['nodes']))
+        if r.kernels is not None:
+            counts = {}
+            if isinstance(r.kernels, tuple):
+                counts[r.kernels[1]] = {s['n']: q['nodes']['kernel'] for s, q in observed(r.kernels[1])}[size['n']]
+            k = expected_kernels(r, size, counts)
+            assert o['nodes']['kernel'] == k, '%s %s: %d kernel nodes, the header says %d' % (key, size, o['nodes']['kernel'], k)
+
+
+@pytest.mark.parametrize('key', ROWS)
+def test_kernel_count_does_not_depend_on_the_batch(key):
+    by_shape = collections.defaultdict(set)
+    for size, o in observed(key):
+        by_shape[tuple(sorted((k, v) for k, v in size.items() if k != 'n'))].add(o['nodes']['kernel'])
+    if CAPTURED[key].kernels is None or isinstance(CAPTURED[key].kernels, (int, tuple)):
+        assert all(len(v) == 1 for v in by_shape.values()), '%s: kernel nodes by shape %s' % (key, dict(by_shape))
+
+
+@pytest.mark.parametrize('key', ROWS)
+def test_replays_compute_what_the_buffers_hold(key):
+    for size, o in observed(key):
+        for rep in (1, 2):
+            assert not o['replay %d' % rep], '%s %s: replay %d with B in the buffers: %s differ from the null-stream run' % (
+                key, size, rep, o['replay %d' % rep])
+
+
+@pytest.mark.filterwarnings('ignore:The CUDA Graph is empty')
+def test_a_failed_capture_names_the_entry_and_leaves_the_stream_usable():
+    import torch
+    side = side_stream()
+
+    def refused(raw_stream):
+        raise ValueError('envbuild(hip): eb_example: bad argument')
+    with pytest.raises(CaptureError, match='eb_example row.*eb_example: bad argument'):
+        capture(side, refused, 'eb_example row')
+    assert not torch.cuda.is_current_stream_capturing()
+    with torch.cuda.stream(side):
+        t = torch.full((8,), 2.0, device='cuda') * 3.0
+    side.synchronize()
+    assert bool((t == 6.0).all())
+
+
+def test_facade_calls_read_the_current_stream_per_call():
+    """MLPNet.call, policy_sample.sample_actions (fp32 net, drawn noise, logp) and OpenLoopMPC.value_and_grad — the tape value-and-
+    gradient launch, no autograd — under `with torch.cuda.stream(side)` and a torch.cuda.graph on that stream: the replays give the eager
+    side-stream bits for whatever the static inputs hold, which they could not if the façade had cached the stream it first saw"""
+    import torch
+    from env_build_amd import policy_sample as ps
+    from env_build_amd.dynamics_and_models import _unwrap
+    from env_build_amd.policy import MLPNet
+    from tests._tape import mpc_setup
+    from tests.test_gpu_policy_sample import make_net
+    net, _, _ = make_net((41, 2, 64, 4, 'elu', 'linear'), True)
+    _, model, mpc, obs0, ref = mpc_setup('left')
+    n, H, B = 65, mpc.horizon, obs0.shape[0]
+    gen = torch.Generator(device='cuda').manual_seed(7)
+    sets = {name: (torch.randn((n, 41), device='cuda', generator=gen), obs0.roll(shift, 0).contiguous(), ref.roll(shift, 0).contiguous(),
+                   0.5 * torch.randn((H, B, 2), device='cuda', generator=gen)) for name, shift in (('A', 0), ('B', 1))}
+    static = [t.clone() for t in sets['A']]
+
+    def work():
+        x, obs, ri, u = static
+        s = ps.sample_actions(net, x, 1.0, None, 0x1234567, 5, want=('logp',))
+        J, g, out5 = mpc.value_and_grad(obs, u, ri, 0)
+        return [_unwrap(MLPNet.call(net, x)), _unwrap(s['actions']), _unwrap(s['logp']), J, g, out5]
+
+    def fill(name):
+        for t, v in zip(static, sets[name]):
+            t.copy_(v)
+
+    side = side_stream()
+    torch.cuda.synchronize()
+    want = {}
+    with torch.cuda.stream(side):
+        for name in ('A', 'B', 'A'):                  # (also the warm-up PyTorch's recipe asks for)
+            fill(name)
+            want[name] = [t.clone() for t in work()]
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
+            outs = work()
+        try:
+            for name in ('B', 'A', 'A'):
+                fill(name)
+                for t in outs:
+                    t.fill_(SENTINEL)
+                graph.replay()
+                side.synchronize()
+                for k, (got, w) in enumerate(zip(outs, want[name])):
+                    assert same(got.cpu().numpy().view(np.uint32), w.cpu().numpy().view(np.uint32)), 'output %d, contents %s' % (k, name)
+            assert not same(want['A'][0].cpu().numpy(), want['B'][0].cpu().numpy())
+        finally:
+            graph.reset()
+    torch.cuda.synchronize()
