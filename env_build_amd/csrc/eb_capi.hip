@@ -37,6 +37,8 @@
 #include "eb_policy_rollout_grad.h"
 #include "../../include/envbuild_policy_sample.h"
 #include "eb_policy_sample.h"
+#include "../../include/envbuild_policy_rollout_sample.h"
+#include "eb_policy_rollout_sample.h"
 #include "eb_grad.h"
 #include "eb_kernels.h"
 
@@ -2571,6 +2573,155 @@ int eb_policy_rollout_grad(eb_handle h, eb_mlp policy, int32_t n_env, int32_t st
     A.tape_off = tape_off;
     EB_HIP(eb::launch_policy_rollout_grad(h->cfg.task, A, (hipStream_t)stream));
     if (g_params) EB_HIP(eb::launch_mlp_wgrad(G, (hipStream_t)stream));
+    return EB_OK;
+}
+
+}  // extern "C"
+
+// ---- include/envbuild_policy_rollout_sample.h: the stochastic closed-loop rollout and its reparameterised gradient
+//      (eb_policy_rollout_sample.hip) ----
+// the first condition of eb_policy_rollout_sample_supported's list this pair of handles does not meet, in g_err, as the code to return;
+// EB_OK when there is none.  The list is policy_rollout_grad_fits', under this entry's name.
+static int policy_rollout_sample_fits(eb_handle h, eb_mlp m) {
+    const int D = obs_dim(h->cfg);
+    if (m->precision != EB_MLP_PRECISION_F32)
+        return fail(EB_EINVAL, "eb_policy_rollout_sample: the policy's precision must be EB_MLP_PRECISION_F32 (an fp16 handle has no fused "
+                               "stochastic rollout: eb_mlp_forward, eb_policy_sample_from_logits and eb_rollout_step per step)");
+    if (m->units > eb::MLP_GRAD_MAX_UNITS)
+        return fail_limit("eb_policy_rollout_sample: hidden width %d pads to %d, beyond the kernels' limit of %d", (int)m->cfg.n_units, m->units,
+                          eb::MLP_GRAD_MAX_UNITS);
+    if (m->cfg.obs_dim != D) return fail_limit("eb_policy_rollout_sample: the policy's obs_dim %d is not the model's %d", (int)m->cfg.obs_dim, D);
+    if (m->cfg.out_dim != 4)
+        return fail_limit("eb_policy_rollout_sample: the policy's out_dim %d is not 4 (mean and log-std of two actions)", (int)m->cfg.out_dim);
+    if (h->cfg.n_veh > eb::PRG_MAX_VEH)
+        return fail_limit("eb_policy_rollout_sample: n_veh %d exceeds the kernel's limit of %d vehicle slots", (int)h->cfg.n_veh, eb::PRG_MAX_VEH);
+    if (h->cfg.n_future != 0)
+        return fail_limit("eb_policy_rollout_sample: n_future %d is not supported (0, the reference's default)", (int)h->cfg.n_future);
+    if (m->cfg.device != h->cfg.device) return fail(EB_EINVAL, "eb_policy_rollout_sample: policy and model live on different devices");
+    const size_t lds = eb::policy_rollout_sample_lds_bytes(D, h->cfg.n_veh, std::max(m->k_pad0, m->units) + 4);
+    if (lds > eb::policy_rollout_sample_lds_limit())
+        return fail_limit("eb_policy_rollout_sample: a block needs %zu bytes of LDS, a compute unit has %zu for it", lds,
+                          eb::policy_rollout_sample_lds_limit());
+    if (m->layers_set != (1u << (m->cfg.n_hidden + 1)) - 1u)
+        return fail(EB_ESTATE, "eb_policy_rollout_sample: a layer was never set (eb_mlp_set_layer for every layer, or eb_mlp_set_params_device)");
+    return EB_OK;
+}
+
+// n_env and steps against the entry's caps; the rows of the row reduction in *rows
+static int policy_rollout_sample_shape(int32_t n_env, int32_t steps, long long* n_pad, long long* rows) {
+    if (n_env < 0) return fail(EB_EINVAL, "eb_policy_rollout_sample: n_env < 0");
+    if (steps < 1 || steps > EB_POLICY_ROLLOUT_SAMPLE_MAX_STEPS)
+        return fail_limit("eb_policy_rollout_sample: steps %d is outside 1 .. %d", (int)steps, EB_POLICY_ROLLOUT_SAMPLE_MAX_STEPS);
+    *n_pad = ((long long)n_env + eb::MLP_ROWS - 1) / eb::MLP_ROWS * eb::MLP_ROWS;
+    *rows = *n_pad * steps;
+    if (*rows > eb::PRG_MAX_ROWS)
+        return fail_limit("eb_policy_rollout_sample: %d steps x %lld padded envs are %lld rows, one row reduction takes %lld: split the batch",
+                          (int)steps, *n_pad, *rows, eb::PRG_MAX_ROWS);
+    return EB_OK;
+}
+
+// the row reduction's arguments (head 0: the logits' cotangent) and the workspace's size: mlp_grad_layout for `rows` rows, then the tape
+static size_t policy_rollout_sample_layout(eb_mlp m, long long rows, eb::MlpGradArgs* G, long long* tape_off) {
+    mlp_grad_args(m, (int32_t)rows, eb::MLP_HEAD_LOGITS, 0.0f, G);
+    const size_t mlp_bytes = eb::mlp_grad_layout(*G);
+    *tape_off = (long long)(mlp_bytes / sizeof(float));
+    return mlp_bytes + (size_t)rows * eb::PRS_TAPE_FLOATS * sizeof(float);
+}
+
+extern "C" {
+
+int eb_policy_rollout_sample_abi_version(void) { return EB_POLICY_ROLLOUT_SAMPLE_ABI_VERSION; }
+
+int eb_policy_rollout_sample_supported(eb_handle h, eb_mlp policy, int32_t* ok) {
+    if (!h) return fail(EB_EINVAL, "eb_policy_rollout_sample_supported: null handle");
+    if (!policy) return fail(EB_EINVAL, "eb_policy_rollout_sample_supported: null policy");
+    if (!ok) return fail(EB_EINVAL, "eb_policy_rollout_sample_supported: null output pointer");
+    *ok = policy_rollout_sample_fits(h, policy) == EB_OK ? 1 : 0;
+    return EB_OK;
+}
+
+int eb_policy_rollout_sample_workspace_bytes(eb_handle h, eb_mlp policy, int32_t n_env, int32_t steps, int32_t with_grad, size_t* bytes) {
+    if (!h) return fail(EB_EINVAL, "eb_policy_rollout_sample_workspace_bytes: null handle");
+    if (!policy) return fail(EB_EINVAL, "eb_policy_rollout_sample_workspace_bytes: null policy");
+    if (!bytes) return fail(EB_EINVAL, "eb_policy_rollout_sample_workspace_bytes: null output pointer");
+    int rc = policy_rollout_sample_fits(h, policy);
+    if (rc) return rc;
+    long long n_pad, rows;
+    rc = policy_rollout_sample_shape(n_env, steps, &n_pad, &rows);
+    if (rc) return rc;
+    eb::MlpGradArgs G;
+    long long tape_off;
+    *bytes = (n_env == 0 || !with_grad) ? 0 : policy_rollout_sample_layout(policy, rows, &G, &tape_off);
+    return EB_OK;
+}
+
+int eb_policy_rollout_sample(eb_handle h, eb_mlp policy, const eb_policy_rollout_sample_args* a) {
+    // the arguments themselves first: neither handle is looked at before the struct is known to be this version's
+    if (!h) return fail(EB_EINVAL, "eb_policy_rollout_sample: null handle");
+    if (!policy) return fail(EB_EINVAL, "eb_policy_rollout_sample: null policy");
+    if (!a) return fail(EB_EINVAL, "eb_policy_rollout_sample: null args");
+    if (a->struct_size != sizeof(eb_policy_rollout_sample_args))
+        return fail_limit("eb_policy_rollout_sample: args->struct_size is %u, sizeof(eb_policy_rollout_sample_args) is %zu",
+                          (unsigned)a->struct_size, sizeof(eb_policy_rollout_sample_args));
+    int rc = check_tape(h, "eb_policy_rollout_sample: null handle");
+    if (rc) return rc;
+    rc = policy_rollout_sample_fits(h, policy);
+    if (rc) return rc;
+    const int32_t n_env = a->n_env, steps = a->steps;
+    long long n_pad, rows;
+    rc = policy_rollout_sample_shape(n_env, steps, &n_pad, &rows);
+    if (rc) return rc;
+    if (a->action_range != a->action_range || a->w_logp != a->w_logp)
+        return fail(EB_EINVAL, "eb_policy_rollout_sample: action_range or w_logp is NaN");
+    const bool with_grad = a->g_actions_steps || a->g_obs0 || a->g_params;
+    eb::MlpGradArgs G;
+    long long tape_off = 0;
+    const size_t need = policy_rollout_sample_layout(policy, rows, &G, &tape_off);
+    G.g_params = a->g_params;
+    hipStream_t stream = (hipStream_t)a->stream;
+    if (n_env == 0) {                                                           // zero rows: the reduce kernel writes zeros, nothing else runs
+        if (!a->g_params) return EB_OK;
+        EB_HIP(hipSetDevice(h->cfg.device));
+        EB_HIP(eb::launch_mlp_wgrad(G, stream));
+        return EB_OK;
+    }
+    if (!a->obs_in) return fail(EB_EINVAL, "eb_policy_rollout_sample: null obs_in");
+    if (a->obs_out == a->obs_in) return fail(EB_EINVAL, "eb_policy_rollout_sample: obs_out must not alias obs_in");
+    if (with_grad && !a->workspace) return fail(EB_EINVAL, "eb_policy_rollout_sample: null workspace with a gradient asked for");
+    if (with_grad && a->workspace_bytes < need)
+        return fail_limit("eb_policy_rollout_sample: the workspace holds %zu bytes, %d envs x %d steps need %zu "
+                          "(eb_policy_rollout_sample_workspace_bytes)", a->workspace_bytes, (int)n_env, (int)steps, need);
+    const int32_t* ref_idx = a->ref_idx;
+    int32_t path_id = a->path_id;
+    rc = check_path_arg(h, &ref_idx, &path_id);
+    if (rc) return rc;
+    EB_HIP(hipSetDevice(h->cfg.device));
+    eb::PolicyRolloutSampleArgs A;
+    std::memset(static_cast<void*>(&A), 0, sizeof A);
+    fill_tape_scene(h, n_env, steps, A);
+    A.obs0 = a->obs_in; A.ref_idx = ref_idx; A.path_id = path_id;
+    A.obs_out = a->obs_out; A.out5_steps = a->out5_steps; A.actions_steps = a->actions_steps; A.obs_steps = a->obs_steps; A.cost = a->cost;
+    A.g_actions_steps = a->g_actions_steps; A.g_obs0 = a->g_obs0;
+    A.nv_magic = eb::div_magic(A.n_veh);
+    A.n_pad = (int)n_pad;
+    for (int k = 0; k < 5; ++k) A.w5[k] = a->w5[k];
+    // the policy, as mlp_grad_args hands it to the backward's kernels
+    const eb::MlpArgs& F = G.fwd;
+    A.scale = F.scale; A.n_hidden = F.n_hidden; A.units = F.units; A.hidden_act = F.hidden_act; A.out_act = F.out_act;
+    A.action_range = a->action_range; A.row_stride = F.row_stride; A.kt_out = G.kt_out;
+    for (int L = 0; L < eb::MLP_MAX_HIDDEN; ++L) A.hid[L] = F.hid[L];
+    A.outl = F.outl;
+    G.ws = A.ws = with_grad ? static_cast<float*>(a->workspace) : nullptr;
+    for (int L = 0; L < eb::MLP_GRAD_LAYERS; ++L) { A.wt[L] = G.wt[L]; A.x_off[L] = G.x_off[L]; A.d_off[L] = G.d_off[L]; }
+    A.tape_off = tape_off;
+    // the sampling head, as policy_sample_head fills eb_policy_sample's
+    A.row_ids = a->row_ids; A.eps_steps = a->eps_steps; A.logp_steps = a->logp_steps; A.eps_out_steps = a->eps_out_steps;
+    A.seed = a->seed; A.counter = a->counter;
+    A.log_ar = a->action_range > 0.0f ? (float)std::log((double)a->action_range) : 0.0f;
+    A.w_logp = a->w_logp;
+    A.with_grad = with_grad ? 1 : 0;
+    EB_HIP(eb::launch_policy_rollout_sample(h->cfg.task, A, stream));
+    if (a->g_params) EB_HIP(eb::launch_mlp_wgrad(G, stream));
     return EB_OK;
 }
 

@@ -8,7 +8,9 @@ since the last upload (its `_version`): no host copy, no synchronisation, one po
 `policy_rollout` and `HierarchicalDecision`, at either precision; differentiating needs precision 'fp32'.
 
 `rollout_loss` is the ADP loss of a whole closed-loop rollout under a `TrainableMLPNet` as ONE autograd node: value and parameter
-gradient come from eb_policy_rollout_grad (include/envbuild_policy_rollout_grad.h) in its forward.
+gradient come from eb_policy_rollout_grad (include/envbuild_policy_rollout_grad.h) in its forward.  `rollout_loss_sampled` is the
+maximum-entropy form under the stochastic head, J = sum of cost + w_logp * sum of log pi, through eb_policy_rollout_sample
+(include/envbuild_policy_rollout_sample.h).
 
 `mlp_backward_reference` restates the header's contract in NumPy.  There is no CPU path for the network itself.
 """
@@ -22,7 +24,7 @@ from . import _capi
 from .dynamics_and_models import _dev
 from .policy import MLPNet, _act_det, _tanh_det
 
-__all__ = ['TrainableMLPNet', 'mlp_backward_reference', 'rollout_loss']
+__all__ = ['TrainableMLPNet', 'mlp_backward_reference', 'rollout_loss', 'rollout_loss_sampled']
 
 
 def _act(act, x, dtype):
@@ -305,3 +307,59 @@ def rollout_loss(model, net, obs0, ref_idx, horizon, w5, action_range=1.0, fused
         model.api.policy_rollout_grad_supported(model.handle, net._handle, C.byref(ok))
         fused = bool(ok.value)
     return _RolloutLoss.apply(model, net, steps, w5, action_range, bool(fused), *net._params)
+
+
+class _RolloutLossSampled(torch.autograd.Function):
+    """J = sum of cost + w_logp * sum of logp of the stochastic rollout; the entry runs in forward and leaves dJ/dtheta for backward"""
+
+    @staticmethod
+    def forward(ctx, model, net, steps, w5, w_logp, action_range, eps, seed, counter, fused, *params):
+        from .policy_rollout import _composed_sample, _fused_sample
+        net._sync()
+        run = _fused_sample if fused else _composed_sample
+        out = run(model, net, -1.0 if action_range is None else float(action_range), steps, w5, w_logp, eps, seed, counter, None,
+                  ('cost', 'logp', 'g_params'))
+        ctx.g_flat = out['g_params']
+        ctx.slices = net._slices
+        ctx.mark_non_differentiable(out['logp_steps'])
+        return out['cost'].sum() + w_logp * out['logp_steps'].sum(), out['logp_steps']
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_logp):
+        flat = ctx.g_flat * g
+        return (None,) * 10 + tuple(flat[a:b].view(shape) for a, b, shape in ctx.slices)
+
+
+def rollout_loss_sampled(model, net, obs0, ref_idx, horizon, w5, w_logp, seed, counter, eps=None, action_range=1.0, fused=None,
+                         return_logp=False):
+    """J = sum over envs of cost + w_logp * sum over envs and steps of log pi(a_t | obs_t), for the closed-loop rollout of `horizon`
+    steps of `model` under the STOCHASTIC head of the TrainableMLPNet `net`: step t samples with (seed, counter + t), or takes eps
+    [horizon, B, 2] as its noise.  A scalar tensor on the autograd graph whose backward hands upstream * dJ/dtheta — the
+    reparameterised gradient, the noise held fixed — to the network's parameters.  Maximum-entropy ADP is w5 = (-1, lam, 0, 0, 0) /
+    (horizon * B) and w_logp = alpha / (horizon * B).  return_logp: also logp_steps [horizon, B] (not differentiable).
+
+    One autograd node: eb_policy_rollout_sample runs in the forward (three launches whatever the horizon) and the gradient is complete
+    when forward returns; the `_sync()` / `_version` rule is rollout_loss's.  fused=None takes the one-call entry where
+    eb_policy_rollout_sample_supported says yes, the composed loop of single entries elsewhere."""
+    from . import policy_rollout as pr
+    if not isinstance(net, TrainableMLPNet):
+        raise TypeError('rollout_loss_sampled differentiates a TrainableMLPNet, got %s' % type(net).__name__)
+    steps = int(horizon)
+    if steps < 1:
+        raise ValueError('horizon must be at least 1')
+    w5 = pr._w5(w5)
+    model.reset(obs0.detach() if isinstance(obs0, torch.Tensor) else obs0, ref_idx)
+    B = pr._unwrap(model.obses).shape[0]
+    e = None
+    if eps is not None:
+        e = (eps if isinstance(eps, torch.Tensor) else torch.as_tensor(eps)).detach().to(device=model.device, dtype=torch.float32).contiguous()
+        if tuple(e.shape) != (steps, B, 2):
+            raise ValueError('eps must be [%d, %d, 2], got %s' % (steps, B, tuple(e.shape)))
+    if fused is None:
+        ok = C.c_int32(0)
+        pr._sample_call(model.api, 'eb_policy_rollout_sample_supported', model.handle, net._handle, C.byref(ok))
+        fused = bool(ok.value)
+    loss, logp = _RolloutLossSampled.apply(model, net, steps, w5, float(w_logp), action_range, e, int(seed), int(counter), bool(fused),
+                                           *net._params)
+    return (loss, logp) if return_logp else loss
