@@ -37,6 +37,8 @@
 #include "eb_policy_rollout_grad.h"
 #include "../../include/envbuild_policy_sample.h"
 #include "eb_policy_sample.h"
+#include "../../include/envbuild_policy_logp.h"
+#include "eb_policy_logp.h"
 #include "../../include/envbuild_policy_rollout_sample.h"
 #include "eb_policy_rollout_sample.h"
 #include "eb_grad.h"
@@ -2442,6 +2444,86 @@ int eb_policy_sample_vjp(int32_t n, int32_t out_dim, const float* logits, const 
     if (n == 0) return EB_OK;
     const eb::PolicySampleVjpArgs A{logits, eps, g_actions, g_logp, g_logits, n, out_dim, action_range};
     EB_HIP(eb::launch_policy_sample_vjp(A, (hipStream_t)stream));
+    return EB_OK;
+}
+
+}  // extern "C"
+
+// ---- include/envbuild_policy_logp.h: the log-probability of given actions (eb_policy_logp.hip) ----
+// the first condition of eb_policy_logp's list this handle does not meet (eb_policy_sample's list), in g_err, as the code to return
+static int policy_logp_fits(eb_mlp m) {
+    if (m->precision != EB_MLP_PRECISION_F32)
+        return fail(EB_EINVAL, "eb_policy_logp: the handle's precision must be EB_MLP_PRECISION_F32 (an fp16 handle goes through "
+                               "eb_mlp_forward and eb_policy_logp_from_logits)");
+    if (m->cfg.out_dim < 2 || (m->cfg.out_dim & 1)) return fail(EB_EINVAL, "eb_policy_logp: out_dim must be 2 * act_dim");
+    if (m->layers_set != (1u << (m->cfg.n_hidden + 1)) - 1u)
+        return fail(EB_ESTATE, "eb_policy_logp: a layer was never set (eb_mlp_set_layer for every layer, or eb_mlp_set_params_device)");
+    return EB_OK;
+}
+
+// the checks the fused entry and the epilogue alone share, and the head both launches take
+static int policy_logp_head(const char* who, const eb_policy_logp_args* a, int32_t out_dim, eb::PolicyLogpHead* H) {
+    if (a->n < 0 || out_dim < 2 || out_dim > 32 || (out_dim & 1) || (a->n > 0 && (!a->actions || !a->logp)) ||
+        a->action_range != a->action_range) {
+        std::snprintf(g_err, sizeof g_err, "%s: bad argument (n >= 0, out_dim even in 2..32, actions, logp, action_range not NaN)", who);
+        return EB_EINVAL;
+    }
+    H->actions = a->actions;
+    H->action_range = a->action_range;
+    H->log_ar = a->action_range > 0.0f ? (float)std::log((double)a->action_range) : 0.0f;
+    H->logp = a->logp; H->z_out = a->z_out;
+    return EB_OK;
+}
+
+extern "C" {
+
+int eb_policy_logp_abi_version(void) { return EB_POLICY_LOGP_ABI_VERSION; }
+
+int eb_policy_logp_supported(eb_mlp m, int32_t* ok) {
+    if (!m) return fail(EB_EINVAL, "eb_policy_logp_supported: null handle");
+    if (!ok) return fail(EB_EINVAL, "eb_policy_logp_supported: null output pointer");
+    *ok = policy_logp_fits(m) == EB_OK ? 1 : 0;
+    return EB_OK;
+}
+
+int eb_policy_logp(eb_mlp m, const eb_policy_logp_args* a) {
+    if (!m) return fail(EB_EINVAL, "eb_policy_logp: null handle");
+    if (!a) return fail(EB_EINVAL, "eb_policy_logp: null args");
+    int rc = policy_logp_fits(m);
+    if (rc) return rc;
+    if (a->n > 0 && !a->obs) return fail(EB_EINVAL, "eb_policy_logp: null obs");
+    eb::PolicyLogpArgs A;
+    rc = policy_logp_head("eb_policy_logp", a, m->cfg.out_dim, &A.head);
+    if (rc) return rc;
+    rc = mlp_args(m, 0, nullptr, nullptr, eb::MLP_HEAD_LOGITS, a->action_range, &A.fwd, "eb_policy_logp: null handle");   // n = 0 for its checks
+    if (rc || a->n == 0) return rc;
+    A.fwd.n = a->n; A.fwd.obs = a->obs; A.fwd.out = a->logits_out;
+    EB_HIP(hipSetDevice(m->cfg.device));
+    EB_HIP(eb::launch_policy_logp(A, (hipStream_t)a->stream));
+    return EB_OK;
+}
+
+int eb_policy_logp_from_logits(const eb_policy_logp_args* a) {
+    if (!a) return fail(EB_EINVAL, "eb_policy_logp_from_logits: null args");
+    eb::PolicyLogpLogitsArgs A;
+    const int rc = policy_logp_head("eb_policy_logp_from_logits", a, a->out_dim, &A.head);
+    if (rc) return rc;
+    if (a->n > 0 && !a->logits) return fail(EB_EINVAL, "eb_policy_logp_from_logits: null logits");
+    if (a->n == 0) return EB_OK;
+    A.logits = a->logits; A.n = a->n; A.out_dim = a->out_dim;
+    EB_HIP(eb::launch_policy_logp_from_logits(A, (hipStream_t)a->stream));
+    return EB_OK;
+}
+
+int eb_policy_logp_vjp(const eb_policy_logp_args* a) {
+    if (!a) return fail(EB_EINVAL, "eb_policy_logp_vjp: null args");
+    if (a->n < 0 || a->out_dim < 2 || a->out_dim > 32 || (a->out_dim & 1))
+        return fail(EB_EINVAL, "eb_policy_logp_vjp: bad argument (n >= 0, out_dim even in 2..32)");
+    if (a->n > 0 && (!a->logits || !a->z || !a->g_logp || !a->g_logits))
+        return fail(EB_EINVAL, "eb_policy_logp_vjp: null logits, z, g_logp or g_logits");
+    if (a->n == 0) return EB_OK;
+    const eb::PolicyLogpVjpArgs A{a->logits, a->z, a->g_logp, a->g_logits, a->n, a->out_dim};
+    EB_HIP(eb::launch_policy_logp_vjp(A, (hipStream_t)a->stream));
     return EB_OK;
 }
 

@@ -286,6 +286,10 @@ class Policy4Toyota(object):
             return out['actions'], out['logp']
         return self.compute_mode(obs), 0.
 
+    def compute_logp(self, obs, actions):              # utils/policy.py:71-82: _logits2dist(logits).log_prob(actions)
+        from .policy_logp import log_prob_actions
+        return log_prob_actions(self.policy, obs, actions, getattr(self.args, 'action_range', None))['logp']
+
     def compute_obj_v(self, obs):                      # utils/policy.py:100-103
         return DevArray(self.obj_v(obs).t[:, 0])
 
