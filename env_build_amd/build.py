@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'lib', 'libenvbuild_hip.so')
 HASH_FILE = LIB + '.srchash'
 SOURCES = ['eb_capi.hip', 'eb_kernels.hip', 'eb_rollout.hip', 'eb_env_kernels.hip', 'eb_env_step.hip', 'eb_env_step_t1.hip', 'eb_env_step_t2.hip',
-           'eb_policy.hip', 'eb_rollout_vjp.hip', 'eb_rollout_tape_vjp.hip', 'eb_rollout_tape_cand.hip', 'eb_rollout_tape_cand_vjp.hip', 'eb_rollout_tape_sample.hip', 'eb_rollout_tape_ilqr.hip', 'eb_policy_f16.hip', 'eb_policy_rollout.hip', 'eb_policy_grad.hip', 'eb_policy_rollout_grad.hip', 'eb_policy_sample.hip', 'eb_policy_rollout_sample.hip', 'eb_policy_logp.hip']   # (the env step's kernels: one translation unit per task — the three compile side by side)
+           'eb_policy.hip', 'eb_rollout_vjp.hip', 'eb_rollout_tape_vjp.hip', 'eb_rollout_tape_cand.hip', 'eb_rollout_tape_cand_vjp.hip', 'eb_rollout_tape_sample.hip', 'eb_rollout_tape_ilqr.hip', 'eb_policy_f16.hip', 'eb_policy_rollout.hip', 'eb_policy_grad.hip', 'eb_policy_rollout_grad.hip', 'eb_policy_sample.hip', 'eb_policy_rollout_sample.hip', 'eb_policy_logp.hip', 'eb_ppo.hip']   # (the env step's kernels: one translation unit per task — the three compile side by side)
 HEADERS = ['eb_device.h', 'eb_kernels.h', 'eb_mlp_device.h', 'eb_env_device.h', 'eb_env_step_body.h', os.path.join('..', '..', 'include', 'envbuild.h'),
            'eb_grad.h', 'eb_grad_device.h', 'eb_tape_grad_device.h', 'eb_tape_device.h', os.path.join('..', '..', 'include', 'envbuild_grad.h'),
            'eb_cand.h', os.path.join('..', '..', 'include', 'envbuild_cand.h'),
@@ -31,7 +31,8 @@ HEADERS = ['eb_device.h', 'eb_kernels.h', 'eb_mlp_device.h', 'eb_env_device.h', 
            os.path.join('..', '..', 'include', 'envbuild_policy_rollout_grad.h'),
            'eb_policy_sample.h', 'eb_policy_sample_device.h', os.path.join('..', '..', 'include', 'envbuild_policy_sample.h'),
            'eb_policy_rollout_sample.h', os.path.join('..', '..', 'include', 'envbuild_policy_rollout_sample.h'),
-           'eb_policy_head_device.h', 'eb_policy_logp.h', 'eb_policy_logp_device.h', os.path.join('..', '..', 'include', 'envbuild_policy_logp.h')]
+           'eb_policy_head_device.h', 'eb_policy_logp.h', 'eb_policy_logp_device.h', os.path.join('..', '..', 'include', 'envbuild_policy_logp.h'),
+           'eb_ppo.h', 'eb_ppo_device.h', os.path.join('..', '..', 'include', 'envbuild_ppo.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fno-fast-math',
          '-fPIC', '-Wno-unused-value', '-Wno-pass-failed',
          '-mllvm', '-amdgpu-kernarg-preload-count=14']   # the rollout kernel's leading arguments (14 dwords: all of FusedHot) arrive in SGPRs

@@ -39,6 +39,8 @@
 #include "eb_policy_sample.h"
 #include "../../include/envbuild_policy_logp.h"
 #include "eb_policy_logp.h"
+#include "../../include/envbuild_ppo.h"
+#include "eb_ppo.h"
 #include "../../include/envbuild_policy_rollout_sample.h"
 #include "eb_policy_rollout_sample.h"
 #include "eb_grad.h"
@@ -2524,6 +2526,91 @@ int eb_policy_logp_vjp(const eb_policy_logp_args* a) {
     if (a->n == 0) return EB_OK;
     const eb::PolicyLogpVjpArgs A{a->logits, a->z, a->g_logp, a->g_logits, a->n, a->out_dim};
     EB_HIP(eb::launch_policy_logp_vjp(A, (hipStream_t)a->stream));
+    return EB_OK;
+}
+
+}  // extern "C"
+
+// ---- include/envbuild_ppo.h: the clipped surrogate and generalised advantage estimation (eb_ppo.hip) ----
+// the first condition of eb_ppo_surrogate's list this handle does not meet (eb_policy_logp's list), in g_err, as the code to return
+static int ppo_fits(eb_mlp m) {
+    if (m->precision != EB_MLP_PRECISION_F32)
+        return fail(EB_EINVAL, "eb_ppo_surrogate: the handle's precision must be EB_MLP_PRECISION_F32 (an fp16 handle goes through "
+                               "eb_mlp_forward and eb_ppo_surrogate_from_logits)");
+    if (m->cfg.out_dim < 2 || (m->cfg.out_dim & 1)) return fail(EB_EINVAL, "eb_ppo_surrogate: out_dim must be 2 * act_dim");
+    if (m->layers_set != (1u << (m->cfg.n_hidden + 1)) - 1u)
+        return fail(EB_ESTATE, "eb_ppo_surrogate: a layer was never set (eb_mlp_set_layer for every layer, or eb_mlp_set_params_device)");
+    return EB_OK;
+}
+
+// the checks the fused entry and the row alone share, and the head both launches take
+static int ppo_head(const char* who, const eb_ppo_args* a, int32_t out_dim, eb::PpoHead* H) {
+    if (a->n < 0 || out_dim < 2 || out_dim > 32 || (out_dim & 1) || (a->n > 0 && (!a->actions || !a->logp_old || !a->adv || !a->logp)) ||
+        a->action_range != a->action_range || !(a->clip >= 0.0f) || a->ent_coef != a->ent_coef || a->scale != a->scale) {
+        std::snprintf(g_err, sizeof g_err, "%s: bad argument (n >= 0, out_dim even in 2..32, actions, logp_old, adv, logp, clip >= 0, "
+                                           "action_range, clip, ent_coef and scale not NaN)", who);
+        return EB_EINVAL;
+    }
+    H->actions = a->actions; H->logp_old = a->logp_old; H->adv = a->adv; H->adv_norm = a->adv_norm;
+    H->action_range = a->action_range;
+    H->log_ar = a->action_range > 0.0f ? (float)std::log((double)a->action_range) : 0.0f;
+    H->lo = 1.0f - a->clip; H->hi = 1.0f + a->clip;
+    H->w = -a->scale;
+    H->g_ent = -(a->scale * a->ent_coef);
+    H->logp = a->logp; H->ratio = a->ratio; H->surr = a->surr; H->ent = a->ent; H->g_logits = a->g_logits; H->z_out = a->z_out;
+    return EB_OK;
+}
+
+extern "C" {
+
+int eb_ppo_abi_version(void) { return EB_PPO_ABI_VERSION; }
+
+int eb_ppo_surrogate_supported(eb_mlp m, int32_t* ok) {
+    if (!m) return fail(EB_EINVAL, "eb_ppo_surrogate_supported: null handle");
+    if (!ok) return fail(EB_EINVAL, "eb_ppo_surrogate_supported: null output pointer");
+    *ok = ppo_fits(m) == EB_OK ? 1 : 0;
+    return EB_OK;
+}
+
+int eb_ppo_surrogate(eb_mlp m, const eb_ppo_args* a) {
+    if (!m) return fail(EB_EINVAL, "eb_ppo_surrogate: null handle");
+    if (!a) return fail(EB_EINVAL, "eb_ppo_surrogate: null args");
+    int rc = ppo_fits(m);
+    if (rc) return rc;
+    if (a->n > 0 && !a->obs) return fail(EB_EINVAL, "eb_ppo_surrogate: null obs");
+    eb::PpoArgs A;
+    rc = ppo_head("eb_ppo_surrogate", a, m->cfg.out_dim, &A.head);
+    if (rc) return rc;
+    rc = mlp_args(m, 0, nullptr, nullptr, eb::MLP_HEAD_LOGITS, a->action_range, &A.fwd, "eb_ppo_surrogate: null handle");   // n = 0 for its checks
+    if (rc || a->n == 0) return rc;
+    A.fwd.n = a->n; A.fwd.obs = a->obs; A.fwd.out = a->logits_out;
+    EB_HIP(hipSetDevice(m->cfg.device));
+    EB_HIP(eb::launch_ppo_surrogate(A, (hipStream_t)a->stream));
+    return EB_OK;
+}
+
+int eb_ppo_surrogate_from_logits(const eb_ppo_args* a) {
+    if (!a) return fail(EB_EINVAL, "eb_ppo_surrogate_from_logits: null args");
+    eb::PpoLogitsArgs A;
+    const int rc = ppo_head("eb_ppo_surrogate_from_logits", a, a->out_dim, &A.head);
+    if (rc) return rc;
+    if (a->n > 0 && !a->logits) return fail(EB_EINVAL, "eb_ppo_surrogate_from_logits: null logits");
+    if (a->n == 0) return EB_OK;
+    A.logits = a->logits; A.n = a->n; A.out_dim = a->out_dim;
+    EB_HIP(eb::launch_ppo_surrogate_from_logits(A, (hipStream_t)a->stream));
+    return EB_OK;
+}
+
+int eb_gae(const eb_gae_args* a) {
+    if (!a) return fail(EB_EINVAL, "eb_gae: null args");
+    if (a->T < 1 || a->T > 65535 || a->n < 0 || !std::isfinite(a->gamma) || !std::isfinite(a->lam))
+        return fail(EB_EINVAL, "eb_gae: bad argument (T in 1..65535, n >= 0, gamma and lam finite)");
+    if (a->n > 0 && (!a->rewards || !a->values || !a->nonterminal || !a->adv || (!a->next_values && !a->v_last)))
+        return fail(EB_EINVAL, "eb_gae: null rewards, values, nonterminal or adv, or null v_last without next_values");
+    if (a->n == 0) return EB_OK;
+    const eb::GaeArgs A{a->rewards, a->values, a->v_last, a->nonterminal, a->next_values, a->carry, (float)a->gamma,
+                        (float)((double)a->gamma * (double)a->lam), a->adv, a->ret, a->T, a->n};
+    EB_HIP(eb::launch_gae(A, (hipStream_t)a->stream));
     return EB_OK;
 }
 
