@@ -9,7 +9,9 @@ its path inside torch/lib: the same mapping, no second runtime).
 
 Every graph made here is what one stream recorded, i.e. a single chain; `is_chain()` says so from the graph's edges."""
 import collections
+import contextlib
 import ctypes as C
+import gc
 import os
 
 # hipGraphNodeType (hip_runtime_api.h)
@@ -42,6 +44,22 @@ def hip_runtime():
 def _check(rc, what):
     if rc != 0:
         raise CaptureError('%s: HIP error %d (%s)' % (what, rc, hip_runtime().hipGetErrorString(rc).decode()))
+
+
+@contextlib.contextmanager
+def no_collection():
+    """The cyclic garbage collector held off for a captured region.  A collection that falls inside one may finalise a handle some earlier
+    test left in a reference cycle (HostModel.__del__ -> eb_destroy: hipDeviceSynchronize, hipFree, hipStreamDestroy; MLPNet.__del__ ->
+    eb_mlp_destroy: hipFree) — calls a capturing thread must not make, and the process has aborted from them.  torch.cuda.graph used to
+    collect before it captured; since PyTorch 2.9 it does not (torch.compiler.config.force_cudagraph_gc).  Objects whose last reference
+    goes inside the region are still freed there, as before: that is the code under capture, not the collector's timing."""
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
 
 
 def side_stream():
@@ -106,7 +124,7 @@ def capture(stream, fn, what='call'):
     import torch
     g = torch.cuda.CUDAGraph(keep_graph=True)
     err = None
-    with torch.cuda.stream(stream):
+    with torch.cuda.stream(stream), no_collection():
         g.capture_begin(capture_error_mode='thread_local')
         try:
             fn(stream.cuda_stream)

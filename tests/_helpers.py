@@ -599,3 +599,39 @@ def max_err(a, b, rtol):
     """max over elements of |a-b| - rtol*|b| (<= atol passes)."""
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     return float(np.max(np.abs(a - b) - rtol * np.abs(b))) if a.size else 0.0
+
+
+# ---- the rollout kernels against the oracle: the start rows and the bars (tests/test_gpu_parity.py, test_gpu_gated.py,
+#      test_gpu_kernel_census.py) ----
+PEN_RTOL = 1e-6
+
+
+def initial_obs(host, inp):
+    """make_rollout_inputs' scene as observation rows, the tracking columns from the oracle"""
+    from env_build_amd.synthetic import assemble_obs
+    ego = inp['ego']
+    trk = host.tracking_error(ego[:, 3], ego[:, 4], ego[:, 5], ego[:, 0], host.n_future, ref_idx=inp['ref_idx'])
+    return assemble_obs(ego, trk, inp['veh'])
+
+
+def check_out5(o5_d, o5_h, where):
+    """rewards and veh2road4real bit for bit, the three penalty sums within PEN_RTOL"""
+    assert np.array_equal(o5_d[0], o5_h[0]), 'rewards differ %s' % where
+    assert np.array_equal(o5_d[4], o5_h[4]), 'veh2road4real differs %s' % where
+    for k in (1, 2, 3):
+        np.testing.assert_allclose(o5_d[k], o5_h[k], rtol=PEN_RTOL, atol=0, err_msg='out5[%d] %s' % (k, where))
+
+
+def stepwise(host, obs0, inp, H):
+    """H x rollout_step -> (last obs, out5 [H, 5, n], obs of every step [H, n, D])"""
+    obs, o5s, states = obs0, [], []
+    for t in range(H):
+        obs, o5, _ = host.rollout_step(obs, inp['actions'][t], inp['ref_idx'])
+        o5s.append(o5); states.append(obs)
+    return obs, np.stack(o5s), np.stack(states)
+
+
+def check_out5_steps(o5_d, o5_h):
+    """check_out5's rule over [H, 5, n]"""
+    assert np.array_equal(o5_d[:, 0], o5_h[:, 0]) and np.array_equal(o5_d[:, 4], o5_h[:, 4])
+    np.testing.assert_allclose(o5_d, o5_h, rtol=1e-6, atol=0)

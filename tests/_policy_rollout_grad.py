@@ -101,3 +101,55 @@ def rows_of(d, idx):
 
 def model(task, N, mode='training'):
     return TapeModel(task, n_veh=N, mode=mode)
+
+
+PREMISE = {('left', 8), ('right', 5), ('straight', 32)}
+
+
+def forward_and_reverse_equal_the_loop(case, sizes=(1, 63, 64, 65, 200), horizons=(1, 5, 25), only_g_params_at=5, others=True):
+    """case = (task, N, units, hidden layers, hidden activation): every per-row output of the entry equals the loop's bit for bit at
+    every batch size and horizon (tests/test_gpu_policy_rollout_grad.py and the rows of tests/test_gpu_kernel_census.py call this one
+    text); `others`: the other heads (with the output weights scaled up: raw actions beyond the clip, a blocked cotangent), no scale,
+    selecting mode — at 200 rows, 5 steps."""
+    task, N, units, n_hidden, hact = case
+    obs0, ref_idx, net, scale = scene(task, N, units, n_hidden, hact=hact)
+    dev = model(task, N)
+    m = dev.make_mlp(*net, scale)
+    assert supported(dev, m)[0] == 1
+    w5 = tuple(v / (25 * 200) for v in W5)
+    for B in sizes:
+        for steps in horizons:
+            ref = loop(dev, m, obs0[:B], steps, w5, ref_idx[:B])
+            what = '%s B=%d steps=%d' % (case, B, steps)
+            assert_equal(entry(dev, m, obs0[:B], steps, w5, ref_idx[:B]), ref, what, PER_ROW)
+            if steps == only_g_params_at:
+                only = entry(dev, m, obs0[:B], steps, w5, ref_idx[:B], want=('g_params',))
+                assert sorted(only) == ['g_params'] and np.all(np.isfinite(only['g_params'])) and np.any(only['g_params'] != 0)
+            if B == 200 and steps == 25 and (task, N) in PREMISE:          # the loop's own outputs reach what the kernel has to get right
+                hit, road = (ref['out5'][:, 3] > 0).any(0), (ref['out5'][:, 4] > 0).any(0)
+                assert hit.any() and (~hit).any() and road.any() and np.all(np.isfinite(ref['obs']))
+                moved = (ref['g_actions'] != 0).any((0, 2))
+                assert moved.mean() > 0.5 and np.any(ref['g_obs0'] != 0)
+                print('%s N=%d: %d rows collide, %d hit a wall, %d of %d rows with a non-zero g_actions' % (
+                    task, N, int(hit.sum()), int(road.sum()), int(moved.sum()), B))
+    if others:
+        sel = model(task, N, 'selecting')
+        m_plain = dev.make_mlp(*net)
+        assert supported(sel, m_plain)[0] == 1
+        big = scene(task, N, units, n_hidden, hact=hact, gain=40.0)[2]
+        m_big = dev.make_mlp(*big, scale)
+        for mm, ar in ((m, 0.5), (m_big, -1.0)):
+            ref = loop(dev, mm, obs0, 5, W5, ref_idx, ar=ar)
+            if ar < 0:
+                beyond = np.abs(ref['actions']) > 1.05
+                assert beyond.any() and (~beyond).any() and np.all(ref['g_actions'][beyond] == 0) and np.all(np.isfinite(ref['obs']))
+            assert_equal(entry(dev, mm, obs0, 5, W5, ref_idx, ar=ar), ref, '%s action_range %g' % (case, ar), PER_ROW)
+        ref = loop(dev, m_plain, obs0, 5, W5, ref_idx)
+        assert_equal(entry(dev, m_plain, obs0, 5, W5, ref_idx), ref, '%s no scale' % (case,), PER_ROW)
+        for path_id in (0, 2):
+            for mm in (m, m_plain):
+                ref = loop(sel, mm, obs0, 5, W5, None, path_id)
+                assert_equal(entry(sel, mm, obs0, 5, W5, None, path_id), ref, '%s selecting path %d' % (case, path_id), PER_ROW)
+        for mm in (m_plain, m_big):
+            dev.api.mlp_destroy(mm)
+    dev.api.mlp_destroy(m)

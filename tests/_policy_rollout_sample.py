@@ -8,7 +8,8 @@ import ctypes as C
 import numpy as np
 
 from env_build_amd import policy_rollout as PR, policy_sample as PS
-from tests import _policy
+from env_build_amd.policy_sample import policy_noise_reference
+from tests import _policy, _policy_rollout_grad as G
 from tests._policy import SENTINEL, assert_equal, param_count, same, scene, split_params  # noqa: F401  (its tests reach them through here)
 from tests._policy_rollout_grad import W5, model, rows_of as _rows_of  # noqa: F401
 from tests._tape import cost_in_the_headers_order
@@ -143,3 +144,92 @@ def rows_of(d, idx):
     """the per-row outputs of `d` for the envs idx"""
     pick = {'last': lambda v: v[idx], 'cost': lambda v: v[idx], 'g_obs0': lambda v: v[idx], 'out5': lambda v: v[:, :, idx]}
     return {k: pick.get(k, lambda v: v[:, idx])(v) for k, v in d.items() if k in PER_ROW}
+
+
+SEED = 0x5EED
+
+
+def given_noise(steps, B, seed=3):
+    return np.random.default_rng(seed).standard_normal((steps, B, 2)).astype(np.float32)
+
+
+def forward_equals_the_loop(case, sizes=(1, 63, 64, 65, 200), horizons=(1, 5), long=25, others=True):
+    """case = (task, N, units, hidden layers, hidden activation): every forward output of the entry equals the loop's bit for bit, noise
+    drawn and given (tests/test_gpu_policy_rollout_sample.py and the rows of tests/test_gpu_kernel_census.py call this one text); at 200
+    rows also `long` steps, with the loop's own premise; `others`: the other heads, no scale, selecting mode, a counter, row ids."""
+    task, N, units, n_hidden, hact = case
+    obs0, ref_idx, net, scale = scene(task, N, units, n_hidden, hact=hact)
+    dev = model(task, N)
+    m = dev.make_mlp(*net, scale)
+    assert supported(dev, m)[0] == 1
+    for B in sizes:
+        for steps in tuple(horizons) + ((long,) if B == 200 else ()):
+            for eps in (None, given_noise(steps, B)):
+                kw = dict(ref_idx=ref_idx[:B], eps=eps, seed=SEED)
+                ref = loop(dev, m, obs0[:B], steps, W5, grad=False, **kw)
+                what = '%s B=%d steps=%d noise %s' % (case, B, steps, 'drawn' if eps is None else 'given')
+                assert_equal(entry(dev, m, obs0[:B], steps, W5, want=FORWARD, **kw), ref, what, FORWARD)
+                if eps is None:
+                    for t in range(steps):
+                        assert same(ref['eps'][t], policy_noise_reference(np.arange(B), 2, SEED, t)), what
+                else:
+                    assert same(ref['eps'], eps)
+            if B == 200 and steps == long:         # the LOOP's own outputs (noise drawn) reach what the kernel has to get right
+                ref = loop(dev, m, obs0, steps, W5, ref_idx=ref_idx, seed=SEED, grad=False)
+                hit, road = (ref['out5'][:, 3] > 0).any(0), (ref['out5'][:, 4] > 0).any(0)
+                x = np.abs(ref['y'][:, :, :2].astype(np.float64) + np.exp(ref['y'][:, :, 2:].astype(np.float64)) * ref['eps'])
+                assert hit.any() and (~hit).any() and road.any() and (~road).any() and np.all(np.isfinite(ref['obs']))
+                assert (x < 0.6).any() and (x > 0.65).any()            # both branches of the deterministic tanh (0.625)
+                print('%s N=%d: %d rows collide, %d hit a wall, %.0f%% of |x| below 0.625' % (task, N, int(hit.sum()), int(road.sum()),
+                                                                                           100.0 * (x < 0.625).mean()))
+    if others:
+        B = 200
+        sel = model(task, N, 'selecting')
+        m_plain = dev.make_mlp(*net)
+        assert supported(sel, m_plain)[0] == 1
+        ids = np.random.default_rng(9).integers(0, 2 ** 32, B, dtype=np.uint64).astype(np.uint32)
+        for mm, mdl, kw in ((m, dev, dict(ref_idx=ref_idx, ar=0.5)), (m, dev, dict(ref_idx=ref_idx, ar=-1.0)),
+                            (m_plain, dev, dict(ref_idx=ref_idx)), (m, sel, dict(path_id=0)), (m_plain, sel, dict(path_id=2)),
+                            (m, dev, dict(ref_idx=ref_idx, counter=2 ** 40 + 7)), (m, dev, dict(ref_idx=ref_idx, row_ids=ids))):
+            ref = loop(mdl, mm, obs0, 5, W5, seed=SEED, grad=False, **kw)
+            assert np.all(np.isfinite(ref['obs']))
+            assert_equal(entry(mdl, mm, obs0, 5, W5, seed=SEED, want=FORWARD, **kw), ref, '%s %s' % (case, sorted(kw)), FORWARD)
+            if 'row_ids' in kw:
+                assert same(ref['eps'][3], policy_noise_reference(ids, 2, SEED, 3))
+            if 'counter' in kw:
+                assert same(ref['eps'][4], policy_noise_reference(np.arange(B), 2, SEED, 2 ** 40 + 11))
+        dev.api.mlp_destroy(m_plain)
+    dev.api.mlp_destroy(m)
+
+
+def reverse_equals_the_loop(case, sizes=(1, 65, 200), horizons=(1, 5)):
+    """every per-row output, gradients included, equals the loop's bit for bit over four (w_logp, action_range, noise) combinations;
+    w_logp = 0 and eps = 0 against eb_policy_rollout_grad"""
+    task, N, units, n_hidden, hact = case
+    obs0, ref_idx, net, scale = scene(task, N, units, n_hidden, hact=hact)
+    dev = model(task, N)
+    m = dev.make_mlp(*net, scale)
+    for B in sizes:
+        for steps in horizons:
+            w5 = tuple(v / (steps * B) for v in W5)
+            for w_logp, ar, eps in ((0.0, 1.0, None), (0.3, 1.0, None), (0.3, 0.5, given_noise(steps, B)), (0.3, -1.0, None)):
+                kw = dict(w_logp=w_logp, ref_idx=ref_idx[:B], ar=ar, eps=eps, seed=SEED, counter=5)
+                ref = loop(dev, m, obs0[:B], steps, w5, **kw)
+                got = entry(dev, m, obs0[:B], steps, w5, **kw)
+                assert_equal(got, ref, '%s B=%d steps=%d w_logp %g ar %g' % (case, B, steps, w_logp, ar), PER_ROW)
+                assert (B == 1 or np.any(ref['g_actions'] != 0)) and np.all(np.isfinite(ref['g_obs0']))   # (one row may sit beyond the clip)
+                only = entry(dev, m, obs0[:B], steps, w5, want=('g_obs0',), **kw)
+                assert sorted(only) == ['g_obs0'] and same(only['g_obs0'], ref['g_obs0'])
+            # w_logp = 0 and eps = 0 against eb_policy_rollout_grad.  With action_range = 1 the identity holds on EVERY column of
+            # g_actions and g_obs0, as numbers: the head's cotangent g * (1 * (1 - t^2)) + 0 * 2t is the parent's (g * 1) * (1 - t^2),
+            # and the log-std columns' s * (std * 0) - 0 are zeros, which add nothing to the products with W^T (a zero's sign may
+            # differ, hence == and not the bits).  With another action_range the two roundings of g * ar * (1 - t^2) differ, and only
+            # the LAST step's g_actions — the model step's reverse from lambda = 0, no policy in it — is asserted.
+            zero = np.zeros((steps, B, 2), np.float32)
+            for ar in (1.0, 0.5):
+                det = G.entry(dev, m, obs0[:B], steps, w5, ref_idx[:B], ar=ar, want=('g_actions', 'g_obs0'))
+                got = entry(dev, m, obs0[:B], steps, w5, w_logp=0.0, ref_idx=ref_idx[:B], ar=ar, eps=zero, want=('g_actions', 'g_obs0'))
+                assert np.array_equal(got['g_actions'][-1], det['g_actions'][-1])
+                if ar == 1.0:
+                    assert np.array_equal(got['g_actions'], det['g_actions']) and np.array_equal(got['g_obs0'], det['g_obs0'])
+    dev.api.mlp_destroy(m)

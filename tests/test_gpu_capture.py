@@ -12,7 +12,7 @@ import functools
 import numpy as np
 import pytest
 
-from tests._capture import CaptureError, capture, side_stream
+from tests._capture import CaptureError, capture, no_collection, side_stream
 from tests._capture_cases import CAPTURED, UNSPECIFIED, expected_kernels
 from tests._policy import SENTINEL, same
 
@@ -189,7 +189,7 @@ def test_facade_calls_read_the_current_stream_per_call():
             fill(name)
             want[name] = [t.clone() for t in work()]
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
+        with no_collection(), torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):     # (see _capture.no_collection)
             outs = work()
         try:
             for name in ('B', 'A', 'A'):

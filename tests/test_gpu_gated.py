@@ -9,29 +9,13 @@ import pytest
 
 from env_build_amd import _capi
 
-from env_build_amd.synthetic import assemble_obs, make_rollout_inputs
-from tests._helpers import DeviceModel, HostModel, oracle_lib
+from env_build_amd.synthetic import make_rollout_inputs
+from tests._helpers import DeviceModel, HostModel, check_out5_steps, initial_obs, oracle_lib, stepwise
 
 pytestmark = pytest.mark.gpu
 
 
-def _initial_obs(host, inp):
-    ego = inp['ego']
-    trk = host.tracking_error(ego[:, 3], ego[:, 4], ego[:, 5], ego[:, 0], host.n_future, ref_idx=inp['ref_idx'])
-    return assemble_obs(ego, trk, inp['veh'])
-
-
-def _stepwise(host, obs0, inp, H):
-    obs, o5s, states = obs0, [], []
-    for t in range(H):
-        obs, o5, _ = host.rollout_step(obs, inp['actions'][t], inp['ref_idx'])
-        o5s.append(o5); states.append(obs)
-    return obs, np.stack(o5s), np.stack(states)
-
-
-def _check(o5_d, o5_h):
-    assert np.array_equal(o5_d[:, 0], o5_h[:, 0]) and np.array_equal(o5_d[:, 4], o5_h[:, 4])
-    np.testing.assert_allclose(o5_d, o5_h, rtol=1e-6, atol=0)
+_initial_obs, _stepwise, _check = initial_obs, stepwise, check_out5_steps      # (tests/_helpers.py: the census rows are held to the same text)
 
 
 @pytest.mark.parametrize('task,N,B,tile,nf', [('left', 16, 4096, -1, 0), ('straight', 9, 777, 2, 2), ('right', 32, 1500, 1, 0),

@@ -20,11 +20,10 @@ import pytest
 
 from env_build_amd.synthetic import assemble_obs, make_rollout_inputs
 from env_build_amd.endtoend_env_utils import VEH_NUM
-from tests._helpers import GOLDEN, DeviceModel, HostModel, close, golden, oracle_lib
+from tests._helpers import GOLDEN, PEN_RTOL, DeviceModel, HostModel, check_out5, close, golden, initial_obs, oracle_lib
 
 pytestmark = pytest.mark.gpu
 TASKS = ('left', 'straight', 'right')
-PEN_RTOL = 1e-6
 FIX_ATOL = 5e-6    # next to rtol 1e-5 against reference-generated fixtures (tests/test_oracle_golden.py: ATOL)
 
 
@@ -32,17 +31,7 @@ def _pair(task, **kw):
     return HostModel(oracle_lib(), task, **kw), DeviceModel(task, **kw)
 
 
-def _initial_obs(host, inp):
-    ego = inp['ego']
-    trk = host.tracking_error(ego[:, 3], ego[:, 4], ego[:, 5], ego[:, 0], host.n_future, ref_idx=inp['ref_idx'])
-    return assemble_obs(ego, trk, inp['veh'])
-
-
-def _check_out5(o5_d, o5_h, where):
-    assert np.array_equal(o5_d[0], o5_h[0]), 'rewards differ %s' % where
-    assert np.array_equal(o5_d[4], o5_h[4]), 'veh2road4real differs %s' % where
-    for k in (1, 2, 3):
-        np.testing.assert_allclose(o5_d[k], o5_h[k], rtol=PEN_RTOL, atol=0, err_msg='out5[%d] %s' % (k, where))
+_initial_obs, _check_out5 = initial_obs, check_out5      # (tests/_helpers.py: the census rows are held to the same text)
 
 
 @pytest.mark.parametrize('task', TASKS)

@@ -4,7 +4,6 @@ eb_rollout_step through the same fp16 handle, and every comparison is bit for bi
 sizes, horizons, penalties, action ranges, modes and scale, (2) row independence and repeatability, (3) eb_shield_is_safe, (4) the
 reference's G14 flags, (5) eb_policy_rollout_supported and the refusals, (6) the façade and the example."""
 import ctypes as C
-import functools
 import os
 import sys
 
@@ -20,68 +19,21 @@ from tests._policy import F16, F32, assert_equal, f16_mlp, loop, loop_view, same
 from tests._policy_cases import G14, make_layers  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-EVERYTHING = ('out5', 'actions', 'obs', 'punish', 'safe')
-supported =functools.partial(_policy.supported, family='policy_rollout')
+supported = _policy.rollout_supported
+entry = _policy.rollout_entry
 
 
-def entry(dev, m, obs, steps, ref_idx=None, path_id=0, ar=1.0, penalty=0, want=EVERYTHING):
-    """eb_policy_rollout -> dict; an output that is not in `want` is passed as NULL"""
-    ob, ri = dev._in(obs), dev._in(ref_idx, np.int32)
-    n, D = ob.shape
-    bufs = {'last': dev._out((n, D)),
-            'out5': dev._out((steps, 5, n)) if 'out5' in want else None,
-            'actions': dev._out((steps, n, 2)) if 'actions' in want else None,
-            'obs': dev._out((steps, n, D)) if 'obs' in want else None,
-            'punish': dev._out((n,)) if 'punish' in want else None,
-            'safe': dev._out((n,), np.uint8) if 'safe' in want else None}
-    p = dev._ptr
-    dev.api.policy_rollout(dev.h, m, n, int(steps), p(ob), p(ri), int(path_id), C.c_float(ar), int(penalty), p(bufs['last']),
-                           p(bufs['out5']), p(bufs['actions']), p(bufs['obs']), p(bufs['punish']), p(bufs['safe']), dev.stream)
-    return {k: dev._ret(v) for k, v in bufs.items() if v is not None}
-
-
-# ---- 1: every output == the loop ----
+# ---- 1: every output == the loop (the body: tests/_policy.every_output_equals_the_loop) ----
 CASES = [('left', 8, 256, 2), ('right', 5, 64, 1), ('straight', 32, 256, 2), ('left', 32, 128, 3), ('left', 1, 100, 2)]
-PREMISE = {('left', 8), ('right', 5), ('straight', 32)}
+assert _policy.PREMISE == {('left', 8), ('right', 5), ('straight', 32)}
 
 
 @pytest.mark.parametrize('case', CASES, ids=lambda c: '%s_N%d_%dx%d' % (c[0], c[1], c[3], c[2]))
 def test_every_output_equals_the_loop(case):
-    task, N, units, n_hidden = case
-    obs0, ref_idx, net, scale = scene(*case)
-    dev = DeviceModel(task, n_veh=N)
-    sel = DeviceModel(task, n_veh=N, mode='selecting')
-    m, m_plain = f16_mlp(dev, *net, scale), f16_mlp(dev, *net)
-    assert supported(dev, m)[0] == 1 and supported(sel, m_plain)[0] == 1
-    # training mode, scale on: every batch size (one tile, a tile edge, a partial tile), every horizon, both penalties, with every
-    # optional output and with none
-    for B in (1, 63, 64, 65, 200):
-        ref = loop(dev, m, obs0[:B], 20, ref_idx[:B])
-        if B == 200 and (task, N) in PREMISE:       # the loop's own outputs reach what the kernel has to get right
-            v2v, road, real = ref['out5'][:, 3], ref['out5'][:, 4], ref['out5'][:, 2]
-            hit = (v2v > 0).any(0)
-            assert hit.any() and (~hit).any() and (road > 0).any() and np.all(np.isfinite(ref['obs']))
-            assert len(set(loop_view(ref, 20, 0)['safe'])) == 2 and (real > 0).any()
-            print('%s N=%d: %d rows collide, %d hit a wall' % (task, N, int(hit.sum()), int((road > 0).any(0).sum())))
-        for steps, penalty in ((20, 0), (5, 1), (1, 0)):
-            want = loop_view(ref, steps, penalty)
-            what = '%s B=%d steps=%d penalty=%d' % (case, B, steps, penalty)
-            assert_equal(entry(dev, m, obs0[:B], steps, ref_idx[:B], penalty=penalty), want, what)
-            assert_equal(entry(dev, m, obs0[:B], steps, ref_idx[:B], penalty=penalty, want=()), want, what + ' (optional outputs NULL)')
-        assert_equal(entry(dev, m, obs0[:B], 5, ref_idx[:B], penalty=0, want=('punish', 'safe')), loop_view(ref, 5, 0), 'punish / safe only')
-    # the other heads, no scale, selecting mode
-    B = 200
-    for ar in (0.5, -1.0):
-        ref = loop(dev, m, obs0, 5, ref_idx, ar=ar)
-        assert_equal(entry(dev, m, obs0, 5, ref_idx, ar=ar, penalty=1), loop_view(ref, 5, 1), '%s action_range %g' % (case, ar))
-    ref = loop(dev, m_plain, obs0, 5, ref_idx)
-    assert_equal(entry(dev, m_plain, obs0, 5, ref_idx), loop_view(ref, 5, 0), '%s no scale' % (case,))
-    for path_id in (0, 2):
-        for mm in (m, m_plain):
-            ref = loop(sel, mm, obs0, 5, None, path_id)
-            assert_equal(entry(sel, mm, obs0, 5, None, path_id, penalty=1), loop_view(ref, 5, 1), '%s selecting path %d' % (case, path_id))
-    dev.api.mlp_destroy(m)
-    dev.api.mlp_destroy(m_plain)
+    """training mode, scale on: every batch size (one tile, a tile edge, a partial tile), every horizon, both penalties, with every
+    optional output and with none; then the other heads, no scale, selecting mode"""
+    _policy.every_output_equals_the_loop(case, sizes=(1, 63, 64, 65, 200), loop_steps=20, horizons=((20, 0), (5, 1), (1, 0)), short=5,
+                                         others=True)
 
 
 # ---- 2: rows, launches ----

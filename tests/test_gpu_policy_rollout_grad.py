@@ -26,50 +26,13 @@ W5 = H.W5
 #        task, N, units, hidden layers, hidden activation
 CASES = [('left', 8, 256, 2, 'elu'), ('right', 5, 64, 1, 'relu'), ('straight', 32, 256, 2, 'tanh'), ('left', 32, 128, 3, 'relu'),
          ('left', 1, 100, 2, 'elu')]
-PREMISE = {('left', 8), ('right', 5), ('straight', 32)}
+assert H.PREMISE == {('left', 8), ('right', 5), ('straight', 32)}
 
 
 @pytest.mark.parametrize('case', CASES, ids=lambda c: '%s_N%d_%dx%d_%s' % (c[0], c[1], c[3], c[2], c[4]))
 def test_forward_and_reverse_equal_the_loop(case):
-    task, N, units, n_hidden, hact = case
-    obs0, ref_idx, net, scale = H.scene(task, N, units, n_hidden, hact=hact)
-    dev, sel = H.model(task, N), H.model(task, N, 'selecting')
-    m, m_plain = dev.make_mlp(*net, scale), dev.make_mlp(*net)
-    assert H.supported(dev, m)[0] == 1 and H.supported(sel, m_plain)[0] == 1
-    w5 = tuple(v / (25 * 200) for v in W5)
-    for B in (1, 63, 64, 65, 200):
-        for steps in (1, 5, 25):
-            ref = H.loop(dev, m, obs0[:B], steps, w5, ref_idx[:B])
-            what = '%s B=%d steps=%d' % (case, B, steps)
-            H.assert_equal(H.entry(dev, m, obs0[:B], steps, w5, ref_idx[:B]), ref, what, H.PER_ROW)
-            if steps == 5:
-                only = H.entry(dev, m, obs0[:B], steps, w5, ref_idx[:B], want=('g_params',))
-                assert sorted(only) == ['g_params'] and np.all(np.isfinite(only['g_params'])) and np.any(only['g_params'] != 0)
-            if B == 200 and steps == 25 and (task, N) in PREMISE:          # the loop's own outputs reach what the kernel has to get right
-                hit, road = (ref['out5'][:, 3] > 0).any(0), (ref['out5'][:, 4] > 0).any(0)
-                assert hit.any() and (~hit).any() and road.any() and np.all(np.isfinite(ref['obs']))
-                moved = (ref['g_actions'] != 0).any((0, 2))
-                assert moved.mean() > 0.5 and np.any(ref['g_obs0'] != 0)
-                print('%s N=%d: %d rows collide, %d hit a wall, %d of %d rows with a non-zero g_actions' % (
-                    task, N, int(hit.sum()), int(road.sum()), int(moved.sum()), B))
-    # the other heads (with the output weights scaled up: raw actions beyond the clip, a blocked cotangent), no scale, selecting mode
-    B = 200
-    big = H.scene(task, N, units, n_hidden, hact=hact, gain=40.0)[2]
-    m_big = dev.make_mlp(*big, scale)
-    for mm, ar in ((m, 0.5), (m_big, -1.0)):
-        ref = H.loop(dev, mm, obs0, 5, W5, ref_idx, ar=ar)
-        if ar < 0:
-            beyond = np.abs(ref['actions']) > 1.05
-            assert beyond.any() and (~beyond).any() and np.all(ref['g_actions'][beyond] == 0) and np.all(np.isfinite(ref['obs']))
-        H.assert_equal(H.entry(dev, mm, obs0, 5, W5, ref_idx, ar=ar), ref, '%s action_range %g' % (case, ar), H.PER_ROW)
-    ref = H.loop(dev, m_plain, obs0, 5, W5, ref_idx)
-    H.assert_equal(H.entry(dev, m_plain, obs0, 5, W5, ref_idx), ref, '%s no scale' % (case,), H.PER_ROW)
-    for path_id in (0, 2):
-        for mm in (m, m_plain):
-            ref = H.loop(sel, mm, obs0, 5, W5, None, path_id)
-            H.assert_equal(H.entry(sel, mm, obs0, 5, W5, None, path_id), ref, '%s selecting path %d' % (case, path_id), H.PER_ROW)
-    for mm in (m, m_plain, m_big):
-        dev.api.mlp_destroy(mm)
+    """the body: tests/_policy_rollout_grad.forward_and_reverse_equal_the_loop"""
+    H.forward_and_reverse_equal_the_loop(case, sizes=(1, 63, 64, 65, 200), horizons=(1, 5, 25), only_g_params_at=5, others=True)
 
 
 # ---- 2: g_params bit for bit at multiples of 64 ----

@@ -26,56 +26,13 @@ W5 = H.W5
 #        task, N, units, hidden layers, hidden activation: one per instantiation width and task
 CASES = [('left', 8, 256, 2, 'elu'), ('right', 5, 64, 1, 'relu'), ('straight', 32, 128, 3, 'tanh')]
 IDS = lambda c: '%s_N%d_%dx%d_%s' % (c[0], c[1], c[3], c[2], c[4])       # noqa: E731
-SEED = 0x5EED
+SEED, given_noise = H.SEED, H.given_noise
 
 
-def given_noise(steps, B, seed=3):
-    return np.random.default_rng(seed).standard_normal((steps, B, 2)).astype(np.float32)
-
-
-# ---- 1: forward == the loop ----
+# ---- 1: forward == the loop (the body: tests/_policy_rollout_sample.forward_equals_the_loop) ----
 @pytest.mark.parametrize('case', CASES, ids=IDS)
 def test_forward_equals_the_loop(case):
-    task, N, units, n_hidden, hact = case
-    obs0, ref_idx, net, scale = H.scene(task, N, units, n_hidden, hact=hact)
-    dev, sel = H.model(task, N), H.model(task, N, 'selecting')
-    m, m_plain = dev.make_mlp(*net, scale), dev.make_mlp(*net)
-    assert H.supported(dev, m)[0] == 1 and H.supported(sel, m_plain)[0] == 1
-    for B in (1, 63, 64, 65, 200):
-        for steps in (1, 5) + ((25,) if B == 200 else ()):
-            for eps in (None, given_noise(steps, B)):
-                kw = dict(ref_idx=ref_idx[:B], eps=eps, seed=SEED)
-                ref = H.loop(dev, m, obs0[:B], steps, W5, grad=False, **kw)
-                what = '%s B=%d steps=%d noise %s' % (case, B, steps, 'drawn' if eps is None else 'given')
-                H.assert_equal(H.entry(dev, m, obs0[:B], steps, W5, want=H.FORWARD, **kw), ref, what, H.FORWARD)
-                if eps is None:
-                    for t in range(steps):
-                        assert H.same(ref['eps'][t], policy_noise_reference(np.arange(B), 2, SEED, t)), what
-                else:
-                    assert H.same(ref['eps'], eps)
-            if B == 200 and steps == 25:           # the LOOP's own outputs (noise drawn) reach what the kernel has to get right
-                ref = H.loop(dev, m, obs0, steps, W5, ref_idx=ref_idx, seed=SEED, grad=False)
-                hit, road = (ref['out5'][:, 3] > 0).any(0), (ref['out5'][:, 4] > 0).any(0)
-                x = np.abs(ref['y'][:, :, :2].astype(np.float64) + np.exp(ref['y'][:, :, 2:].astype(np.float64)) * ref['eps'])
-                assert hit.any() and (~hit).any() and road.any() and (~road).any() and np.all(np.isfinite(ref['obs']))
-                assert (x < 0.6).any() and (x > 0.65).any()            # both branches of the deterministic tanh (0.625)
-                print('%s N=%d: %d rows collide, %d hit a wall, %.0f%% of |x| below 0.625' % (task, N, int(hit.sum()), int(road.sum()),
-                                                                                           100.0 * (x < 0.625).mean()))
-    # the other heads, no scale, selecting mode, a counter, row ids
-    B = 200
-    ids = np.random.default_rng(9).integers(0, 2 ** 32, B, dtype=np.uint64).astype(np.uint32)
-    for mm, model, kw in ((m, dev, dict(ref_idx=ref_idx, ar=0.5)), (m, dev, dict(ref_idx=ref_idx, ar=-1.0)),
-                          (m_plain, dev, dict(ref_idx=ref_idx)), (m, sel, dict(path_id=0)), (m_plain, sel, dict(path_id=2)),
-                          (m, dev, dict(ref_idx=ref_idx, counter=2 ** 40 + 7)), (m, dev, dict(ref_idx=ref_idx, row_ids=ids))):
-        ref = H.loop(model, mm, obs0, 5, W5, seed=SEED, grad=False, **kw)
-        assert np.all(np.isfinite(ref['obs']))
-        H.assert_equal(H.entry(model, mm, obs0, 5, W5, seed=SEED, want=H.FORWARD, **kw), ref, '%s %s' % (case, sorted(kw)), H.FORWARD)
-        if 'row_ids' in kw:
-            assert H.same(ref['eps'][3], policy_noise_reference(ids, 2, SEED, 3))
-        if 'counter' in kw:
-            assert H.same(ref['eps'][4], policy_noise_reference(np.arange(B), 2, SEED, 2 ** 40 + 11))
-    for mm in (m, m_plain):
-        dev.api.mlp_destroy(mm)
+    H.forward_equals_the_loop(case, sizes=(1, 63, 64, 65, 200), horizons=(1, 5), long=25, others=True)
 
 
 # ---- 2: eps = 0 is the deterministic rollout ----
@@ -95,37 +52,10 @@ def test_zero_noise_gives_the_deterministic_rollouts_forward(case):
     dev.api.mlp_destroy(m)
 
 
-# ---- 3: the reverse == the loop ----
+# ---- 3: the reverse == the loop (the body: tests/_policy_rollout_sample.reverse_equals_the_loop) ----
 @pytest.mark.parametrize('case', CASES, ids=IDS)
 def test_reverse_equals_the_loop(case):
-    task, N, units, n_hidden, hact = case
-    obs0, ref_idx, net, scale = H.scene(task, N, units, n_hidden, hact=hact)
-    dev = H.model(task, N)
-    m = dev.make_mlp(*net, scale)
-    for B in (1, 65, 200):
-        for steps in (1, 5):
-            w5 = tuple(v / (steps * B) for v in W5)
-            for w_logp, ar, eps in ((0.0, 1.0, None), (0.3, 1.0, None), (0.3, 0.5, given_noise(steps, B)), (0.3, -1.0, None)):
-                kw = dict(w_logp=w_logp, ref_idx=ref_idx[:B], ar=ar, eps=eps, seed=SEED, counter=5)
-                ref = H.loop(dev, m, obs0[:B], steps, w5, **kw)
-                got = H.entry(dev, m, obs0[:B], steps, w5, **kw)
-                H.assert_equal(got, ref, '%s B=%d steps=%d w_logp %g ar %g' % (case, B, steps, w_logp, ar), H.PER_ROW)
-                assert (B == 1 or np.any(ref['g_actions'] != 0)) and np.all(np.isfinite(ref['g_obs0']))   # (one row may sit beyond the clip)
-                only = H.entry(dev, m, obs0[:B], steps, w5, want=('g_obs0',), **kw)
-                assert sorted(only) == ['g_obs0'] and H.same(only['g_obs0'], ref['g_obs0'])
-            # w_logp = 0 and eps = 0 against eb_policy_rollout_grad.  With action_range = 1 the identity holds on EVERY column of
-            # g_actions and g_obs0, as numbers: the head's cotangent g * (1 * (1 - t^2)) + 0 * 2t is the parent's (g * 1) * (1 - t^2),
-            # and the log-std columns' s * (std * 0) - 0 are zeros, which add nothing to the products with W^T (a zero's sign may
-            # differ, hence == and not the bits).  With another action_range the two roundings of g * ar * (1 - t^2) differ, and only
-            # the LAST step's g_actions — the model step's reverse from lambda = 0, no policy in it — is asserted.
-            zero = np.zeros((steps, B, 2), np.float32)
-            for ar in (1.0, 0.5):
-                det = G.entry(dev, m, obs0[:B], steps, w5, ref_idx[:B], ar=ar, want=('g_actions', 'g_obs0'))
-                got = H.entry(dev, m, obs0[:B], steps, w5, w_logp=0.0, ref_idx=ref_idx[:B], ar=ar, eps=zero, want=('g_actions', 'g_obs0'))
-                assert np.array_equal(got['g_actions'][-1], det['g_actions'][-1])
-                if ar == 1.0:
-                    assert np.array_equal(got['g_actions'], det['g_actions']) and np.array_equal(got['g_obs0'], det['g_obs0'])
-    dev.api.mlp_destroy(m)
+    H.reverse_equals_the_loop(case, sizes=(1, 65, 200), horizons=(1, 5))
 
 
 # ---- 4: g_params ----

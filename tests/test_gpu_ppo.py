@@ -283,7 +283,7 @@ def gae_case(T):
     return rewards, values, v_last, live, nv, carry
 
 
-@pytest.mark.parametrize('T', [1, 2, 33])
+@pytest.mark.parametrize('T', [1, 2, 3, 4, 8, 33])      # window remainders 1, 2, 3 of GAE_WIN = 4, one and two exact windows, many
 def test_gae_is_the_restatement_and_the_examples_loop_bit_for_bit(T):
     import torch
     rewards, values, v_last, live, nv, carry = gae_case(T)

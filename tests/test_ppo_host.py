@@ -284,7 +284,7 @@ def gae_case(T, n=7, seed=0):
 
 
 @pytest.mark.parametrize('gamma, lam', [(0.99, 0.95), (0.9, 0.8), (1.0, 1.0), (0.997, 0.3)])
-@pytest.mark.parametrize('T', [1, 2, 33])
+@pytest.mark.parametrize('T', [1, 2, 3, 4, 8, 33])      # window remainders 1, 2, 3 of GAE_WIN = 4, one and two exact windows, many
 def test_gae_float32_restatement_is_the_examples_loop_bit_for_bit(T, gamma, lam):
     rewards, values, v_last, live = gae_case(T)
     want = example_loop(rewards, values, v_last, live, gamma, lam)
