@@ -7,7 +7,10 @@ Staleness is decided by CONTENT, not by mtime: the SHA-256 of every source, head
 written next to the library (libenvbuild_hip.so.srchash) when it is built, and `needs_build()` /
 `check_fresh()` compare it with the hash of the sources present.  A library that was copied somewhere
 together with different sources (e.g. a snapshot pushed to a GPU box) is therefore never silently reused:
-it is rebuilt when hipcc is there, and `_capi.hip_api()` refuses to load it otherwise."""
+it is rebuilt when hipcc is there, and `_capi.hip_api()` refuses to load it otherwise.
+
+`build_train()` does the same for env_build_amd/lib/libenvbuild_train.so, the training-only kernels (csrc/eb_train.hip): a library of its
+own with its own source list and hash, which `env_build_amd.train` loads on first use and nothing else does."""
 import hashlib
 import os
 import subprocess
@@ -105,13 +108,14 @@ def build(force=False, verbose=False):
         return _build_locked(verbose)
 
 
-def _build_locked(verbose):
+def _build_locked(verbose, lib=None, sources=None, digest=None):
     import shutil
     import tempfile
     from concurrent.futures import ThreadPoolExecutor
+    lib, sources = lib or LIB, sources or SOURCES
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    digest = source_hash()           # of what the compiler is about to read
-    objdir = tempfile.mkdtemp(prefix='eb_build_', dir=os.path.dirname(LIB))
+    digest = digest or source_hash()           # of what the compiler is about to read
+    objdir = tempfile.mkdtemp(prefix='eb_build_', dir=os.path.dirname(lib))
     try:
         def compile_one(f):
             obj = os.path.join(objdir, os.path.splitext(f)[0] + '.o')
@@ -120,20 +124,63 @@ def _build_locked(verbose):
                 print(' '.join(cmd))
             subprocess.check_call(cmd)
             return obj
-        with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1)) as pool:
-            objs = list(pool.map(compile_one, SOURCES))
-        tmp = LIB + '.tmp%d' % os.getpid()
+        with ThreadPoolExecutor(max_workers=min(len(sources), os.cpu_count() or 1)) as pool:
+            objs = list(pool.map(compile_one, sources))
+        tmp = lib + '.tmp%d' % os.getpid()
         cmd = [hipcc] + LINK_FLAGS + objs + ['-o', tmp]
         if verbose:
             print(' '.join(cmd))
         subprocess.check_call(cmd)
-        os.replace(tmp, LIB)
+        os.replace(tmp, lib)
     finally:
         shutil.rmtree(objdir, ignore_errors=True)
-    with open(HASH_FILE, 'w') as fh:
+    with open(lib + '.srchash', 'w') as fh:
         fh.write(digest + '\n')
-    return LIB
+    return lib
+
+
+# ---- libenvbuild_train.so: the training-only kernels (include/envbuild_train.h).  A library of its own — libenvbuild_hip.so, SOURCES,
+# HEADERS and source_hash() know nothing of it — built with the same flags, the same content-hash staleness rule, the same lock
+# discipline and the same atomic replace. ----
+TRAIN_LIB = os.path.join(HERE, 'lib', 'libenvbuild_train.so')
+TRAIN_SOURCES = ['eb_train.hip']
+TRAIN_HEADERS = ['eb_train.h', 'eb_train_device.h', os.path.join('..', '..', 'include', 'envbuild_train.h'),
+                 os.path.join('..', '..', 'include', 'envbuild.h')]
+
+
+def train_source_hash():
+    """source_hash() of the training library: the flags and the bytes of TRAIN_SOURCES and TRAIN_HEADERS"""
+    h = hashlib.sha256()
+    h.update('\0'.join(FLAGS + ['|'] + LINK_FLAGS).encode())
+    for f in TRAIN_SOURCES + TRAIN_HEADERS:
+        h.update(b'\0' + f.encode() + b'\0')
+        with open(os.path.join(CSRC, f), 'rb') as fh:
+            h.update(fh.read())
+    return h.hexdigest()
+
+
+def train_needs_build():
+    try:
+        with open(TRAIN_LIB + '.srchash') as fh:
+            built = fh.read().strip()
+    except OSError:
+        built = None
+    return not os.path.isfile(TRAIN_LIB) or built != train_source_hash()
+
+
+def build_train(force=False, verbose=False):
+    """build() for libenvbuild_train.so"""
+    if not force and not train_needs_build():
+        return TRAIN_LIB
+    import fcntl
+    os.makedirs(os.path.dirname(TRAIN_LIB), exist_ok=True)
+    with open(TRAIN_LIB + '.lock', 'w') as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        if not force and not train_needs_build():
+            return TRAIN_LIB
+        return _build_locked(verbose, TRAIN_LIB, TRAIN_SOURCES, train_source_hash())
 
 
 if __name__ == '__main__':
     print(build(force=True, verbose=True))
+    print(build_train(force=True, verbose=True))
