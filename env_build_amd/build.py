@@ -10,7 +10,8 @@ together with different sources (e.g. a snapshot pushed to a GPU box) is therefo
 it is rebuilt when hipcc is there, and `_capi.hip_api()` refuses to load it otherwise.
 
 `build_train()` does the same for env_build_amd/lib/libenvbuild_train.so, the training-only kernels (csrc/eb_train.hip): a library of its
-own with its own source list and hash, which `env_build_amd.train` loads on first use and nothing else does."""
+own with its own source list and hash, which `env_build_amd.train` loads on first use and nothing else does.
+`build_epoch()` likewise for env_build_amd/lib/libenvbuild_epoch.so (csrc/eb_epoch.hip), which `env_build_amd.epoch` loads."""
 import hashlib
 import os
 import subprocess
@@ -181,6 +182,49 @@ def build_train(force=False, verbose=False):
         return _build_locked(verbose, TRAIN_LIB, TRAIN_SOURCES, train_source_hash())
 
 
+# ---- libenvbuild_epoch.so: the kernels around the minibatch chain — keyed gather, advantage statistics, logging sums, the iteration
+# counter (include/envbuild_epoch.h).  A third library of its own, built the way the second one is.  eb_epoch_device.h takes splitmix64
+# from eb_env_device.h, so that header and what it includes are part of this library's hash too (and stay in HEADERS, unchanged). ----
+EPOCH_LIB = os.path.join(HERE, 'lib', 'libenvbuild_epoch.so')
+EPOCH_SOURCES = ['eb_epoch.hip']
+EPOCH_HEADERS = ['eb_epoch.h', 'eb_epoch_device.h', os.path.join('..', '..', 'include', 'envbuild_epoch.h'),
+                 'eb_env_device.h', 'eb_device.h', 'eb_kernels.h', os.path.join('..', '..', 'include', 'envbuild.h')]
+
+
+def epoch_source_hash():
+    """source_hash() of the epoch library: the flags and the bytes of EPOCH_SOURCES and EPOCH_HEADERS"""
+    h = hashlib.sha256()
+    h.update('\0'.join(FLAGS + ['|'] + LINK_FLAGS).encode())
+    for f in EPOCH_SOURCES + EPOCH_HEADERS:
+        h.update(b'\0' + f.encode() + b'\0')
+        with open(os.path.join(CSRC, f), 'rb') as fh:
+            h.update(fh.read())
+    return h.hexdigest()
+
+
+def epoch_needs_build():
+    try:
+        with open(EPOCH_LIB + '.srchash') as fh:
+            built = fh.read().strip()
+    except OSError:
+        built = None
+    return not os.path.isfile(EPOCH_LIB) or built != epoch_source_hash()
+
+
+def build_epoch(force=False, verbose=False):
+    """build() for libenvbuild_epoch.so"""
+    if not force and not epoch_needs_build():
+        return EPOCH_LIB
+    import fcntl
+    os.makedirs(os.path.dirname(EPOCH_LIB), exist_ok=True)
+    with open(EPOCH_LIB + '.lock', 'w') as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        if not force and not epoch_needs_build():
+            return EPOCH_LIB
+        return _build_locked(verbose, EPOCH_LIB, EPOCH_SOURCES, epoch_source_hash())
+
+
 if __name__ == '__main__':
     print(build(force=True, verbose=True))
     print(build_train(force=True, verbose=True))
+    print(build_epoch(force=True, verbose=True))
