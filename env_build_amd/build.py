@@ -11,7 +11,8 @@ it is rebuilt when hipcc is there, and `_capi.hip_api()` refuses to load it othe
 
 `build_train()` does the same for env_build_amd/lib/libenvbuild_train.so, the training-only kernels (csrc/eb_train.hip): a library of its
 own with its own source list and hash, which `env_build_amd.train` loads on first use and nothing else does.
-`build_epoch()` likewise for env_build_amd/lib/libenvbuild_epoch.so (csrc/eb_epoch.hip), which `env_build_amd.epoch` loads."""
+`build_epoch()` likewise for env_build_amd/lib/libenvbuild_epoch.so (csrc/eb_epoch.hip), which `env_build_amd.epoch` loads, and
+`build_collect()` for env_build_amd/lib/libenvbuild_collect.so (csrc/eb_collect.hip), which `env_build_amd.collect` loads."""
 import hashlib
 import os
 import subprocess
@@ -224,7 +225,49 @@ def build_epoch(force=False, verbose=False):
         return _build_locked(verbose, EPOCH_LIB, EPOCH_SOURCES, epoch_source_hash())
 
 
+# ---- libenvbuild_collect.so: the collection phase — the rollout buffer, truncation bootstraps, the episode log
+# (include/envbuild_collect.h).  A fourth library of its own, built the way the second and third are; it includes no header of theirs. ----
+COLLECT_LIB = os.path.join(HERE, 'lib', 'libenvbuild_collect.so')
+COLLECT_SOURCES = ['eb_collect.hip']
+COLLECT_HEADERS = ['eb_collect.h', 'eb_collect_device.h', os.path.join('..', '..', 'include', 'envbuild_collect.h'),
+                   os.path.join('..', '..', 'include', 'envbuild.h')]
+
+
+def collect_source_hash():
+    """source_hash() of the collection library: the flags and the bytes of COLLECT_SOURCES and COLLECT_HEADERS"""
+    h = hashlib.sha256()
+    h.update('\0'.join(FLAGS + ['|'] + LINK_FLAGS).encode())
+    for f in COLLECT_SOURCES + COLLECT_HEADERS:
+        h.update(b'\0' + f.encode() + b'\0')
+        with open(os.path.join(CSRC, f), 'rb') as fh:
+            h.update(fh.read())
+    return h.hexdigest()
+
+
+def collect_needs_build():
+    try:
+        with open(COLLECT_LIB + '.srchash') as fh:
+            built = fh.read().strip()
+    except OSError:
+        built = None
+    return not os.path.isfile(COLLECT_LIB) or built != collect_source_hash()
+
+
+def build_collect(force=False, verbose=False):
+    """build() for libenvbuild_collect.so"""
+    if not force and not collect_needs_build():
+        return COLLECT_LIB
+    import fcntl
+    os.makedirs(os.path.dirname(COLLECT_LIB), exist_ok=True)
+    with open(COLLECT_LIB + '.lock', 'w') as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        if not force and not collect_needs_build():
+            return COLLECT_LIB
+        return _build_locked(verbose, COLLECT_LIB, COLLECT_SOURCES, collect_source_hash())
+
+
 if __name__ == '__main__':
     print(build(force=True, verbose=True))
     print(build_train(force=True, verbose=True))
     print(build_epoch(force=True, verbose=True))
+    print(build_collect(force=True, verbose=True))
