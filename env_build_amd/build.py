@@ -12,7 +12,8 @@ it is rebuilt when hipcc is there, and `_capi.hip_api()` refuses to load it othe
 `build_train()` does the same for env_build_amd/lib/libenvbuild_train.so, the training-only kernels (csrc/eb_train.hip): a library of its
 own with its own source list and hash, which `env_build_amd.train` loads on first use and nothing else does.
 `build_epoch()` likewise for env_build_amd/lib/libenvbuild_epoch.so (csrc/eb_epoch.hip), which `env_build_amd.epoch` loads, and
-`build_collect()` for env_build_amd/lib/libenvbuild_collect.so (csrc/eb_collect.hip), which `env_build_amd.collect` loads."""
+`build_collect()` for env_build_amd/lib/libenvbuild_collect.so (csrc/eb_collect.hip), which `env_build_amd.collect` loads, and
+`build_ctl()` for env_build_amd/lib/libenvbuild_ctl.so (csrc/eb_ctl.hip), which `env_build_amd.ctl` loads."""
 import hashlib
 import os
 import subprocess
@@ -266,8 +267,52 @@ def build_collect(force=False, verbose=False):
         return _build_locked(verbose, COLLECT_LIB, COLLECT_SOURCES, collect_source_hash())
 
 
+# ---- libenvbuild_ctl.so: the controls of the update phase on the device — the iteration's learning-rate factor and the approximate-KL
+# stop (include/envbuild_ctl.h).  A fifth library of its own, built the way the other three small ones are.  Its unit takes the Adam
+# element, its uniforms and the block fold from eb_train_device.h and eb_adam_args from envbuild_train.h, so those two headers are part of
+# this library's hash too (and stay in TRAIN_HEADERS, unchanged). ----
+CTL_LIB = os.path.join(HERE, 'lib', 'libenvbuild_ctl.so')
+CTL_SOURCES = ['eb_ctl.hip']
+CTL_HEADERS = ['eb_ctl.h', 'eb_ctl_device.h', os.path.join('..', '..', 'include', 'envbuild_ctl.h'),
+               'eb_train_device.h', os.path.join('..', '..', 'include', 'envbuild_train.h'), os.path.join('..', '..', 'include', 'envbuild.h')]
+
+
+def ctl_source_hash():
+    """source_hash() of the control library: the flags and the bytes of CTL_SOURCES and CTL_HEADERS"""
+    h = hashlib.sha256()
+    h.update('\0'.join(FLAGS + ['|'] + LINK_FLAGS).encode())
+    for f in CTL_SOURCES + CTL_HEADERS:
+        h.update(b'\0' + f.encode() + b'\0')
+        with open(os.path.join(CSRC, f), 'rb') as fh:
+            h.update(fh.read())
+    return h.hexdigest()
+
+
+def ctl_needs_build():
+    try:
+        with open(CTL_LIB + '.srchash') as fh:
+            built = fh.read().strip()
+    except OSError:
+        built = None
+    return not os.path.isfile(CTL_LIB) or built != ctl_source_hash()
+
+
+def build_ctl(force=False, verbose=False):
+    """build() for libenvbuild_ctl.so"""
+    if not force and not ctl_needs_build():
+        return CTL_LIB
+    import fcntl
+    os.makedirs(os.path.dirname(CTL_LIB), exist_ok=True)
+    with open(CTL_LIB + '.lock', 'w') as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        if not force and not ctl_needs_build():
+            return CTL_LIB
+        return _build_locked(verbose, CTL_LIB, CTL_SOURCES, ctl_source_hash())
+
+
 if __name__ == '__main__':
     print(build(force=True, verbose=True))
     print(build_train(force=True, verbose=True))
     print(build_epoch(force=True, verbose=True))
     print(build_collect(force=True, verbose=True))
+    print(build_ctl(force=True, verbose=True))
