@@ -1,5 +1,5 @@
 """The table behind tests/test_stream_census.py and tests/test_gpu_capture.py: for every entry of include/*.h that takes a
-`void* stream`, either a row of CAPTURED — how to issue it on a stream of the caller's, and how many kernel nodes a capture of it must
+`void* stream` parameter, either a row of CAPTURED — how to issue it on a stream of the caller's, and how many kernel nodes a capture of it must
 hold — or a member of NOT_CAPTURED with the reason.  A helper module like _tape.py and _policy.py: pytest does not collect it, and
 importing it touches no device (rows allocate when their `make` is called).
 
@@ -48,13 +48,89 @@ def stream_entries(include_dir=None):
     return out
 
 
+def _stripped(path):
+    with open(path) as fh:
+        text = fh.read()
+    return re.sub(r'//[^\n]*', ' ', re.sub(r'/\*.*?\*/', ' ', text, flags=re.S))
+
+
+def struct_stream_entries(include_dir=None):
+    """every `int eb_*( ... const <struct>* ... );` of include/*.h whose argument struct carries a `void* stream` field, directly or in
+    a member struct (eb_adam_ctl_args holds an eb_adam_args), comments stripped -> {name: the struct's name}.  The entries
+    stream_entries() cannot see: the stream is no parameter of theirs."""
+    paths = sorted(glob.glob(os.path.join(include_dir or os.path.join(ROOT, 'include'), '*.h')))
+    texts = [_stripped(p) for p in paths]
+    fields = {}
+    for text in texts:
+        for m in re.finditer(r'\btypedef\s+struct\s+\w*\s*\{([^{}]*)\}\s*(\w+)\s*;', text):
+            assert m.group(2) not in fields, '%s defined twice' % m.group(2)
+            fields[m.group(2)] = [' '.join(f.split()) for f in m.group(1).split(';') if f.strip()]
+
+    def has_stream(name, seen=()):
+        for f in fields.get(name, ()):
+            if re.fullmatch(r'void\s*\*\s*stream', f):
+                return True
+            member = re.fullmatch(r'(?:struct\s+)?(\w+)\s+\w+(?:\s*\[[^\]]*\])?', f)       # a struct held by value
+            if member and member.group(1) in fields and member.group(1) not in seen and has_stream(member.group(1), seen + (name,)):
+                return True
+        return False
+    out = {}
+    for text in texts:
+        for m in re.finditer(r'\bint\s+(eb_\w+)\s*\(([^;{}()]*)\)\s*;', text):
+            for p in m.group(2).split(','):
+                a = re.fullmatch(r'(?:const\s+)?(?:struct\s+)?(\w+)\s*\*\s*\w+', ' '.join(p.split()))
+                if a and has_stream(a.group(1)):
+                    assert m.group(1) not in out, '%s declared twice' % m.group(1)
+                    out[m.group(1)] = a.group(1)
+    return out
+
+
+# entry -> (module of tests/, the test function that issues it on the null stream, on a side stream and under capture with replays).  An
+# entry that joins the ABI with its stream inside a struct fails tests/test_stream_census.py until it has such a test and a row here.
+STRUCT_STREAM_HELD = {
+    'eb_policy_rollout_sample': ('test_gpu_policy_rollout_sample', 'test_side_stream_and_capture'),
+    'eb_policy_logp': ('test_gpu_policy_logp', 'test_side_stream_capture_and_replay_for_the_three_entries'),
+    'eb_policy_logp_from_logits': ('test_gpu_policy_logp', 'test_side_stream_capture_and_replay_for_the_three_entries'),
+    'eb_policy_logp_vjp': ('test_gpu_policy_logp', 'test_side_stream_capture_and_replay_for_the_three_entries'),
+    'eb_ppo_surrogate': ('test_gpu_ppo', 'test_side_stream_capture_and_replay_for_the_three_entries'),
+    'eb_ppo_surrogate_from_logits': ('test_gpu_ppo', 'test_side_stream_capture_and_replay_for_the_three_entries'),
+    'eb_gae': ('test_gpu_ppo', 'test_side_stream_capture_and_replay_for_the_three_entries'),
+    'eb_value_loss': ('test_gpu_train', 'test_both_entries_on_a_side_stream_and_under_capture'),
+    'eb_adam_step': ('test_gpu_train', 'test_both_entries_on_a_side_stream_and_under_capture'),
+    'eb_minibatch_gather': ('test_gpu_epoch', 'test_every_entry_on_a_side_stream_and_under_capture'),
+    'eb_adv_stats': ('test_gpu_epoch', 'test_every_entry_on_a_side_stream_and_under_capture'),
+    'eb_ppo_log': ('test_gpu_epoch', 'test_every_entry_on_a_side_stream_and_under_capture'),
+    'eb_epoch_advance': ('test_gpu_epoch', 'test_every_entry_on_a_side_stream_and_under_capture'),
+    'eb_collect_begin': ('test_gpu_collect', 'test_every_entry_on_a_side_stream_and_under_capture'),
+    'eb_collect_record': ('test_gpu_collect', 'test_every_entry_on_a_side_stream_and_under_capture'),
+    'eb_collect_next_values': ('test_gpu_collect', 'test_every_entry_on_a_side_stream_and_under_capture'),
+    'eb_collect_episode_log': ('test_gpu_collect', 'test_every_entry_on_a_side_stream_and_under_capture'),
+    'eb_ctl_begin': ('test_gpu_ctl', 'test_every_entry_on_a_side_stream_and_under_capture'),
+    'eb_kl_stop': ('test_gpu_ctl', 'test_every_entry_on_a_side_stream_and_under_capture'),
+    'eb_adam_step_ctl': ('test_gpu_ctl', 'test_every_entry_on_a_side_stream_and_under_capture'),
+}
+
+
+def function_text(module, name):
+    """the source of tests/<module>.py's function `name` plus that of the module-level functions it calls by name (one level: the
+    capture tests of two modules keep their raw calls in a `capture_cases()` of their own); None when there is no such function"""
+    import ast
+    with open(os.path.join(ROOT, 'tests', module + '.py')) as fh:
+        src = fh.read()
+    defs = {n.name: n for n in ast.parse(src).body if isinstance(n, ast.FunctionDef)}
+    if name not in defs:
+        return None
+    called = {c.func.id for c in ast.walk(defs[name]) if isinstance(c, ast.Call) and isinstance(c.func, ast.Name)}
+    return '\n'.join(ast.get_source_segment(src, defs[n]) for n in [name] + sorted(called & (set(defs) - {name})))
+
+
 # ---- allocate | call ----
 class Call(object):
     """inputs / outputs: name -> device tensor (allocated once; overwrite in place); initial: the inputs' contents as made;
-    run(raw_stream): the C call(s), nothing else"""
+    run(raw_stream): the C call(s), nothing else; dev: the model whose helper was recorded"""
 
     def __init__(self):
-        self.inputs, self.outputs, self.initial, self.calls, self.keep = {}, {}, {}, [], []
+        self.inputs, self.outputs, self.initial, self.calls, self.keep, self.dev = {}, {}, {}, [], [], None
 
     def run(self, raw_stream):
         s = C.c_void_p(raw_stream)
@@ -69,6 +145,7 @@ def record(dev, body, only=None):
     call, api, token, cls = Call(), dev.api, C.c_void_p(0), type(dev)
     seen, by_pointer, in_struct = collections.OrderedDict(), {}, {}
     call.keep.append(dev)
+    call.dev = dev
 
     def pointer_fields(obj, prefix):
         for fname, ftype in obj._fields_:
@@ -177,15 +254,15 @@ def _policy_scene(size, which, f16=False):
     return m, mlp, net, _rows(obs0, size['n'], which), _rows(ref_idx, size['n'], which).astype(np.int32)
 
 
-def _env_scene(size, which, M=14):
+def _env_scene(size, which, M=14, task=TASK):
     from env_build_amd import _capi
     from env_build_amd.endtoend_env_utils import VEHICLE_MODE_LIST
     from tests._env_step_check import random_scene
     from tests._tape import TapeModel
     B, seed = size['n'], 44 + SEEDS[which]
-    native = VEHICLE_MODE_LIST[TASK]
+    native = VEHICLE_MODE_LIST[task]
     modes = [native[i % len(native)] for i in range(M)]
-    ego, cand, _, lw, light, _, ref = random_scene(TASK, B, M, seed)
+    ego, cand, _, lw, light, _, ref = random_scene(task, B, M, seed)
     cmode = np.tile(np.array([_capi.VMODE_ID[x] for x in modes], np.uint8), (B, 1))
     rng = np.random.default_rng(seed + 1)
     cmode[rng.random((B, M)) < 0.05] = _capi.VMODE_EMPTY
@@ -194,7 +271,7 @@ def _env_scene(size, which, M=14):
              v_light=rng.integers(0, 4, B).astype(np.uint8), params=rng.normal(size=(B, 4)).astype(np.float32))
     s['entry'] = np.stack([rng.uniform(-60, 60, M), rng.uniform(-60, 60, M), rng.choice([0., 90., 180., -90.], M),
                            rng.choice([-1., 0., 1.], M), rng.choice([-1., 0., 1.], M)], 1).astype(np.float32)
-    s['m'], s['tr'] = TapeModel(TASK, mode='training'), TapeModel(TASK, n_veh=M, modes=modes)
+    s['m'], s['tr'] = TapeModel(task, mode='training'), TapeModel(task, n_veh=M, modes=modes)
     s['obs0'] = s['m'].get_obs(ego, cand, cmode, light, ref_idx=ref)
     return s
 
@@ -241,20 +318,28 @@ def _small(method, args):
     return make
 
 
-def _get_obs(size, which):
-    s = _env_scene(size, which)
+def _get_obs(size, which, task=TASK):
+    s = _env_scene(size, which, task=task)
     return record(s['m'], lambda d: d.get_obs(s['ego'], s['cand'], s['cmode'], s['v_light'], ref_idx=s['ref'], virtual=s['virtual']))
 
 
-def _env_step(size, which):
-    s = _env_scene(size, which)
+def _env_step(size, which, task=TASK, auto_reset=False, time_limit=False):
+    """auto_reset: with the pool's reset of the envs the step finishes (eb_auto_reset); time_limit: with eb_time_limit"""
+    s = _env_scene(size, which, task=task)
+    kw = {}
+    if auto_reset:
+        from env_build_amd.endtoend import _lane_entry
+        entry = np.array([list(_lane_entry(x)[:3]) + list(_lane_entry(x)[3]) for x in s['modes']], np.float32)
+        kw['auto_reset'] = dict(seed=99, counter=5, training=1, pool=dict(entry=entry, span=60.0, v_max=8.0, seed=4242, counter=17, edge_span=5.0))
+    if time_limit:
+        kw['time_limit'] = (np.random.default_rng(SEEDS[which]).integers(0, 205, size['n']).astype(np.int32), 200)
     c = record(s['m'], lambda d: d.env_step(s['tr'], s['obs0'], s['raw'], s['ego'], s['cand'], s['cmode'], ref_idx=s['ref'], cand_lw=s['lw'],
-                                            v_light=s['v_light'], virtual=s['virtual']))
+                                            v_light=s['v_light'], virtual=s['virtual'], **kw))
     c.keep.append(s['tr'])
     return c
 
 
-def _flow_scene(size, which, K=2):
+def _flow_scene(size, which, K=2, task=TASK):
     """the scene of _env_step_check.flow_auto_reset_case: the flow source with a sixth of the egos off the road, so that a step
     finishes envs"""
     from env_build_amd import _capi
@@ -269,10 +354,10 @@ def _flow_scene(size, which, K=2):
     clen = np.array([VTYPES[FLOWS[x][1]][0] for x in slot_modes], np.float32)
     lw = np.tile(np.array([[VTYPES[FLOWS[x][1]][0], VTYPES[FLOWS[x][1]][1]] for x in slot_modes], np.float32), (B, 1, 1))
     rng = np.random.default_rng(seed)
-    inp = make_rollout_inputs(TASK, B, 8, 1, seed=seed)
+    inp = make_rollout_inputs(task, B, 8, 1, seed=seed)
     ego, ref = inp['ego'].copy(), inp['ref_idx'].copy()
     ego[::6, 3] += rng.uniform(7, 12, len(ego[::6])) * rng.choice([-1, 1], len(ego[::6]))
-    m, tr = TapeModel(TASK, mode='training'), TapeModel(TASK, n_veh=M, modes=slot_modes)
+    m, tr = TapeModel(task, mode='training'), TapeModel(task, n_veh=M, modes=slot_modes)
     active = (rng.random((B, M)) < 0.4).astype(np.uint8)
     along = rng.uniform(0, 95, (B, M)).astype(np.float32)
     cand = np.stack([lane[None, :, 0] + along * lane[None, :, 3], lane[None, :, 1] + along * lane[None, :, 4],
@@ -289,9 +374,12 @@ def _flow_scene(size, which, K=2):
                           counter=1))
 
 
-def _env_step_auto_reset_flow(size, which):
-    s = _flow_scene(size, which)
+def _env_step_auto_reset_flow(size, which, task=TASK, auto_reset=True):
+    """auto_reset False: the step with the flow rule alone"""
+    s = _flow_scene(size, which, task=task)
     reset = dict(seed=777, counter=1, training=1, flow=dict(cand_len=s['clen'], phase0=s['phase0'], random_phase=0, seed=4242, counter=1))
+    if not auto_reset:
+        reset = None
     c = record(s['m'], lambda d: d.env_step(s['tr'], s['obs'], s['raw'], s['ego'], s['cand'], s['mode'], ref_idx=s['ref'], cand_lw=s['lw'],
                                             v_light=s['light'], virtual=s['virtual'], flow=s['flow'], auto_reset=reset))
     c.keep.append(s['tr'])
@@ -324,13 +412,13 @@ def _env(method, args, handle='m'):
     return make
 
 
-def _env_reset_pool(size, which):
+def _env_reset_pool(size, which, task=TASK, M=12):
     from env_build_amd.endtoend import _lane_entry
-    s = _env_scene(size, which, M=12)
+    s = _env_scene(size, which, M=M, task=task)
     entry = np.array([list(_lane_entry(x)[:3]) + list(_lane_entry(x)[3]) for x in s['modes']], np.float32)
     rng = np.random.default_rng(21 + SEEDS[which])
     mask = (rng.random(size['n']) < 0.3).astype(np.uint8)
-    obs = rng.normal(size=(size['n'], D)).astype(np.float32)
+    obs = rng.normal(size=(size['n'], s['m'].D)).astype(np.float32)
     pool = dict(entry=entry, span=60.0, v_max=8.0, seed=4242, counter=17, edge_span=5.0)
     c = record(s['m'], lambda d: d.env_reset_pool(s['tr'], 99, 5, 1, s['ego'], s['params'], s['ref'], s['virtual'], s['v_light'], s['cand'],
                                                   s['cmode'], obs, pool, mask=mask))

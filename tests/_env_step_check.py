@@ -30,7 +30,7 @@ def random_scene(task, B, M, seed):
     return ego, cand, cmode, lw, light, act, inp['ref_idx']
 
 
-def composite_case(make, task, B, M, NV, nf, tile=None):
+def composite_case(make, task, B, M, NV, nf, tile=None, waves=None):
     """make(task, **kw) -> a HostModel / DeviceModel; -> the composite's eight outputs (for cross-library comparison)"""
     native = VEHICLE_MODE_LIST[task]
     modes = [native[i % len(native)] for i in range(M)]
@@ -60,6 +60,8 @@ def composite_case(make, task, B, M, NV, nf, tile=None):
     m, tr = make(task, **kw), make(task, n_veh=M, modes=modes)
     if tile is not None:
         m.set_tile(tile)          # the one-launch step: 0 / 1 / 2 = 64- / 32- / 16-env tiles (eb_debug_set_tile)
+    if waves is not None:
+        m.set_env_waves(waves)    # 4 / 8 waves per block of the one-launch kernels (eb_debug_set_env_waves)
     obs0 = m.get_obs(ego, cand, cmode, light, ref_idx=ref)
     # the six calls
     act = m.action_transform(raw)
@@ -205,7 +207,7 @@ def g20_parked_flow_case(make, task, tile=None, widened=False):
     return trace
 
 
-def auto_reset_case(make, task, B, M, NV=None, nf=0, tile=None, close_p=0.02, seed=5, v_light_none=False, strict=True, scene=None):
+def auto_reset_case(make, task, B, M, NV=None, nf=0, tile=None, close_p=0.02, seed=5, v_light_none=False, strict=True, scene=None, waves=None):
     """eb_env_step(auto_reset) == eb_env_step, then the terminal rows -> final_obs, then eb_env_reset_pool(mask = done != 0) in place —
     every output and every piece of state, bit for bit; done_code keeps the step's codes.
     scene: dict(ego, cand, cmode, virtual, v_light, ref) of B envs and M candidates in place of the drawn one (g20_parked_scene)."""
@@ -238,6 +240,8 @@ def auto_reset_case(make, task, B, M, NV=None, nf=0, tile=None, close_p=0.02, se
     m, tr = make(task, **kw), make(task, n_veh=M, modes=modes)
     if tile is not None:
         m.set_tile(tile)
+    if waves is not None:
+        m.set_env_waves(waves)    # 4 / 8 waves per block of the one-launch kernels (eb_debug_set_env_waves)
     obs0 = m.get_obs(ego, cand, cmode, v_light, ref_idx=ref, virtual=virtual)
     # the two calls
     sc, o5, d16, ego1, par1, cand1, obs1, done1 = m.env_step(tr, obs0, raw, ego, cand, cmode, ref_idx=ref, v_light=v_light, virtual=virtual,
@@ -294,7 +298,8 @@ def auto_reset_bad_args_case(make, task='left', B=40, M=8):
                    auto_reset=dict(seed=1, counter=1, training=1, pool=pool))
 
 
-def flow_rule_case(make, task, B=300, K=5, steps=40, tile=None, light_cycle=1, seed=3, strict=True, hostile=False, scene=None, NV=None):
+def flow_rule_case(make, task, B=300, K=5, steps=40, tile=None, light_cycle=1, seed=3, strict=True, hostile=False, scene=None, NV=None,
+                   waves=None):
     """eb_env_step(flow) == eb_env_step, then eb_traffic_flow_step on what it left — every output and every piece of the flow
     source's state, bit for bit, over a closed loop that starts from an empty junction (emissions, exits, accelerations, the
     light programme all occur on the way); -> the trace of the fused path (for cross-library comparison).
@@ -313,6 +318,8 @@ def flow_rule_case(make, task, B=300, K=5, steps=40, tile=None, light_cycle=1, s
     m, tr = make(task, mode='training', **({} if NV is None else dict(n_veh=NV))), make(task, n_veh=M, modes=slot_modes)
     if tile is not None:
         m.set_tile(tile)
+    if waves is not None:
+        m.set_env_waves(waves)    # 4 / 8 waves per block of the one-launch kernels (eb_debug_set_env_waves)
     # a junction in mid-traffic: some slots occupied along their lanes (a few of them far out and heading away: they leave)
     active = (rng.random((B, M)) < 0.4).astype(np.uint8)
     along = rng.uniform(0, 95, (B, M)).astype(np.float32)
@@ -438,7 +445,7 @@ def respawn_conflict_case(make, B=300, M=16, seed=4):
     return safe
 
 
-def reset_pool_case(make, task, B=260, M=12, seed=21, tile=None, NV=None):
+def reset_pool_case(make, task, B=260, M=12, seed=21, tile=None, NV=None, waves=None):
     """eb_env_reset_pool == eb_env_reset, eb_traffic_respawn(forced, clear of the ego), v_light clear, eb_get_obs(row mask, OLD
     flags), flag swap — for the masked envs only; the other envs' rows are untouched."""
     from env_build_amd.endtoend import _lane_entry
@@ -457,6 +464,8 @@ def reset_pool_case(make, task, B=260, M=12, seed=21, tile=None, NV=None):
     tr = make(task, n_veh=M, modes=modes)
     if tile is not None:
         m.set_tile(tile)          # the one-launch reset: 0 / 1 / 2 = 64- / 32- / 16-env tiles (eb_debug_set_tile)
+    if waves is not None:
+        m.set_env_waves(waves)    # 4 / 8 waves per block of the one-launch kernels (eb_debug_set_env_waves)
     pool = dict(entry=entry, span=60.0, v_max=8.0, seed=4242, counter=17, edge_span=5.0)
     outs = []
     for mask in (rng.random(B) < 0.3, None):
@@ -503,7 +512,7 @@ def wrap_guard_case(m):
     return out
 
 
-def time_limit_case(make, task, B, M, tile=None, max_steps=200, seed=8):
+def time_limit_case(make, task, B, M, tile=None, max_steps=200, seed=8, waves=None):
     """ABI 5, eb_time_limit — gym's TimeLimit around the registered env (README.md:55-59): the step counts rise by one; an env no
     reference predicate has finished takes EB_DONE_TIME_LIMIT when its count reaches the limit; a finished env's count restarts;
     nothing else about the step changes.  With auto_reset the truncated envs are reset like the others; the resets clear the
@@ -523,6 +532,8 @@ def time_limit_case(make, task, B, M, tile=None, max_steps=200, seed=8):
     m, tr = make(task, mode='training'), make(task, n_veh=M, modes=modes)
     if tile is not None:
         m.set_tile(tile)
+    if waves is not None:
+        m.set_env_waves(waves)    # 4 / 8 waves per block of the one-launch kernels (eb_debug_set_env_waves)
     obs0 = m.get_obs(ego, cand, cmode, light, ref_idx=ref)
     plain = m.env_step(tr, obs0, raw, ego, cand, cmode, ref_idx=ref, v_light=light, virtual=virtual)
     got = m.env_step(tr, obs0, raw, ego, cand, cmode, ref_idx=ref, v_light=light, virtual=virtual, time_limit=(steps, max_steps))
@@ -580,7 +591,7 @@ def parked_ego_case(make, task='left', B=3, max_steps=200):
     return codes
 
 
-def flow_auto_reset_case(make, task, B=260, K=5, steps=12, tile=None, seed=13, strict=True):
+def flow_auto_reset_case(make, task, B=260, K=5, steps=12, tile=None, seed=13, strict=True, waves=None):
     """ABI 5 — eb_env_step(flow + auto_reset): the step over the flow source that also resets the envs it finished == eb_env_step(flow),
     then the terminal rows -> final_obs, eb_env_reset(mask), eb_traffic_flow_reset(mask, new ego), eb_get_obs(row_mask, OLD flags, the
     light the reset set), flag swap — every output and every piece of state, bit for bit, over a closed loop in which egos do finish;
@@ -600,6 +611,8 @@ def flow_auto_reset_case(make, task, B=260, K=5, steps=12, tile=None, seed=13, s
     m, tr = make(task, mode='training'), make(task, n_veh=M, modes=slot_modes)
     if tile is not None:
         m.set_tile(tile)
+    if waves is not None:
+        m.set_env_waves(waves)    # 4 / 8 waves per block of the one-launch kernels (eb_debug_set_env_waves)
     active = (rng.random((B, M)) < 0.4).astype(np.uint8)
     along = rng.uniform(0, 95, (B, M)).astype(np.float32)
     cand = np.stack([lane[None, :, 0] + along * lane[None, :, 3], lane[None, :, 1] + along * lane[None, :, 4],

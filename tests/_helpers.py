@@ -540,6 +540,10 @@ class DeviceModel(HostModel):
         """Force the rollout kernel's tile shape (eb_debug_set_tile; -1 = pick by batch size)."""
         self.api.debug_set_tile(self.h, int(variant))
 
+    def set_env_waves(self, waves):
+        """Force the waves per block of the one-launch env kernels (eb_debug_set_env_waves; 4 / 8, 0 = by grid size)."""
+        self.api.debug_set_env_waves(self.h, int(waves))
+
     def rollout_plan(self, n_env):
         """eb_debug_rollout_plan -> (tile shape 0 / 1 / 2, workgroups, rolling loads, priority by progress) for a batch of n_env"""
         out = (C.c_int32 * 4)()

@@ -11,8 +11,15 @@ tests/test_gpu_kernel_census.py — or `Unreachable(reason)`; `Faulted(reason)` 
 cause is not found (no launch is made for it; none today).  `COUNTED` maps every other family to its instantiation count.  A new kernel or
 instantiation anywhere in the library fails tests/test_kernel_census.py until someone extends HELD or updates COUNTED.
 
-Widening HELD to env_step_kernel (45 instantiations) and to the <RT, CT> policy kernels (mlp_f16_kernel, policy_sample_kernel,
-policy_logp_kernel, ppo_surrogate_kernel, mlp_bwd_data_kernel) is a later pull request: today they are counted, not held.
+`ENV_HELD` does the same for the one-launch env kernels of csrc/eb_env_step_body.h: env_step_kernel<TASK, ET, OBS, AUTO, NW> (45) and
+env_reset_pool_kernel<TASK, ET, NW> (15) — 3 tasks x 5 shapes (64-env tiles with four waves, 32- and 16-env tiles with four and eight)
+x 4 kinds (step, step + auto reset, observation, masked reset), 60 rows, every one a Case, launched with the tile AND the waves per block
+forced and held against the oracle by tests/test_gpu_env_census.py.  The four-wave kernels of the small tiles run in production only
+above 3 * n_cu blocks; no test of the suite is that large on the small tiles, so before these rows nothing launched those 24 kernels.
+`ENV_FEATURES` adds the rows that reach code only some calls switch on: the flow rule (on 16-env tiles x four waves: FUSED_FLOW), the
+flow rule with auto reset (there: DRAW_LATE), and the episode step limit (its wave depends on NW).  `claimed_env_kernel(case)` restates
+launch_env_step's rule.  The <RT, CT> policy kernels (mlp_f16_kernel, policy_sample_kernel, policy_logp_kernel, ppo_surrogate_kernel,
+mlp_bwd_data_kernel) stay counted: their own modules run one width per instantiation.
 
 The witness — which kernels a call enqueues — is read from the hipGraph a stream capture of the call produces (tests/_capture.py):
 hipGraphKernelNodeGetParams gives each kernel node's host-side handle, `handle_names` maps the handles of the library's kernels (dynamic
@@ -31,6 +38,8 @@ TAPE = ('rollout_tape_4x8', 'rollout_tape_4x4', 'rollout_tape_1x4')
 GATED = ('rollout_gated_4x8', 'rollout_gated_4x4', 'rollout_gated_1x4')
 POLICY = ('policy_rollout_kernel', 'policy_rollout_grad_kernel', 'policy_rollout_sample_kernel')
 HELD_FAMILIES = FUSED + TAPE + GATED + POLICY
+ENV_FAMILIES = ('env_step_kernel', 'env_reset_pool_kernel')
+ALL_HELD_FAMILIES = HELD_FAMILIES + ENV_FAMILIES
 RECORD_WAVES = (4, 4, 1)                                    # rw of tile shape 0 / 1 / 2 (4x8, 4x4, 1x4)
 TILE_RECORDS = (4 * 64 * 8, 4 * 64 * 4, 1 * 64 * 4)         # fused_tile_records
 WIDTH_OF = {(1, 1): 64, (2, 1): 128, (2, 2): 256}           # the closed-loop kernels' <RT, CT> per (padded) hidden-layer width
@@ -38,7 +47,8 @@ POLICY_ENTRY = {'policy_rollout_kernel': 'policy_rollout', 'policy_rollout_grad_
                 'policy_rollout_sample_kernel': 'policy_rollout_sample'}
 
 Kernel = collections.namedtuple('Kernel', 'family args symbol')     # args: tuple of int / bool / 'f32' / 'f16', None when not parsed
-Case = collections.namedtuple('Case', 'entry task n_veh tile rolling storage mode units')
+# (waves, auto_reset: the env rows' — eb_debug_set_env_waves 4 / 8, or 0 = by grid size; eb_env_step with / without eb_auto_reset)
+Case = collections.namedtuple('Case', 'entry task n_veh tile rolling storage mode units waves auto_reset', defaults=(None, None))
 Unreachable = collections.namedtuple('Unreachable', 'reason')
 Faulted = collections.namedtuple('Faulted', 'reason')
 
@@ -188,8 +198,7 @@ HELD = _held()
 
 COUNTED = {
     'acc_fold_kernel': 1, 'action_transform_kernel': 1, 'copy_rows_masked_kernel': 1, 'ego_dynamics_kernel': 1, 'ego_predict_kernel': 1,
-    'env_ego_step_kernel': 1, 'env_pre_kernel': 3, 'env_reset_kernel': 1, 'env_reset_pool_kernel': 15, 'env_step_kernel': 45,
-    'exit_frame_kernel': 1, 'f_xu_kernel': 1, 'flag_swap_kernel': 1, 'gae_kernel': 1, 'gate_feed_kernel': 1, 'get_obs_exit_kernel': 3,
+    'env_ego_step_kernel': 1, 'env_pre_kernel': 3, 'env_reset_kernel': 1, 'exit_frame_kernel': 1, 'f_xu_kernel': 1, 'flag_swap_kernel': 1, 'gae_kernel': 1, 'gate_feed_kernel': 1, 'get_obs_exit_kernel': 3,
     'get_obs_kernel': 6, 'judge_done_kernel': 1, 'mlp_bwd_data_kernel': 3, 'mlp_f16_kernel': 4, 'mlp_kernel': 4, 'mlp_pack_kernel': 1,
     'mlp_wgrad_kernel': 1, 'mlp_wgrad_reduce_kernel': 1, 'path_points_kernel': 1, 'phi_diff_kernel': 1, 'policy_logp_kernel': 4,
     'policy_logp_logits_kernel': 1, 'policy_logp_vjp_kernel': 1, 'policy_sample_kernel': 4, 'policy_sample_logits_kernel': 1,
@@ -201,14 +210,95 @@ COUNTED = {
 }
 
 
+# ---- the one-launch env kernels (csrc/eb_env_step.hip: launch_env_step; csrc/eb_env_step_body.h: launch_env_step_task) ----
+ENV_SHAPES = ((64, 4), (32, 4), (32, 8), (16, 4), (16, 8))  # (ET, NW): eight waves per block exist for the 16- and 32-env tiles only
+ENV_KINDS = ('step', 'auto', 'obs', 'reset')                # eb_env_step, eb_env_step + eb_auto_reset, eb_get_obs, eb_env_reset_pool
+ENV_ENTRY = {'step': 'env_step', 'auto': 'env_step', 'obs': 'get_obs', 'reset': 'env_reset_pool'}
+TILE_OF_ET = {64: 0, 32: 1, 16: 2}                          # eb_debug_set_tile on the env-side kernels
+ENV_CAND = 14                                               # candidates per env of the pool rows (the flow rows: 12 K = 24)
+FLOW_K = 2
+
+
+def env_kind(case):
+    return {'get_obs': 'obs', 'env_reset_pool': 'reset'}.get(case.entry) or ('auto' if case.auto_reset else 'step')
+
+
+def env_key(kind, t, et, nw):
+    if kind == 'reset':
+        return ('env_reset_pool_kernel', t, et, nw)
+    return ('env_step_kernel', t, et, kind == 'obs', kind == 'auto', nw)
+
+
+def claimed_env_kernel(case, n_env=None, n_cu=None):
+    """the key of the kernel an env Case says it launches: the kind from the entry and its arguments, ET from the forced tile, NW from
+    the forced waves (eight exist below 64-env tiles only) or — waves 0 — from the grid: eight while n_blocks <= 3 * n_cu.  (A forced
+    tile that does not fit the LDS falls back to 16-env tiles; the rows are shaped to fit and the GPU witness is the judge.)"""
+    assert case.entry in ENV_ENTRY.values() and case.tile in (0, 1, 2) and case.waves in (0, 4, 8)
+    et = {v: k for k, v in TILE_OF_ET.items()}[case.tile]
+    if case.waves:
+        eight = case.waves == 8
+    else:
+        eight = (n_env + et - 1) // et <= 3 * n_cu
+    return env_key(env_kind(case), TASKS.index(case.task), et, 8 if eight and et <= 32 else 4)
+
+
+def env_batch_of(case):
+    """two full tiles plus three envs"""
+    return 2 * {v: k for k, v in TILE_OF_ET.items()}[case.tile] + 3
+
+
+def _env_held():
+    rows = collections.OrderedDict()
+    for kind in ENV_KINDS:
+        for t, task in enumerate(TASKS):
+            for et, nw in ENV_SHAPES:
+                rows[env_key(kind, t, et, nw)] = Case(ENV_ENTRY[kind], task, NATIVE[task], TILE_OF_ET[et], None, 'f32', 'training', None,
+                                                      nw, kind == 'auto')
+    return rows
+
+
+ENV_HELD = _env_held()
+# the 24 kernels no test launched before these rows: the small tiles with four waves per block
+ENV_NEW = [key for key in ENV_HELD if key[-1] == 4 and key[2] in (16, 32)]
+# feature rows: (feature, key of the kernel the row runs on) — the flow rule on the 15 plain-step kernels, the flow rule with auto reset
+# and the episode step limit on the 15 auto-reset kernels
+ENV_FEATURES = ([('flow', k) for k in ENV_HELD if k[0] == 'env_step_kernel' and not k[3] and not k[4]] +
+                [('flow_auto', k) for k in ENV_HELD if k[0] == 'env_step_kernel' and k[4]] +
+                [('time_limit', k) for k in ENV_HELD if k[0] == 'env_step_kernel' and k[4]])
+# what each row's scene is drawn with, per batch size (2 ET + 3) where it has to differ: seeds, close_p, steps and K are chosen so that the
+# ORACLE meets the conditions of tests/test_env_census_scenes.py (a flow row emits and lets exit, an auto-reset row finishes envs in
+# its first tile and outside it, a masked reset masks an env of the ragged tail) — conditions on the inputs, decided on the CPU
+ENV_PARAMS = {                                              # None: every (task, B) of the kind; (task, B): that scene's own
+    'step': {},
+    'auto': {None: dict(seed=5, close_p=0.02)},
+    'obs': {},
+    'reset': {None: dict(seed=21), ('left', 67): dict(seed=23), ('straight', 35): dict(seed=22), ('right', 67): dict(seed=24)},
+    'flow': {None: dict(steps=6, seed=3)},
+    'flow_auto': {None: dict(steps=2, seed=13), ('right', 67): dict(seed=15)},
+    'time_limit': {None: dict(seed=8)},
+}
+
+
+def env_params(kind, task, B):
+    p = ENV_PARAMS[kind]
+    return dict(p.get(None, {}), **p.get((task, B), {}))
+
+
+def env_rows():
+    """[(row id, kind or feature, key, Case)]: the 60 rows of ENV_HELD, then the 45 feature rows"""
+    rows = [(row_id(k), env_kind(c), k, c) for k, c in ENV_HELD.items()]
+    return rows + [('%s-%s' % (f, row_id(k)), f, k, ENV_HELD[k]) for f, k in ENV_FEATURES]
+
+
 def census(kernels):
-    """-> (held kernels that are no key of HELD, keys of HELD the library lacks, {family: (found, expected)} where COUNTED disagrees),
-    all empty when every kernel is accounted for"""
-    held = {key_of(k): k for k in kernels if k.family in HELD_FAMILIES and k.args is not None}
-    extra = sorted(k.symbol for key, k in held.items() if key not in HELD)
-    extra += sorted(k.symbol for k in kernels if k.family in HELD_FAMILIES and k.args is None)
-    missing = sorted(key for key in HELD if key not in held)
-    found = collections.Counter(k.family for k in kernels if k.family not in HELD_FAMILIES)
+    """-> (held kernels that are no key of HELD / ENV_HELD, keys of the two the library lacks, {family: (found, expected)} where COUNTED
+    disagrees), all empty when every kernel is accounted for"""
+    rows = set(HELD) | set(ENV_HELD)
+    held = {key_of(k): k for k in kernels if k.family in ALL_HELD_FAMILIES and k.args is not None}
+    extra = sorted(k.symbol for key, k in held.items() if key not in rows)
+    extra += sorted(k.symbol for k in kernels if k.family in ALL_HELD_FAMILIES and k.args is None)
+    missing = sorted((key for key in rows if key not in held), key=row_id)
+    found = collections.Counter(k.family for k in kernels if k.family not in ALL_HELD_FAMILIES)
     counts = {f: (found.get(f, 0), COUNTED.get(f, 0)) for f in set(found) | set(COUNTED) if found.get(f, 0) != COUNTED.get(f, 0)}
     return extra, missing, counts
 
@@ -228,6 +318,15 @@ def check_witness(key, launched):
     launched = set(launched)
     assert key in launched, 'the row claims %s, its call launches %s' % (row_id(key), sorted(row_id(k) for k in launched) or 'no held kernel')
     assert launched == {key}, 'the row claims %s, its call also launches %s' % (row_id(key), sorted(row_id(k) for k in launched - {key}))
+
+
+def is_hip_error(e):
+    """a HIP error (the card may have faulted: no more launches) as opposed to a failing comparison or a refused argument"""
+    from env_build_amd import _capi
+    if isinstance(e, AssertionError):
+        return False
+    text = str(e)                # an EbError from EB_HIP names the runtime call that failed (hipGetLastError(): ...); torch says 'HIP error'
+    return (isinstance(e, _capi.EbError) and re.search(r'\bhip[A-Z]', text) is not None) or 'HIP error' in text or 'hipError' in text
 
 
 # ---- host-side kernel handles of the loaded library ----
@@ -256,7 +355,7 @@ def handle_names(lib_path, loaded):
     with open(lib_path, 'rb') as fh:
         data = fh.read()
     table = elf_symbols(data)
-    anchor = next(s for s in kernel_symbols(data) if s in table and parse(s).family in FUSED)
+    anchor = next(s for s in kernel_symbols(data) if s in table and parse(s).family in FUSED)      # (a dynamic symbol)
     base = C.addressof(C.c_char.in_dll(loaded, anchor)) - table[anchor]
     return {base + table[s]: parse(s) for s in kernel_symbols(data) if s in table}
 

@@ -18,7 +18,6 @@ an MI355X: 3.6 s for the 123 rows (the slowest, the first to create a handle pai
 
 A faulted card gets no more launches: a row that ends in a HIP error makes every later row skip; a failing comparison does not."""
 import ctypes as C
-import re
 
 import numpy as np
 import pytest
@@ -36,11 +35,7 @@ _faulted = []                # the rows that ended in a HIP error
 _models, _scenes, _handles = {}, {}, {}
 
 
-def _is_hip_error(e):
-    if isinstance(e, AssertionError):
-        return False
-    text = str(e)                # an EbError from EB_HIP names the runtime call that failed (hipGetLastError(): ...); torch says 'HIP error'
-    return (isinstance(e, _capi.EbError) and re.search(r'\bhip[A-Z]', text) is not None) or 'HIP error' in text or 'hipError' in text
+_is_hip_error = K.is_hip_error
 
 
 def _pair(case):

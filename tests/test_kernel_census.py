@@ -1,6 +1,7 @@
 """CPU: every kernel of the cross-compiled libenvbuild_hip.so is accounted for by tests/_kernel_census.py — an instantiation of the
 rollout and closed-loop families is a key of HELD (launched and held against the oracle by tests/test_gpu_kernel_census.py, or
-Unreachable with the reason), every other family's instantiation count is in COUNTED.  A kernel or an instantiation that joins the
+Unreachable with the reason), an instantiation of the one-launch env kernels a key of ENV_HELD (tests/test_gpu_env_census.py; every
+one a Case), every other family's instantiation count is in COUNTED.  A kernel or an instantiation that joins the
 library makes this fail, naming it, until someone has decided where it belongs."""
 import collections
 import glob
@@ -34,7 +35,9 @@ def test_every_kernel_of_the_library_is_held_or_counted(kernels):
     found = collections.Counter(k.family for k in kernels)
     assert {f: found[f] for f in K.HELD_FAMILIES} == FAMILY_COUNTS
     assert found['env_step_kernel'] == 45 and found['env_reset_pool_kernel'] == 15
-    assert len(K.HELD) == 141 and sum(K.COUNTED.values()) == 167 and not set(K.COUNTED) & set(K.HELD_FAMILIES)
+    assert len(K.HELD) == 141 and len(K.ENV_HELD) == 60 and sum(K.COUNTED.values()) == 107
+    assert not set(K.COUNTED) & set(K.ALL_HELD_FAMILIES) and not set(K.HELD) & set(K.ENV_HELD)
+    assert len(K.HELD) + len(K.ENV_HELD) + sum(K.COUNTED.values()) == 308
 
 
 def test_rows_are_cases_or_unreachable_with_a_reason():
@@ -57,6 +60,65 @@ def test_rows_are_cases_or_unreachable_with_a_reason():
     assert K.batch_of(K.HELD[('rollout_fused_4x8', 0, True, 8, 'f32')]) == 131
     assert K.batch_of(K.HELD[('rollout_fused_1x4', 0, True, 4, 'f32')]) == 35
     assert K.batch_of(K.HELD[('rollout_tape_1x4', 2, False, 'f32')]) == 105
+
+
+def test_env_rows_are_cases_and_claim_their_key():
+    """ENV_HELD: 3 tasks x 5 (tile, waves) shapes x 4 kinds = 60 keys, every one a Case whose forced tile and waves reach the key by
+    the host's rule (launch_env_step); the feature rows sit on the 15 plain-step and the 15 auto-reset kernels"""
+    assert len(K.ENV_HELD) == 60 and all(isinstance(r, K.Case) for r in K.ENV_HELD.values())
+    want = {K.env_key(kind, t, et, nw) for kind in K.ENV_KINDS for t in range(3) for et, nw in K.ENV_SHAPES}
+    assert set(K.ENV_HELD) == want and len(want) == 60
+    assert collections.Counter(k[0] for k in K.ENV_HELD) == {'env_step_kernel': 45, 'env_reset_pool_kernel': 15}
+    for key, r in K.ENV_HELD.items():
+        assert K.claimed_env_kernel(r) == key, (key, r)
+        assert r.task == K.TASKS[key[1]] and r.n_veh == VEH_NUM[r.task] and r.mode == 'training' and r.waves == key[-1]
+        assert K.env_batch_of(r) == 2 * key[2] + 3 and r.entry == K.ENV_ENTRY[K.env_kind(r)]
+        if key[0] == 'env_step_kernel':
+            assert (key[3], key[4]) == {'step': (False, False), 'auto': (False, True), 'obs': (True, False)}[K.env_kind(r)]
+        else:
+            assert K.env_kind(r) == 'reset'
+    assert len(K.ENV_NEW) == 24 and all(k[-1] == 4 and k[2] in (16, 32) for k in K.ENV_NEW)
+    assert collections.Counter(f for f, _ in K.ENV_FEATURES) == {'flow': 15, 'flow_auto': 15, 'time_limit': 15}
+    for f, k in K.ENV_FEATURES:
+        assert k in K.ENV_HELD and k[0] == 'env_step_kernel' and not k[3] and k[4] == (f != 'flow')
+    rows = K.env_rows()
+    assert len(rows) == 105 and len({r[0] for r in rows}) == 105
+    # the default rule: waves left at 0, eight waves per block while the grid has at most 3 blocks per CU, on the small tiles only
+    free = lambda tile: K.ENV_HELD[K.env_key('step', 0, 64, 4)]._replace(tile=tile, waves=0)
+    assert K.claimed_env_kernel(free(2), n_env=16 * 768, n_cu=256) == K.env_key('step', 0, 16, 8)
+    assert K.claimed_env_kernel(free(2), n_env=16 * 768 + 1, n_cu=256) == K.env_key('step', 0, 16, 4)
+    assert K.claimed_env_kernel(free(1), n_env=32 * 768, n_cu=256) == K.env_key('step', 0, 32, 8)
+    assert K.claimed_env_kernel(free(1), n_env=32 * 768 + 1, n_cu=256) == K.env_key('step', 0, 32, 4)
+    assert K.claimed_env_kernel(free(1), n_env=32 * 3 * 213 + 1, n_cu=213) == K.env_key('step', 0, 32, 4)
+    assert K.claimed_env_kernel(free(0), n_env=64, n_cu=256) == K.env_key('step', 0, 64, 4)
+    assert K.claimed_env_kernel(free(0)._replace(waves=8)) == K.env_key('step', 0, 64, 4)      # no eight-wave kernel on 64-env tiles
+
+
+def test_the_env_witness_rejects_the_eight_wave_twin_and_a_new_tile_is_unaccounted_for(kernels):
+    for key in K.ENV_NEW:
+        twin = key[:-1] + (8,)
+        assert twin in K.ENV_HELD
+        K.check_witness(key, [key])
+        with pytest.raises(AssertionError, match='claims %s' % K.row_id(key)):
+            K.check_witness(key, [twin])
+    key = K.env_key('auto', 1, 16, 4)
+    with pytest.raises(AssertionError, match='also launches'):                        # (the reset as a launch of its own)
+        K.check_witness(key, [key, K.env_key('reset', 1, 16, 4)])
+    with pytest.raises(AssertionError, match='claims env_step_kernel-1-16-0-1-4'):    # the plain step where the auto reset is claimed
+        K.check_witness(key, [K.env_key('step', 1, 16, 4)])
+    p = K.parse
+    assert p('_ZN2eb15env_step_kernelILi2ELi32ELb1ELb0ELi8EEEvNS_11EnvStepArgsE')[:2] == ('env_step_kernel', (2, 32, True, False, 8))
+    assert p('_ZN2eb21env_reset_pool_kernelILi0ELi64ELi4EEEvNS_11EnvStepArgsE')[:2] == ('env_reset_pool_kernel', (0, 64, 4))
+    with open(eb_build.LIB, 'rb') as fh:
+        data = fh.read()
+    for new in ('_ZN2eb15env_step_kernelILi0ELi128ELb0ELb0ELi4EEEvNS_11EnvStepArgsE',       # a 128-env tile
+                '_ZN2eb15env_step_kernelILi0ELi64ELb0ELb0ELi8EEEvNS_11EnvStepArgsE',        # eight waves on the 64-env tile
+                '_ZN2eb21env_reset_pool_kernelILi1ELi16ELi2EEEvNS_11EnvStepArgsE'):         # two waves per block
+        extra, missing, counts = K.census([K.parse(s) for s in K.kernel_symbols(data + new.encode() + b'.kd\0')])
+        assert extra == [new] and not missing and not counts
+    gone = K.env_key('obs', 2, 16, 4)
+    extra, missing, counts = K.census([k for k in kernels if K.key_of(k) != gone])
+    assert missing == [gone] and not extra and not counts
 
 
 def test_no_header_declares_a_gated_fp16_entry():
@@ -136,6 +198,9 @@ def test_host_handles_of_every_kernel_are_in_the_symbol_table(kernels):
     held = [k for k in kernels if k.family in K.HELD_FAMILIES]
     assert len(held) == 141 and all(k.symbol in table for k in held)
     assert len({table[k.symbol] for k in held}) == 141
+    env = [k for k in kernels if k.family in K.ENV_FAMILIES]
+    assert len(env) == 60 and all(k.symbol in table for k in env)
+    assert len({table[k.symbol] for k in held + env}) == 201
 
 
 def test_every_row_has_a_vehicle_near_an_ego_in_its_first_tile():
