@@ -310,7 +310,8 @@ def _sincos_det(x):
     x = np.asarray(x, _f)
     with np.errstate(all='ignore'):
         kf = np.rint(x * _f(0.636619747)).astype(_f)
-        k = kf.astype(np.int64)
+        # the device's v_cvt_i32_f32 (the oracle's cvt_i32_f32): saturating at -2^31 and 2^31 - 1, NaN -> 0
+        k = np.clip(np.nan_to_num(kf.astype(np.float64), nan=0.0), -2.0 ** 31, 2.0 ** 31 - 1).astype(np.int64)
         r = _fmaf(-kf, _f(1.5703125), x)
         r = _fmaf(-kf, _f(4.83751296997070312e-4), r)
         r = _fmaf(-kf, _f(7.54978995489188216e-8), r)

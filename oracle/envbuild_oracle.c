@@ -13,8 +13,10 @@
  * against fixtures under tests/golden/ produced by running the reference's OWN Python files,
  * unmodified, over NumPy-fp32 stand-ins for the tf.* symbols (oracle/gen_golden.py).  At the
  * TF-kernel boundary itself (Eigen's sin/cos/atan) parity is UNPINNED: TF's, NumPy's and this
- * file's transcendental kernels each carry <= 2 ulp error, which is why the fixture comparison
- * uses rtol 1e-5 (+ a stated atol) rather than bit equality.
+ * file's transcendental kernels each carry a few ulp of error (this file's: measured against float64 per
+ * function and domain in DESIGN.md section 4 and held there by tests/test_math_accuracy_host.py: sin/cos
+ * <= 2 ulp on |x| <= pi/4 and <= 2^-23 absolute up to 2^16 * pi/2, atan <= 3 ulp, exp <= 2 ulp), which is
+ * why the fixture comparison uses rtol 1e-5 (+ a stated atol) rather than bit equality.
  *
  * Deliberate choices (all documented in DESIGN.md):
  *  - sin/cos/atan are the deterministic Cephes-style fp32 kernels below (only IEEE + - * / fma
@@ -62,12 +64,23 @@ static const float EXP_V = 8.0f;                    /* EXPECTED_V, UTL:18 */
 /* ------------------------------------------------------------------------------------------ */
 /* deterministic fp32 transcendental kernels (Cephes single-precision scheme)                  */
 /* ------------------------------------------------------------------------------------------ */
+/* The device's float -> int32 conversion (v_cvt_i32_f32) of an integral float: saturating at both ends, NaN -> 0.  In C the
+ * plain cast is undefined from 2^31 on (x86 gives INT_MIN there); the quadrant of eb_sincosf for x >= 2^31 * pi/2, +-inf and
+ * NaN is the device's by this rule (tests/test_gpu_math_probe.py holds the device to it). */
+static int cvt_i32_f32(float kf) {
+    if (!(kf == kf)) return 0;
+    if (kf >= 2147483648.0f) return 2147483647;
+    if (kf <= -2147483648.0f) return -2147483647 - 1;
+    return (int)kf;
+}
+
 static void eb_sincosf(float x, float* s_out, float* c_out) {
     /* k = nearest integer to x / (pi/2); r = x - k*pi/2 by 3-term Cody-Waite with fused steps;
      * minimax polynomials on |r| <= pi/4, Horner with explicit fmaf (correctly rounded with or
-     * without hardware FMA, so the HIP kernels' v_fma_f32 sequence gives the same bits). */
+     * without hardware FMA, so the HIP kernels' v_fma_f32 sequence gives the same bits).
+     * The reduction is exact only while k * 1.5703125 is (|x| up to about 1e5); beyond 2^16 * pi/2 no accuracy is claimed. */
     float kf = nearbyintf(x * 0.636619747f);
-    int k = (int)kf;
+    int k = cvt_i32_f32(kf);
     float r = fmaf(-kf, 1.5703125f, x);
     r = fmaf(-kf, 4.83751296997070312e-4f, r);
     r = fmaf(-kf, 7.54978995489188216e-8f, r);
@@ -1471,7 +1484,7 @@ int eb_oracle_set_threads(int n) {
 #endif
 }
 
-/* exposes the deterministic kernels so tests can bound their error against libm */
+/* exposes the deterministic kernels so tests can bound their error against float64 and hold the device's to the same bits */
 void eb_oracle_sincosf(const float* x, float* s, float* c, int n) {
     for (int i = 0; i < n; ++i) eb_sincosf(x[i], s + i, c + i);
 }
@@ -1856,6 +1869,14 @@ static float eb_tanhf(float x) { /* Cephes tanhf scheme; device twin: eb_mlp_dev
     p = fmaf(p, z, 1.33314422036e-1f);
     p = fmaf(p, z, -3.33332819422e-1f);
     return fmaf(p * z, x, x);
+}
+
+/* exposes the two kernels elementwise (tests/test_math_accuracy_host.py, tests/test_gpu_math_probe.py), as eb_oracle_sincosf / eb_oracle_atanf do */
+void eb_oracle_expf(const float* x, float* y, int n) {
+    for (int i = 0; i < n; ++i) y[i] = eb_expf(x[i]);
+}
+void eb_oracle_tanhf(const float* x, float* y, int n) {
+    for (int i = 0; i < n; ++i) y[i] = eb_tanhf(x[i]);
 }
 
 static float mlp_activate(int act, float x) {
