@@ -13,7 +13,8 @@ it is rebuilt when hipcc is there, and `_capi.hip_api()` refuses to load it othe
 own with its own source list and hash, which `env_build_amd.train` loads on first use and nothing else does.
 `build_epoch()` likewise for env_build_amd/lib/libenvbuild_epoch.so (csrc/eb_epoch.hip), which `env_build_amd.epoch` loads, and
 `build_collect()` for env_build_amd/lib/libenvbuild_collect.so (csrc/eb_collect.hip), which `env_build_amd.collect` loads, and
-`build_ctl()` for env_build_amd/lib/libenvbuild_ctl.so (csrc/eb_ctl.hip), which `env_build_amd.ctl` loads."""
+`build_ctl()` for env_build_amd/lib/libenvbuild_ctl.so (csrc/eb_ctl.hip), which `env_build_amd.ctl` loads, and
+`build_ac()` for env_build_amd/lib/libenvbuild_ac.so (csrc/eb_ac.hip), which `env_build_amd.ac` loads."""
 import hashlib
 import os
 import subprocess
@@ -310,9 +311,55 @@ def build_ctl(force=False, verbose=False):
         return _build_locked(verbose, CTL_LIB, CTL_SOURCES, ctl_source_hash())
 
 
+# ---- libenvbuild_ac.so: the two row kernels of a shared-trunk actor-critic — the PPO and value-loss rows with the whole cotangent, and
+# the sampling row with the split (include/envbuild_ac.h).  A sixth library of its own, built the way the other four small ones are.  Its
+# unit calls the row functions of eb_policy_logp_device.h (and, through it, eb_policy_sample_device.h, eb_mlp_device.h, eb_env_device.h
+# and what they include) and of eb_train_device.h, so those headers are part of this library's hash too (and stay in HEADERS and
+# TRAIN_HEADERS, unchanged). ----
+AC_LIB = os.path.join(HERE, 'lib', 'libenvbuild_ac.so')
+AC_SOURCES = ['eb_ac.hip']
+AC_HEADERS = ['eb_ac.h', os.path.join('..', '..', 'include', 'envbuild_ac.h'),
+              'eb_policy_logp_device.h', 'eb_policy_sample_device.h', 'eb_mlp_device.h', 'eb_env_device.h', 'eb_device.h', 'eb_kernels.h',
+              'eb_train_device.h', os.path.join('..', '..', 'include', 'envbuild.h')]
+
+
+def ac_source_hash():
+    """source_hash() of the actor-critic library: the flags and the bytes of AC_SOURCES and AC_HEADERS"""
+    h = hashlib.sha256()
+    h.update('\0'.join(FLAGS + ['|'] + LINK_FLAGS).encode())
+    for f in AC_SOURCES + AC_HEADERS:
+        h.update(b'\0' + f.encode() + b'\0')
+        with open(os.path.join(CSRC, f), 'rb') as fh:
+            h.update(fh.read())
+    return h.hexdigest()
+
+
+def ac_needs_build():
+    try:
+        with open(AC_LIB + '.srchash') as fh:
+            built = fh.read().strip()
+    except OSError:
+        built = None
+    return not os.path.isfile(AC_LIB) or built != ac_source_hash()
+
+
+def build_ac(force=False, verbose=False):
+    """build() for libenvbuild_ac.so"""
+    if not force and not ac_needs_build():
+        return AC_LIB
+    import fcntl
+    os.makedirs(os.path.dirname(AC_LIB), exist_ok=True)
+    with open(AC_LIB + '.lock', 'w') as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        if not force and not ac_needs_build():
+            return AC_LIB
+        return _build_locked(verbose, AC_LIB, AC_SOURCES, ac_source_hash())
+
+
 if __name__ == '__main__':
     print(build(force=True, verbose=True))
     print(build_train(force=True, verbose=True))
     print(build_epoch(force=True, verbose=True))
     print(build_collect(force=True, verbose=True))
     print(build_ctl(force=True, verbose=True))
+    print(build_ac(force=True, verbose=True))
