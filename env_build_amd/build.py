@@ -14,7 +14,8 @@ own with its own source list and hash, which `env_build_amd.train` loads on firs
 `build_epoch()` likewise for env_build_amd/lib/libenvbuild_epoch.so (csrc/eb_epoch.hip), which `env_build_amd.epoch` loads, and
 `build_collect()` for env_build_amd/lib/libenvbuild_collect.so (csrc/eb_collect.hip), which `env_build_amd.collect` loads, and
 `build_ctl()` for env_build_amd/lib/libenvbuild_ctl.so (csrc/eb_ctl.hip), which `env_build_amd.ctl` loads, and
-`build_ac()` for env_build_amd/lib/libenvbuild_ac.so (csrc/eb_ac.hip), which `env_build_amd.ac` loads."""
+`build_ac()` for env_build_amd/lib/libenvbuild_ac.so (csrc/eb_ac.hip), which `env_build_amd.ac` loads, and
+`build_norm()` for env_build_amd/lib/libenvbuild_norm.so (csrc/eb_norm.hip), which `env_build_amd.norm` loads."""
 import hashlib
 import os
 import subprocess
@@ -356,6 +357,48 @@ def build_ac(force=False, verbose=False):
         return _build_locked(verbose, AC_LIB, AC_SOURCES, ac_source_hash())
 
 
+# ---- libenvbuild_norm.so: the running normalisation of observations and rewards — the batch sums, the merge into the running statistics
+# and the normalisation (include/envbuild_norm.h).  A seventh library of its own, built the way the other five small ones are; it includes
+# no header of theirs. ----
+NORM_LIB = os.path.join(HERE, 'lib', 'libenvbuild_norm.so')
+NORM_SOURCES = ['eb_norm.hip']
+NORM_HEADERS = ['eb_norm.h', 'eb_norm_device.h', os.path.join('..', '..', 'include', 'envbuild_norm.h'),
+                os.path.join('..', '..', 'include', 'envbuild.h')]
+
+
+def norm_source_hash():
+    """source_hash() of the normalisation library: the flags and the bytes of NORM_SOURCES and NORM_HEADERS"""
+    h = hashlib.sha256()
+    h.update('\0'.join(FLAGS + ['|'] + LINK_FLAGS).encode())
+    for f in NORM_SOURCES + NORM_HEADERS:
+        h.update(b'\0' + f.encode() + b'\0')
+        with open(os.path.join(CSRC, f), 'rb') as fh:
+            h.update(fh.read())
+    return h.hexdigest()
+
+
+def norm_needs_build():
+    try:
+        with open(NORM_LIB + '.srchash') as fh:
+            built = fh.read().strip()
+    except OSError:
+        built = None
+    return not os.path.isfile(NORM_LIB) or built != norm_source_hash()
+
+
+def build_norm(force=False, verbose=False):
+    """build() for libenvbuild_norm.so"""
+    if not force and not norm_needs_build():
+        return NORM_LIB
+    import fcntl
+    os.makedirs(os.path.dirname(NORM_LIB), exist_ok=True)
+    with open(NORM_LIB + '.lock', 'w') as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        if not force and not norm_needs_build():
+            return NORM_LIB
+        return _build_locked(verbose, NORM_LIB, NORM_SOURCES, norm_source_hash())
+
+
 if __name__ == '__main__':
     print(build(force=True, verbose=True))
     print(build_train(force=True, verbose=True))
@@ -363,3 +406,4 @@ if __name__ == '__main__':
     print(build_collect(force=True, verbose=True))
     print(build_ctl(force=True, verbose=True))
     print(build_ac(force=True, verbose=True))
+    print(build_norm(force=True, verbose=True))

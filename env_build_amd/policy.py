@@ -297,7 +297,9 @@ class Policy4Toyota(object):
 class LoadPolicy(object):
     """utils/load_policy.py:19-63.  `exp_dir/config.json` holds the arguments; the weights come from
     `exp_dir/models/weights_ite{iter}.npz` when present (else the random initialisation stands — useful for
-    benchmarks).  The preprocessor is folded into the kernels, so run_batch / obj_value_batch take raw obs."""
+    benchmarks).  The 'scale' preprocessor is folded into the kernels and the 'normalize' one (env_build_amd.norm.Preprocessor, its
+    parameters from `exp_dir/models/ppc_params.npz` or the reference's `ppc_params.npy` when present) runs as one launch in front of them,
+    so run_batch / obj_value_batch take raw obs."""
 
     def __init__(self, exp_dir=None, iter=None, args=None, device=None):
         if args is None:
@@ -307,6 +309,7 @@ class LoadPolicy(object):
             args = SimpleNamespace(**args)
         self.args = args
         self.policy = Policy4Toyota(args, device=device)
+        self.preprocessor, self._scratch = None, None
         if exp_dir is not None and iter is not None:
             self.policy.load_weights(os.path.join(exp_dir, 'models'), iter)
         if getattr(args, 'obs_preprocess_type', 'scale') == 'scale' and getattr(args, 'obs_scale', None) is not None:
@@ -314,13 +317,29 @@ class LoadPolicy(object):
             for m in self.policy.models:
                 m.set_obs_scale(scale)
         elif getattr(args, 'obs_preprocess_type', None) == 'normalize':
-            raise NotImplementedError("obs_preprocess_type 'normalize' (running statistics) is not supported")
+            from .norm import Preprocessor             # utils/load_policy.py:32-34: running statistics, on the device (envbuild_norm.h)
+            self.preprocessor = Preprocessor((int(args.obs_dim),), 'normalize', getattr(args, 'reward_preprocess_type', None),
+                                             gamma=getattr(args, 'gamma', 0.99), device=self.policy.policy.device)
+            models = os.path.join(exp_dir, 'models') if exp_dir is not None else None
+            if models is not None and any(os.path.isfile(os.path.join(models, 'ppc_params' + e)) for e in ('.npz', '.npy')):
+                self.preprocessor.load_params(models)
+
+    def _processed(self, obses):
+        """eb_norm_apply into a scratch tensor in front of the network when the preprocessor is 'normalize'; else obses as they are"""
+        if self.preprocessor is None:
+            return obses
+        from .norm import apply
+        x = _dev(obses, self.policy.policy.device)
+        if self._scratch is None or self._scratch.shape != x.shape:
+            self._scratch = torch.empty_like(x)
+        apply(self.preprocessor.ob_rms, x, self._scratch, self.preprocessor.clipob)
+        return self._scratch
 
     def run_batch(self, obses):                        # utils/load_policy.py:53-57
-        actions, _ = self.policy.compute_action(obses)
+        actions, _ = self.policy.compute_action(self._processed(obses))
         return actions
 
     def obj_value_batch(self, obses):                  # utils/load_policy.py:59-63
-        return self.policy.compute_obj_v(obses)
+        return self.policy.compute_obj_v(self._processed(obses))
 
     __call__ = run_batch
