@@ -23,6 +23,10 @@
  *    and rint), NOT libm's, so the HIP kernels can reproduce them bit-for-bit.
  *  - python-float constants are rounded to fp32 at the op where they meet a tensor, in the
  *    reference's evaluation order.
+ *  - the penalty sums are formed in one of two stated orders, eb_oracle_set_penalty_order(): 0, the default, the
+ *    reference's term-by-term sum (what the fixtures are compared in); 1, per vehicle record and then in slot order,
+ *    which is what every HIP kernel computes — the order the GPU tests hold the kernels to bit for bit.
+ *    eb_oracle_penalty_terms() exports the terms themselves, unsummed (tests/_penalty.py re-adds them).
  */
 #define _POSIX_C_SOURCE 200809L
 #include "../include/envbuild.h"
@@ -138,6 +142,7 @@ struct eb_handle_s {
     uint8_t vmode[EB_MAX_VEH]; /* EB_VMODE_* per slot */
     uint8_t turn[EB_MAX_VEH];  /* 0 none, 1 left-turn, 2 right-turn: DAM:416-421 */
     int modes_set;
+    int pen_order;             /* EB_PEN_ORDER_*: how v2v_train / v2v_real are associated (eb_oracle_set_penalty_order) */
 };
 
 enum { TURN_NONE = 0, TURN_LEFT = 1, TURN_RIGHT = 2 };
@@ -306,8 +311,38 @@ static void road_terms(int task, float px, float py, float* train, float* real) 
     *train = t; *real = q;
 }
 
+/* The association of the circle-pair terms in v2v_train / v2v_real.
+ *  REFERENCE: one running sum, a term at a time, as DAM:218-229 writes it.  The default: what the fixtures pin.
+ *  RECORD:    per vehicle ((ff + fr) + rf) + rr, the partials joined in slot order — the one order every HIP kernel
+ *             uses, so that a kernel's penalty sums can be held bit for bit. */
+enum { EB_PEN_ORDER_REFERENCE = 0, EB_PEN_ORDER_RECORD = 1 };
+
+/* the ego's circle centres (front x, front y, rear x, rear y), DAM:211-214 */
+static void ego_points(const float* ego, float* pts) {
+    float es, ec;
+    eb_sincosf(deg2rad(ego[5]), &es, &ec);
+    pts[0] = ego[3] + LWS * ec; pts[1] = ego[4] + LWS * es;
+    pts[2] = ego[3] - LWS * ec; pts[3] = ego[4] - LWS * es;
+}
+
+/* the four circle-pair terms of one vehicle record in the order ff, fr, rf, rr, DAM:219-229 */
+static void veh2veh_terms(const float* pts, const float* v, float* t35, float* t25) {
+    float vs, vc;
+    eb_sincosf(deg2rad(v[3]), &vs, &vc);
+    float vfx = v[0] + LWS * vc, vfy = v[1] + LWS * vs;
+    float vrx = v[0] - LWS * vc, vry = v[1] - LWS * vs;
+    const float ex[2] = {pts[0], pts[2]}, ey[2] = {pts[1], pts[3]}, wx[2] = {vfx, vrx}, wy[2] = {vfy, vry};
+    for (int p = 0; p < 2; ++p)
+        for (int q = 0; q < 2; ++q) {
+            float d = sqrtf(sq(ex[p] - wx[q]) + sq(ey[p] - wy[q]));
+            float a = d - 3.5f, b = d - 2.5f;
+            t35[2 * p + q] = a < 0.0f ? sq(a) : 0.0f;
+            t25[2 * p + q] = b < 0.0f ? sq(b) : 0.0f;
+        }
+}
+
 /* out5: rewards, punish_train, punish_real, veh2veh4real, veh2road4real; d16 nullable. */
-static void rewards_row(const eb_config* c, const float* obs, const float* act, float* o5, float* d16) {
+static void rewards_row(const eb_config* c, int pen_order, const float* obs, const float* act, float* o5, float* d16) {
     const float* ego = obs;
     const float* trk = obs + 6;
     const float* veh = obs + 6 + 3 * (c->n_future + 1);
@@ -318,25 +353,19 @@ static void rewards_row(const eb_config* c, const float* obs, const float* act, 
     float devi_y = -sq(trk[0]);                        /* DAM:205 */
     float devi_phi = -sq(deg2rad(trk[1]));             /* DAM:206 */
     float devi_v = -sq(trk[2]);                        /* DAM:207 */
-    float es, ec;
-    eb_sincosf(deg2rad(ego[5]), &es, &ec);
-    float efx = ego[3] + LWS * ec, efy = ego[4] + LWS * es; /* DAM:211-212 */
-    float erx = ego[3] - LWS * ec, ery = ego[4] - LWS * es; /* DAM:213-214 */
+    float pts[4];
+    ego_points(ego, pts);                                   /* DAM:211-214 */
+    const float efx = pts[0], efy = pts[1], erx = pts[2], ery = pts[3];
     float v2v_real = 0.0f, v2v_train = 0.0f;                /* DAM:215-216 */
     for (int j = 0; j < c->n_veh; ++j) {                    /* DAM:218-229 */
-        const float* v = veh + 4 * j;
-        float vs, vc;
-        eb_sincosf(deg2rad(v[3]), &vs, &vc);
-        float vfx = v[0] + LWS * vc, vfy = v[1] + LWS * vs;
-        float vrx = v[0] - LWS * vc, vry = v[1] - LWS * vs;
-        const float ex[2] = {efx, erx}, ey[2] = {efy, ery}, wx[2] = {vfx, vrx}, wy[2] = {vfy, vry};
-        for (int p = 0; p < 2; ++p)
-            for (int q = 0; q < 2; ++q) {
-                float d = sqrtf(sq(ex[p] - wx[q]) + sq(ey[p] - wy[q]));
-                float t35 = d - 3.5f, t25 = d - 2.5f;
-                v2v_train += t35 < 0.0f ? sq(t35) : 0.0f;
-                v2v_real += t25 < 0.0f ? sq(t25) : 0.0f;
-            }
+        float t35[4], t25[4];
+        veh2veh_terms(pts, veh + 4 * j, t35, t25);
+        if (pen_order == EB_PEN_ORDER_RECORD) {
+            v2v_train += ((t35[0] + t35[1]) + t35[2]) + t35[3];
+            v2v_real += ((t25[0] + t25[1]) + t25[2]) + t25[3];
+        } else {
+            for (int k = 0; k < 4; ++k) { v2v_train += t35[k]; v2v_real += t25[k]; }
+        }
     }
     float road_train = 0.0f, road_real = 0.0f;              /* DAM:231-232 */
     /* the reference interleaves, per ego point, 4 training terms then 4 real terms; each
@@ -367,10 +396,41 @@ int eb_compute_rewards(eb_handle h, int32_t n_env, const float* obs, const float
 #pragma omp parallel for schedule(static)
     for (int i = 0; i < n_env; ++i) {
         float o5[5], d16[16];
-        rewards_row(&h->cfg, obs + (size_t)D * i, actions + 2 * (size_t)i, o5, out_dict16 ? d16 : NULL);
+        rewards_row(&h->cfg, h->pen_order, obs + (size_t)D * i, actions + 2 * (size_t)i, o5, out_dict16 ? d16 : NULL);
         for (int k = 0; k < 5; ++k) out5[(size_t)k * n_env + i] = o5[k];
         if (out_dict16)
             for (int k = 0; k < 16; ++k) out_dict16[(size_t)k * n_env + i] = d16[k];
+    }
+    return EB_OK;
+}
+
+/* Test hook: which association the penalty sums of this handle use from now on (every entry that outputs them forms them in
+ * rewards_row: eb_compute_rewards and its dict, the rollout step / tape / gated twins, eb_env_step, eb_shield_is_safe). */
+int eb_oracle_set_penalty_order(eb_handle h, int order) {
+    if (!h) return fail(EB_EINVAL, "eb_oracle_set_penalty_order: null handle");
+    if (order != EB_PEN_ORDER_REFERENCE && order != EB_PEN_ORDER_RECORD)
+        return fail(EB_EINVAL, "eb_oracle_set_penalty_order: unknown order");
+    h->pen_order = order;
+    return EB_OK;
+}
+
+/* Test hook: the fp32 terms the penalty sums are made of, nothing summed: t35 / t25 [n_env, n_veh, 4] (ff, fr, rf, rr per
+ * slot); road [n_env, 2] = (road_train, road_real), whose own order (front point's walls, then the rear's) is the same in
+ * the reference and in every kernel. */
+int eb_oracle_penalty_terms(eb_handle h, int32_t n_env, const float* obs, float* t35, float* t25, float* road) {
+    if (!h || n_env < 0 || !obs || !t35 || !t25 || !road) return fail(EB_EINVAL, "eb_oracle_penalty_terms: bad argument");
+    const int D = obs_dim(&h->cfg), NV = h->cfg.n_veh;
+    for (int i = 0; i < n_env; ++i) {
+        const float* o = obs + (size_t)D * i;
+        const float* veh = o + 6 + 3 * (h->cfg.n_future + 1);
+        float pts[4];
+        ego_points(o, pts);
+        for (int j = 0; j < NV; ++j)
+            veh2veh_terms(pts, veh + 4 * j, t35 + 4 * ((size_t)NV * i + j), t25 + 4 * ((size_t)NV * i + j));
+        float rt = 0.0f, rr = 0.0f;
+        road_terms(h->cfg.task, pts[0], pts[1], &rt, &rr);
+        road_terms(h->cfg.task, pts[2], pts[3], &rt, &rr);
+        road[2 * (size_t)i] = rt; road[2 * (size_t)i + 1] = rr;
     }
     return EB_OK;
 }
@@ -653,7 +713,7 @@ int eb_rollout_step(eb_handle h, int32_t n_env, const float* obs_in, const float
     for (int i = 0; i < n_env; ++i) {
         float act[2], o5[5];
         action_transform_row(actions + 2 * (size_t)i, act);        /* DAM:120 */
-        rewards_row(&h->cfg, obs_in + (size_t)D * i, act, o5, NULL); /* DAM:121-122 */
+        rewards_row(&h->cfg, h->pen_order, obs_in + (size_t)D * i, act, o5, NULL); /* DAM:121-122 */
         int p = training ? row_path(h, ref_idx, 0, i) : path_id;
         float tmp[6 + 3 * 65 + 4 * EB_MAX_VEH];
         next_obs_row(h, obs_in + (size_t)D * i, act, p, tmp);       /* DAM:123 */

@@ -7,7 +7,7 @@ a small-tile launch takes four waves only above 3 * n_cu blocks, which no other 
 
 Numerics, by the suite's existing bars (tests/test_gpu_parity.py): the case functions of tests/_env_step_check.py on DeviceModel with
 tile and waves forced (each asserts the one launch against the HIP library's single calls, bit for bit) and on the oracle; the two results
-bit for bit, the three penalty sums by check_out5's rule, the 16-row dictionary within PEN_RTOL.  step: composite_case; auto reset:
+bit for bit, the penalty sums and the 16-row dictionary bit for bit too (the oracle sums them in the kernels' order).  step: composite_case; auto reset:
 auto_reset_case; observation: eb_get_obs against the oracle and masked_obs_case; masked reset: reset_pool_case; features: flow_rule_case
 (plain step) and flow_auto_reset_case, time_limit_case (auto reset) at K = 2 routes per approach.  The oracle's result is computed once
 per scene (a kind, a task, a batch) and shared by the rows of every tile shape.
@@ -31,7 +31,7 @@ import pytest
 
 from env_build_amd import _capi
 from tests import _capture, _capture_cases as CC, _env_census as EC, _kernel_census as K
-from tests._helpers import PEN_RTOL, DeviceModel, HostModel, check_out5, oracle_lib
+from tests._helpers import DeviceModel, HostModel, bits_equal, check_out5, oracle_lib, record_host
 
 pytestmark = pytest.mark.gpu
 ROWS = K.env_rows()
@@ -42,7 +42,7 @@ _want, _handles, _clock = {}, {}, []
 
 
 def _on_cpu(t, **kw):
-    return HostModel(oracle_lib(), t, **kw)
+    return record_host(t, **kw)
 
 
 def _reference(kind, task, B):
@@ -60,9 +60,9 @@ def _compare(want, got, B, what, nan_ok):
     elif want is None:
         assert got is None, what
     elif want.dtype == np.float32 and want.shape == (5, B):
-        check_out5(got, want, what)
+        check_out5(got, want, what, exact=True)
     elif want.shape == (16, B):
-        np.testing.assert_allclose(got, want, rtol=PEN_RTOL, atol=0, err_msg=what)
+        bits_equal(got, want, what)
     else:
         assert np.array_equal(want, got, equal_nan=nan_ok), '%s: %d of %d elements differ' % (what, int((want != got).sum()), want.size)
 

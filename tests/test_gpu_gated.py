@@ -10,19 +10,24 @@ import pytest
 from env_build_amd import _capi
 
 from env_build_amd.synthetic import make_rollout_inputs
-from tests._helpers import DeviceModel, HostModel, check_out5_steps, initial_obs, oracle_lib, stepwise
+from tests._helpers import DeviceModel, HostModel, check_out5_steps, initial_obs, oracle_lib, record_host, stepwise
 
 pytestmark = pytest.mark.gpu
 
 
-_initial_obs, _stepwise, _check = initial_obs, stepwise, check_out5_steps      # (tests/_helpers.py: the census rows are held to the same text)
+_initial_obs, _stepwise = initial_obs, stepwise      # (tests/_helpers.py: the census rows are held to the same text)
+
+
+def _check(o5_d, o5_h):
+    """against record_host's sums: every row of out5 bit for bit"""
+    check_out5_steps(o5_d, o5_h, exact=True)
 
 
 @pytest.mark.parametrize('task,N,B,tile,nf', [('left', 16, 4096, -1, 0), ('straight', 9, 777, 2, 2), ('right', 32, 1500, 1, 0),
                                             ('left', 32, 3000, 0, 0)])
 def test_gated_rollout_with_open_gates_equals_stepwise(task, N, B, tile, nf):
     H = 9
-    host, dev = HostModel(oracle_lib(), task, n_veh=N, n_future=nf), DeviceModel(task, n_veh=N, n_future=nf)
+    host, dev = record_host(task, n_veh=N, n_future=nf), DeviceModel(task, n_veh=N, n_future=nf)
     dev.set_tile(tile)
     inp = make_rollout_inputs(task, B, N, H, seed=40 + N, n_future=nf)
     obs0 = _initial_obs(host, inp)
@@ -47,7 +52,7 @@ def test_gated_rollout_fed_step_by_step_from_another_stream(B, N):
     has published step t - 1; the rollout's blocks wait at their gates in between."""
     import torch
     task, H = 'left', 12
-    host, dev = HostModel(oracle_lib(), task, n_veh=N), DeviceModel(task, n_veh=N)
+    host, dev = record_host(task, n_veh=N), DeviceModel(task, n_veh=N)
     inp = make_rollout_inputs(task, B, N, H, seed=7)
     obs0 = _initial_obs(host, inp)
     want_obs, want_o5, want_states = _stepwise(host, obs0, inp, H)
@@ -76,7 +81,7 @@ def test_gated_rollout_fed_step_by_step_from_another_stream(B, N):
 
 def test_gated_rollout_gives_up_at_a_shut_gate_and_refuses_oversized_batches():
     task, N, B, H = 'left', 16, 1024, 6
-    host, dev = HostModel(oracle_lib(), task, n_veh=N), DeviceModel(task, n_veh=N)
+    host, dev = record_host(task, n_veh=N), DeviceModel(task, n_veh=N)
     inp = make_rollout_inputs(task, B, N, H, seed=3)
     obs0 = _initial_obs(host, inp)
     ready = np.ones(H, np.int32)

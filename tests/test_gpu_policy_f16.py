@@ -16,7 +16,7 @@ from env_build_amd import _capi  # noqa: E402
 from env_build_amd.policy import _tanh_det, mlp_f16_reference  # noqa: E402
 from env_build_amd.synthetic import assemble_obs, make_rollout_inputs  # noqa: E402
 from tests._grad_cases import column_tolerance  # noqa: E402
-from tests._helpers import DeviceModel, HostModel, golden, oracle_lib  # noqa: E402
+from tests._helpers import DeviceModel, HostModel, golden, oracle_lib, record_host  # noqa: E402
 from tests._policy import F16, F32, f16_mlp, loop, loop_view, same, sparse_signs  # noqa: E402
 from tests._policy_cases import CONFIGS, G14, make_layers  # noqa: E402
 
@@ -117,7 +117,7 @@ def test_random_networks_within_the_column_bound(cfg):
 
 # ---- shared: a model, start states and a 2 x 256 policy ----
 def shield_case(task, N, B=300, seed=21, mode='training'):
-    host, dev = HostModel(oracle_lib(), task, n_veh=N, mode=mode), DeviceModel(task, n_veh=N, mode=mode)
+    host, dev = record_host(task, n_veh=N, mode=mode), DeviceModel(task, n_veh=N, mode=mode)
     inp = make_rollout_inputs(task, B, N, 5, seed=seed)
     trk = host.tracking_error(inp['ego'][:, 3], inp['ego'][:, 4], inp['ego'][:, 5], inp['ego'][:, 0], 0, ref_idx=inp['ref_idx'])
     obs0 = assemble_obs(inp['ego'], trk, inp['veh'])
@@ -143,8 +143,7 @@ def test_fp32_handles_keep_the_oracle_bits():
         assert same(dev.policy_run_batch(md, 2, obs0, 1.0), host.policy_run_batch(mh, 2, obs0, 1.0))
         w = host.shield_is_safe(mh, obs0, ref_idx=inp['ref_idx'], steps=5, penalty=0)
         g = dev.shield_is_safe(md, obs0, ref_idx=inp['ref_idx'], steps=5, penalty=0)
-        assert same(g[0], w[0]) and same(g[2], w[2]) and same(g[3], w[3])
-        np.testing.assert_allclose(g[1], w[1], rtol=5e-6, atol=0)   # penalty sums: tests/test_gpu_policy.py
+        assert same(g[0], w[0]) and same(g[1], w[1]) and same(g[2], w[2]) and same(g[3], w[3])   # (penalty sums: the oracle in the kernels' order)
         dev.api.mlp_destroy(md)
     host.api.mlp_destroy(mh)
 
