@@ -15,7 +15,8 @@ own with its own source list and hash, which `env_build_amd.train` loads on firs
 `build_collect()` for env_build_amd/lib/libenvbuild_collect.so (csrc/eb_collect.hip), which `env_build_amd.collect` loads, and
 `build_ctl()` for env_build_amd/lib/libenvbuild_ctl.so (csrc/eb_ctl.hip), which `env_build_amd.ctl` loads, and
 `build_ac()` for env_build_amd/lib/libenvbuild_ac.so (csrc/eb_ac.hip), which `env_build_amd.ac` loads, and
-`build_norm()` for env_build_amd/lib/libenvbuild_norm.so (csrc/eb_norm.hip), which `env_build_amd.norm` loads."""
+`build_norm()` for env_build_amd/lib/libenvbuild_norm.so (csrc/eb_norm.hip), which `env_build_amd.norm` loads, and
+`build_offpolicy()` for env_build_amd/lib/libenvbuild_offpolicy.so (csrc/eb_offpolicy.hip), which `env_build_amd.offpolicy` loads."""
 import hashlib
 import os
 import subprocess
@@ -399,6 +400,49 @@ def build_norm(force=False, verbose=False):
         return _build_locked(verbose, NORM_LIB, NORM_SOURCES, norm_source_hash())
 
 
+# ---- libenvbuild_offpolicy.so: off-policy training — the replay ring, the SAC critic and actor rows, the action gradient and the target
+# averaging (include/envbuild_offpolicy.h).  An eighth library of its own, built the way the other six small ones are.  Its unit takes
+# splitmix64 from eb_env_device.h and exp_det from eb_mlp_device.h, so those headers and what they include are part of this library's hash
+# too (and stay in HEADERS, unchanged). ----
+OFFPOLICY_LIB = os.path.join(HERE, 'lib', 'libenvbuild_offpolicy.so')
+OFFPOLICY_SOURCES = ['eb_offpolicy.hip']
+OFFPOLICY_HEADERS = ['eb_offpolicy.h', 'eb_offpolicy_device.h', os.path.join('..', '..', 'include', 'envbuild_offpolicy.h'),
+                     'eb_mlp_device.h', 'eb_env_device.h', 'eb_device.h', 'eb_kernels.h', os.path.join('..', '..', 'include', 'envbuild.h')]
+
+
+def offpolicy_source_hash():
+    """source_hash() of the off-policy library: the flags and the bytes of OFFPOLICY_SOURCES and OFFPOLICY_HEADERS"""
+    h = hashlib.sha256()
+    h.update('\0'.join(FLAGS + ['|'] + LINK_FLAGS).encode())
+    for f in OFFPOLICY_SOURCES + OFFPOLICY_HEADERS:
+        h.update(b'\0' + f.encode() + b'\0')
+        with open(os.path.join(CSRC, f), 'rb') as fh:
+            h.update(fh.read())
+    return h.hexdigest()
+
+
+def offpolicy_needs_build():
+    try:
+        with open(OFFPOLICY_LIB + '.srchash') as fh:
+            built = fh.read().strip()
+    except OSError:
+        built = None
+    return not os.path.isfile(OFFPOLICY_LIB) or built != offpolicy_source_hash()
+
+
+def build_offpolicy(force=False, verbose=False):
+    """build() for libenvbuild_offpolicy.so"""
+    if not force and not offpolicy_needs_build():
+        return OFFPOLICY_LIB
+    import fcntl
+    os.makedirs(os.path.dirname(OFFPOLICY_LIB), exist_ok=True)
+    with open(OFFPOLICY_LIB + '.lock', 'w') as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        if not force and not offpolicy_needs_build():
+            return OFFPOLICY_LIB
+        return _build_locked(verbose, OFFPOLICY_LIB, OFFPOLICY_SOURCES, offpolicy_source_hash())
+
+
 if __name__ == '__main__':
     print(build(force=True, verbose=True))
     print(build_train(force=True, verbose=True))
@@ -407,3 +451,4 @@ if __name__ == '__main__':
     print(build_ctl(force=True, verbose=True))
     print(build_ac(force=True, verbose=True))
     print(build_norm(force=True, verbose=True))
+    print(build_offpolicy(force=True, verbose=True))
