@@ -16,7 +16,8 @@ own with its own source list and hash, which `env_build_amd.train` loads on firs
 `build_ctl()` for env_build_amd/lib/libenvbuild_ctl.so (csrc/eb_ctl.hip), which `env_build_amd.ctl` loads, and
 `build_ac()` for env_build_amd/lib/libenvbuild_ac.so (csrc/eb_ac.hip), which `env_build_amd.ac` loads, and
 `build_norm()` for env_build_amd/lib/libenvbuild_norm.so (csrc/eb_norm.hip), which `env_build_amd.norm` loads, and
-`build_offpolicy()` for env_build_amd/lib/libenvbuild_offpolicy.so (csrc/eb_offpolicy.hip), which `env_build_amd.offpolicy` loads."""
+`build_offpolicy()` for env_build_amd/lib/libenvbuild_offpolicy.so (csrc/eb_offpolicy.hip), which `env_build_amd.offpolicy` loads, and
+`build_per()` for env_build_amd/lib/libenvbuild_per.so (csrc/eb_per.hip), which `env_build_amd.per` loads."""
 import hashlib
 import os
 import subprocess
@@ -443,6 +444,51 @@ def build_offpolicy(force=False, verbose=False):
         return _build_locked(verbose, OFFPOLICY_LIB, OFFPOLICY_SOURCES, offpolicy_source_hash())
 
 
+# ---- libenvbuild_per.so: prioritised experience replay — the radix-32 sum tree over the ring's slots, the stratified draw, the importance
+# weights and the priority write-back (include/envbuild_per.h).  A ninth library of its own, built the way the other seven small ones are.
+# Its unit takes the keyed word from eb_offpolicy_device.h, log_det from eb_policy_sample_device.h, exp_det from eb_mlp_device.h and
+# splitmix64 from eb_env_device.h, so those headers and what they include are part of this library's hash too (and stay in HEADERS and
+# OFFPOLICY_HEADERS, unchanged). ----
+PER_LIB = os.path.join(HERE, 'lib', 'libenvbuild_per.so')
+PER_SOURCES = ['eb_per.hip']
+PER_HEADERS = ['eb_per.h', 'eb_per_device.h', os.path.join('..', '..', 'include', 'envbuild_per.h'),
+               'eb_offpolicy_device.h', 'eb_policy_sample_device.h', 'eb_mlp_device.h', 'eb_env_device.h', 'eb_device.h', 'eb_kernels.h',
+               os.path.join('..', '..', 'include', 'envbuild.h')]
+
+
+def per_source_hash():
+    """source_hash() of the prioritised-replay library: the flags and the bytes of PER_SOURCES and PER_HEADERS"""
+    h = hashlib.sha256()
+    h.update('\0'.join(FLAGS + ['|'] + LINK_FLAGS).encode())
+    for f in PER_SOURCES + PER_HEADERS:
+        h.update(b'\0' + f.encode() + b'\0')
+        with open(os.path.join(CSRC, f), 'rb') as fh:
+            h.update(fh.read())
+    return h.hexdigest()
+
+
+def per_needs_build():
+    try:
+        with open(PER_LIB + '.srchash') as fh:
+            built = fh.read().strip()
+    except OSError:
+        built = None
+    return not os.path.isfile(PER_LIB) or built != per_source_hash()
+
+
+def build_per(force=False, verbose=False):
+    """build() for libenvbuild_per.so"""
+    if not force and not per_needs_build():
+        return PER_LIB
+    import fcntl
+    os.makedirs(os.path.dirname(PER_LIB), exist_ok=True)
+    with open(PER_LIB + '.lock', 'w') as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        if not force and not per_needs_build():
+            return PER_LIB
+        return _build_locked(verbose, PER_LIB, PER_SOURCES, per_source_hash())
+
+
 if __name__ == '__main__':
     print(build(force=True, verbose=True))
     print(build_train(force=True, verbose=True))
@@ -452,3 +498,4 @@ if __name__ == '__main__':
     print(build_ac(force=True, verbose=True))
     print(build_norm(force=True, verbose=True))
     print(build_offpolicy(force=True, verbose=True))
+    print(build_per(force=True, verbose=True))
